@@ -10,12 +10,18 @@ esim_run_sharded, the library exchanging the commuter counts and the census itse
 `--scaling weak` keeps the per-GPU work fixed instead (a world of N x the preset).  Population build and upload are outside
 the timed region; inputs are resident in HBM when it starts.
 
-The timed region is steps 1..K (after W untimed warm-up steps and a reset).  Whatever K is, the line also carries the FULL
-5000-step run of the workload and a run that spends most of its steps under a vaccination programme (`york`, BASELINE.json
-configs[1]), each checked against the records the CPU oracle produced offline (tests/golden/), with wall and device time
-per step -- they cost milliseconds.
+The timed region is steps 1..K (after W untimed warm-up steps and a reset).  The workload is 5000 steps long: on one GPU a K
+beyond that runs it again from time step 0 (a reset between the calls, outside the timed region) until K steps have been timed.
+A plain run does only that and prints the line.  With `--full` the line also carries the device time of the timed region, its
+golden check, the FULL 5000-step run of the workload and a run that spends most of its steps under a vaccination programme
+(`york`, BASELINE.json configs[1]), each checked against the records the CPU oracle produced offline (tests/golden/), with
+wall and device time per step, the roofline of the dominant kernel and the reference-shaped CPU baseline.
 
-  python bench.py --gpus 1 --steps K --warmup W
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed: the records of its last esim_run call
+(DIR/records_<field>.npy) and, on one GPU, the citizens' state after its last step (DIR/state_<field>.npy; a fixed, seeded
+sample of the citizens when the world is larger than DUMP_STATE_SAMPLE).
+
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
 """
@@ -34,6 +40,10 @@ N_SIMD = 1024.0                         # 256 CUs x 4 SIMDs
 CENSUS = ("susceptible", "exposed", "infected", "recovered", "vaccinated")
 # the arithmetic the path computes in -- not a precision claim (RNG contract)
 DTYPE = "u32 citizen word; u32 uniform vs ceil(q*2^32) (reference: f64 uniform; tolerance 2^-32 per draw)"
+EPISODE = 5000                          # steps of the workload (DiseaseModel::max_time_step): one esim_run call at most
+DUMP_STATE_SAMPLE = 1 << 19             # citizens of the state written by --dump-outputs (all of them in a smaller world)
+DUMP_SEED = 20240611                    # the seed of that sample: the same citizens from run to run
+DUMP_MAX_BYTES = 64 << 20
 
 
 def golden_check(preset, rec, seed):
@@ -92,6 +102,50 @@ def timed_run(sim, steps, events_in_a_second_run=False):
                  "final_record": {k: int(rec[k][-1]) for k in ("time_step",) + CENSUS}}
 
 
+def run_steps(sim, steps):
+    """`steps` steps of the workload as the headline times them: calls of esim_run from time step 0, each after a reset and without
+    the library's HIP events, one call if steps <= EPISODE, else the workload again from its start for the steps past it.  Returns
+    the records of the last call and the wall seconds of the calls alone (enqueue, device work, read-back; not the resets)."""
+    rec, wall = None, 0.0
+    while steps > 0:
+        n = min(steps, EPISODE)
+        sim.reset()
+        sim.enable_kernel_timing(0)
+        sim.synchronize()
+        clock = []
+        rec = sim.run(n, clock=clock)        # esim_run returns with the n records on the host
+        wall += clock[0]
+        steps -= n
+    return rec, wall
+
+
+def state_sample(state, n_citizens):
+    """The citizens' state (Simulator.download_state) of a fixed, seeded sample of DUMP_STATE_SAMPLE citizens, or of all of them."""
+    import numpy as np
+    if n_citizens > DUMP_STATE_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_citizens, DUMP_STATE_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n_citizens)
+    return dict({k: v[idx] for k, v in state.items()}, citizen=idx)
+
+
+def write_outputs(directory, rec, state=None):
+    """--dump-outputs: the records of the timed path's last call (records_<field>.npy, float64: the counts exceed float32's 2^24)
+    and a state sample (state_<field>.npy: float64 where a value can exceed 2^24, float32 otherwise).  Returns the files written."""
+    import numpy as np
+    arrays = {"records_" + f: rec[f].astype(np.float64) for f in rec.dtype.names if f not in ("reserved", "pad")}
+    for k, v in (state or {}).items():
+        wide = v.dtype.itemsize >= 4 or v.dtype.kind not in "ub"
+        arrays["state_" + k] = v.astype(np.float64 if wide else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def cpu_baseline(pop, params, seconds, threads):
     """The reference-shaped CPU path (oracle/esim_refshape.cpp: area-parallel array-of-structs citizens, per-area hash maps,
     mutex-guarded lookup table -- the structure of sim/src/simulator.rs:87-103,167-260) on this host, on a bounded sample of the
@@ -131,13 +185,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--preset", default="uk64m", help="synthetic population preset (default: the benchmark workload)")
     ap.add_argument("--scaling", default="strong", choices=("strong", "weak"), help="N > 1: shard ONE world (strong) or a world N times the preset (weak)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time of the reference-shaped baseline sample (0 = skip)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the CPU baseline (0 = what this process may use, at most 16)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU time of the reference-shaped baseline sample (0 = skip)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: host threads of the CPU baseline (0 = what this process may use, at most 16)")
     ap.add_argument("--transport", default="rccl", choices=("rccl", "callback"), help="N > 1: the library's own RCCL communicator, or its callback transport into torch.distributed (rehearsal on one GPU)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend of the rendezvous (default gloo: it only carries the unique id, barriers and the timing maximum)")
-    ap.add_argument("--no-extra-runs", action="store_true", help="skip the full-length and vaccination-regime runs")
+    ap.add_argument("--no-extra-runs", action="store_true", help="--full: skip the full-length and vaccination-regime runs and the roofline's kernel-timed run")
     ap.add_argument("--comm-timeout", type=float, default=120.0, help="N > 1: deadline (s) of the library's waits inside a sharded run; on expiry the communicator is aborted and the line carries value null")
+    ap.add_argument("--full", action="store_true", help="besides the headline: device time of the timed region, golden checks, the full-length and "
+                                                        "vaccination-regime runs, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (this pool's driver supports dmabuf IPC only: RCCL needs it)
     import numpy as np
@@ -243,10 +302,12 @@ def main():
                                      "carries the counter-based figure"},
                 "final_record": {k: int(rec[k][-1]) for k in ("time_step",) + CENSUS},
             }
-            if args.scaling == "strong":
+            if args.full and args.scaling == "strong":
                 g = golden_check(args.preset, rec, int(params.seed))
                 if g:
                     out["golden_check"] = g
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, rec)          # the census of the whole world: every rank's records are the same
             print(json.dumps(out))
         sim.close()
         dist.destroy_process_group()
@@ -254,20 +315,35 @@ def main():
 
     # ---- one GPU: the whole workload on one context ----------------------------------------------------------------
     pop = Population.synthetic(args.preset)
-    params = _lib.default_params(max_steps=5000)
+    params = _lib.default_params(max_steps=EPISODE)
     sim = Simulator(pop, params)
-    sim.enable_kernel_timing(0)                       # (the warm-up takes the same path as the timed call: no HIP events of the library's)
-    sim.run(warmup)                                   # W untimed warm-up steps, then back to time step 0
-    rec, info = timed_run(sim, steps, events_in_a_second_run=True)
-    elapsed = info["wall_us_per_step"] * steps * 1e-6
+    run_steps(sim, warmup)                            # W untimed warm-up steps on the timed path (no HIP events of the library's)
+    rec, elapsed = run_steps(sim, steps)              # the timed region: back to time step 0, K steps
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, rec, state_sample(sim.download_state(), pop.n_citizens))
+    region = ("steps 1..%d of %d" % (steps, EPISODE) if steps <= EPISODE else
+              "%d steps: the %d steps of the workload %d times, then steps 1..%d" % (steps, EPISODE, (steps - 1) // EPISODE, len(rec)))
+    final_record = {k: int(rec[k][-1]) for k in ("time_step",) + CENSUS}
     out = {
         "metric": "citizen-timesteps/sec", "value": pop.n_citizens * steps / elapsed, "unit": "citizen-timesteps/s",
         "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-        "config": {"workload": "%s: %d citizens, %d Output Areas, %d seeds, steps 1..%d of 5000, interventions on" % (args.preset, pop.n_citizens, pop.n_areas, spec.n_seeds, steps),
-                   "seed": int(params.seed), "timed_region": info},
-        "final_record": info["final_record"],
+        "config": {"workload": "%s: %d citizens, %d Output Areas, %d seeds, %s, interventions on" % (args.preset, pop.n_citizens, pop.n_areas, spec.n_seeds, region),
+                   "seed": int(params.seed), "timed_region": {"steps": steps, "wall_us_per_step": elapsed / steps * 1e6, "final_record": final_record}},
+        "final_record": final_record,
     }
+    if not args.full:
+        print(json.dumps(out))
+        sim.close()
+        return
+    # ---- --full: the device figures of the timed region from a second, identical call of its last esim_run with the library's HIP
+    # events (the wall time stays the headline's), and its golden check
+    rec2, info = timed_run(sim, len(rec))
+    assert all((rec[k] == rec2[k]).all() for k in rec.dtype.names), "the two identical calls differ"
+    info = dict(info, steps=steps, wall_us_per_step=elapsed / steps * 1e6)
+    if steps > EPISODE:
+        info["device_figures_of_the_last_steps"] = len(rec)
+    out["config"]["timed_region"] = info
     g = golden_check(args.preset, rec, int(params.seed))
     if g:
         out["golden_check"] = g

@@ -210,7 +210,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, ESIM_BENCH_SAME_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "1300", "--warmup", "24",
-           "--preset", "york", "--transport", "callback"]
+           "--preset", "york", "--transport", "callback", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -226,9 +226,10 @@ def test_bench_two_ranks_on_one_gpu():
 
 
 def test_bench_one_gpu_line():
-    # the one-GPU line on the york preset: the contract's keys, the golden check of the timed region, the full 5000-step run, a
-    # CPU baseline sample whose records equal the GPU's
-    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--steps", "20", "--warmup", "5", "--preset", "york", "--cpu-seconds", "1"]
+    # the one-GPU line of --full on the york preset: the contract's keys, the golden check of the timed region, the full 5000-step
+    # run, a CPU baseline sample whose records equal the GPU's
+    cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--steps", "20", "--warmup", "5", "--preset", "york", "--cpu-seconds", "1",
+           "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
