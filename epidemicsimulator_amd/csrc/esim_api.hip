@@ -52,10 +52,6 @@ struct esim_ctx_impl {
     bool time_parallel = true;         // draw all steps of a chunk in one pass when its marks fit the hash map
     hipEvent_t cev[2] = { nullptr, nullptr }; double chunk_ms = 0; uint64_t chunk_steps = 0, chunk_count = 0;
     uint32_t grid_chunk = 1024;
-    // persistent item map (unsharded contexts): the host's view of it -- valid as long as nothing but map-maintaining chunk passes
-    // has been enqueued since it was (re)built; a rebuild every pmap_rebuild_every chunks sheds the items of the recovered
-    bool pmap = false, map_valid = false, pmap_used = false;      // (off by default: measured slower than the per-chunk rebuild)
-    uint32_t pmap_since_rebuild = 0, pmap_rebuild_every = 4;
     uint64_t vax_chunk_repairs = 0;
     bool quiet = false;                         // Ctrl::quiet at the last read-back of a burst of chunk passes
     bool repair_armed = false;                  // ... its two kernels are enqueued from the first cut of a run on (York never has one: 11 us a chunk saved)
@@ -200,7 +196,6 @@ extern "C" int esim_create(const esim_params *p, esim_ctx **out)
     if (!p || !out) return fail(nullptr, ESIM_EINVAL, "esim_create: null argument");
     if (p->exposed_time + p->infected_time + 2u > TE_BIAS)
         return fail(nullptr, ESIM_ERANGE, "esim_create: exposed_time + infected_time + 2 exceeds the state encoding (512)");
-    static_assert(SCH_RING >= TE_BIAS + 2u * FREE_MAX, "the school rings must hold an Infected window and two chunks");
     if (p->vaccination_rate > VACC_MAX_RATE)
         return fail(nullptr, ESIM_ERANGE, "esim_create: vaccination_rate above 8192 is not supported");
     if (p->bus_capacity == 0 || p->start_hour == 0 || p->end_hour == 0 || p->start_hour > 24 || p->end_hour > 24)
@@ -458,8 +453,6 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
                 for (uint32_t b = 0; b < B; ++b) if (pop->building_type[b] == ESIM_SCHOOL) sch_of[b] = (int32_t)n_sch++;
                 d.n_sch = n_sch;
                 if ((rc = dev_upload(c, &d.sch_of_bld, sch_of.data(), sch_of.size()))) return rc;
-                if ((rc = dev_alloc(c, &d.sch_ring, (size_t)(n_sch ? n_sch : 1) * 2u * SCH_RING))) return rc;
-                HIP_TRY(c, hipMemset(d.sch_ring, 0, sizeof(uint32_t) * (size_t)(n_sch ? n_sch : 1) * 2u * SCH_RING));
             }
             {
                 // the records k_chunk_marks reads with one request each (Dev::where4, Dev::bld8), and the schools' difference arrays
@@ -474,9 +467,7 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
                 HIP_TRY(c, hipMemset(d.sch_diff, 0, sizeof(uint32_t) * sd));
             }
             d.ovf_room_base = ovf_off.back();
-            // (the persistent map keeps two places per member -- a record and a cancellation -- and the routes' riders behind the rooms)
-            d.ovf_route_base = d.ovf_room_base + room_off.back();
-            d.ovf_n = 2u * (d.ovf_route_base + (uint32_t)riders.size()) + 2u;
+            d.ovf_n = d.ovf_room_base + room_off.back() + 1u;
             if ((rc = dev_alloc(c, &d.ovf, (size_t)d.ovf_n))) return rc;
             HIP_TRY(c, hipMemset(d.ovf, 0, sizeof(uint32_t) * (size_t)d.ovf_n));
         }
@@ -484,12 +475,6 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
         d.big_qcap = d.items_cap / SUBQ;             // (a slot is listed at most once a chunk, and there are at most items_cap of them)
         if ((rc = dev_alloc(c, &d.big_list, (size_t)d.big_qcap * SUBQ * 3u))) return rc;
         if ((rc = dev_alloc(c, &d.used_pref, CHUNK_WAVES_MAX + 1u))) return rc;
-        if ((rc = dev_alloc(c, &d.pbig_cnt, SUBQ))) return rc;
-        if ((rc = dev_alloc(c, &d.neg_list, (size_t)NEG_CAP * 2u))) return rc;
-        if ((rc = dev_alloc(c, &d.cancel_list, (size_t)NEG_CAP * 2u))) return rc;
-        HIP_TRY(c, hipMemset(d.cancel_list, 0, sizeof(uint32_t) * (size_t)NEG_CAP * 2u));
-        HIP_TRY(c, hipMemset(d.pbig_cnt, 0, sizeof(uint32_t) * SUBQ));
-        HIP_TRY(c, hipMemset(d.neg_list, 0, sizeof(uint32_t) * (size_t)NEG_CAP * 2u));
         HIP_TRY(c, hipMemset(d.big_list, 0, sizeof(uint32_t) * (size_t)d.big_qcap * SUBQ * 3u));
         HIP_TRY(c, hipMemset(d.used_pref, 0, sizeof(uint32_t) * (CHUNK_WAVES_MAX + 1u)));
         if ((rc = dev_alloc(c, &d.pair_cnt, 16384u))) return rc;
@@ -605,8 +590,6 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if (const char *e = std::getenv("ESIM_TINY_PAIRS")) c->tiny_pairs = (uint32_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("ESIM_SMALL_GRID")) c->small_grid = (uint32_t)std::max(0, std::atoi(e) / 16 * 16);
     if (const char *e = std::getenv("ESIM_SMALL_MULT")) c->small_mult = (uint32_t)std::min(16, std::max(1, std::atoi(e)));
-    if (const char *e = std::getenv("ESIM_PMAP")) c->pmap = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ESIM_PMAP_REBUILD")) c->pmap_rebuild_every = (uint32_t)std::max(1, std::atoi(e));
     if (const char *e = std::getenv("ESIM_DRAW_MULT")) c->draw_mult = (uint32_t)std::min(4, std::max(1, std::atoi(e)));      // (16 384 wavefronts at most: Dev::pair_cnt)
     if (const char *e = std::getenv("ESIM_UNITS_MULT")) c->units_mult = (uint32_t)std::min(16, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("ESIM_GRID_EXPOSE")) c->grid_expose = (uint32_t)std::max(1, std::atoi(e));
@@ -643,7 +626,6 @@ extern "C" int esim_reset(esim_ctx *ctx)
     HIP_TRY(c, hipMemcpy(d.log_off, off.data(), sizeof(uint32_t) * (TE_SLOTS + 1), hipMemcpyHostToDevice));
     if (n_seeds) HIP_TRY(c, hipMemcpy(d.log, c->init_log.data(), sizeof(uint32_t) * n_seeds, hipMemcpyHostToDevice));
     c->host_t = 1;
-    c->map_valid = false;                         // (the device arrays may still hold the last run's map: the first chunk clears them)
     c->stop_flag_dev = 0;
     c->pin_track = false;
     c->free_limit = 0;
@@ -818,7 +800,6 @@ int run_sequential(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, ui
     Dev &d = c->d;
     c->ctrl_fresh = false;                   // (whatever a burst read back is out of date once more steps are enqueued)
     c->quiet = false;
-    c->map_valid = false;                    // (sequential steps do not maintain the persistent item map)
     uint32_t remaining = n_steps, total = 0;
     int rc;
     while (remaining > 0) {
@@ -874,48 +855,25 @@ void kd_resolve(esim_ctx_impl *c)
 // While few citizens are Infected the books, the log scatter, the clean-up and that preparation are ONE single-workgroup
 // kernel (a kernel boundary costs more than these steps); with many, the scatter and clean-up need the whole chip.
 // then_next: 0 nothing, 1 census ahead + decisions of the next chunk, 2 census ahead only.
-// marks -> fold -> draw -> units of one chunk: on the persistent item map (unsharded contexts; k_map_enter only enters who turns
-// Infected in the chunk, after a k_map_clear everybody who is Infected in it) or with the map rebuilt and torn down per chunk
-// (sharded contexts, ESIM_PMAP=0).
+// marks -> fold -> draw -> units of one chunk: the item map is built by k_chunk_marks and torn down by k_chunk_scatter.
 // A chunk with few Infected is nothing but the latency of its kernels: those run on 64 workgroups instead of 1024 then (measured
 // on york, whose chunks are all of that kind: 3.56 instead of 4.0 ms for the 5000 steps).  The choice follows what the last
 // read-back showed, so bursts are kept short while it is in force (the epidemic may double within a hundred steps).
-bool tiny_chunk(const esim_ctx_impl *c) { return c->tiny_pairs && c->last_chunk_pairs <= c->tiny_pairs && c->d.world == 1u && c->d.n_shards == 1u && !c->pmap; }
+bool tiny_chunk(const esim_ctx_impl *c) { return c->tiny_pairs && c->last_chunk_pairs <= c->tiny_pairs && c->d.world == 1u && c->d.n_shards == 1u; }
 bool small_chunk(const esim_ctx_impl *c) { return c->small_grid && c->last_chunk_pairs < 4096u && c->grid_chunk > c->small_grid && !std::getenv("ESIM_GRID_CHUNK"); }
 
 void enqueue_chunk_front(esim_ctx_impl *c)
 {
     Dev &d = c->d;
-    const bool pm = c->pmap && d.world == 1u;
     const uint32_t g = small_chunk(c) ? c->small_grid : c->grid_chunk, g_draw = g * (small_chunk(c) ? c->small_mult : c->draw_mult), g_units = g * (small_chunk(c) ? c->small_mult : c->units_mult);
-    if (pm) {
-        if (!c->map_valid || c->pmap_since_rebuild >= c->pmap_rebuild_every) {
-            kd_mark(c, ESIM_CK_MAP_CLEAR);
-            hipLaunchKernelGGL(k_map_clear, dim3(COUNT_GRID), dim3(TPB), 0, c->stream, d);
-            hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, c->stream, d);
-            (void)hipMemsetAsync(d.sch_ring, 0, sizeof(uint32_t) * (size_t)(d.n_sch ? d.n_sch : 1) * 2u * SCH_RING, c->stream);
-            c->pmap_since_rebuild = 0;
-        }
-        c->map_valid = true; c->pmap_used = true; c->pmap_since_rebuild++;
-        kd_mark(c, ESIM_CK_MARKS);
-        hipLaunchKernelGGL(k_map_enter, dim3(g), dim3(TPB), 0, c->stream, d);
-        kd_mark(c, ESIM_CK_FOLD);
-        hipLaunchKernelGGL(k_chunk_fold<true>, dim3(g), dim3(TPB), 0, c->stream, d);
-        kd_mark(c, ESIM_CK_DRAW);
-        hipLaunchKernelGGL(k_chunk_draw<true>, dim3(g_draw), dim3(TPB), 0, c->stream, d, SUBQ);
-        kd_mark(c, ESIM_CK_UNITS);
-        hipLaunchKernelGGL(k_chunk_units<true>, dim3(g_units), dim3(TPB), 0, c->stream, d);
-        return;
-    }
-    c->map_valid = false;
     kd_mark(c, ESIM_CK_MARKS);
     hipLaunchKernelGGL(k_chunk_marks, dim3(g), dim3(TPB), 0, c->stream, d);
     kd_mark(c, ESIM_CK_FOLD);
-    hipLaunchKernelGGL(k_chunk_fold<false>, dim3(g), dim3(TPB), 0, c->stream, d);
+    hipLaunchKernelGGL(k_chunk_fold, dim3(g), dim3(TPB), 0, c->stream, d);
     kd_mark(c, ESIM_CK_DRAW);
-    hipLaunchKernelGGL(k_chunk_draw<false>, dim3(g_draw), dim3(TPB), 0, c->stream, d, g * (TPB / 64u));
+    hipLaunchKernelGGL(k_chunk_draw, dim3(g_draw), dim3(TPB), 0, c->stream, d, g * (TPB / 64u));
     kd_mark(c, ESIM_CK_UNITS);
-    hipLaunchKernelGGL(k_chunk_units<false>, dim3(g_units), dim3(TPB), 0, c->stream, d);
+    hipLaunchKernelGGL(k_chunk_units, dim3(g_units), dim3(TPB), 0, c->stream, d);
 }
 
 void enqueue_parallel_chunk(esim_ctx_impl *c, int then_next, uint32_t limit_t)
@@ -936,7 +894,7 @@ void enqueue_parallel_chunk(esim_ctx_impl *c, int then_next, uint32_t limit_t)
 void enqueue_vax_chunk(esim_ctx_impl *c, uint32_t limit_t)
 {
     Dev &d = c->d;
-    if (c->quiet && !(c->pmap && d.world == 1u) && d.world == 1u) {
+    if (c->quiet && d.world == 1u) {
         // Nobody is Exposed or Infected any more (the last read-back said so, and nobody is infected from outside): what is left of the
         // run is the vaccination programme.  No marks, no draws, nothing to scatter: the plan, the decisions, the census the
         // vaccinations move, the books, the words (York: the last 3400 of its 5000 steps are of this kind).
@@ -944,7 +902,6 @@ void enqueue_vax_chunk(esim_ctx_impl *c, uint32_t limit_t)
         hipLaunchKernelGGL(k_chunk_vax<false>, dim3(FREE_MAX + 1u), dim3(FIN_TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 0);
         kd_mark(c, ESIM_CK_DECIDE);
         hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1, 0);
-        c->map_valid = false;
         kd_mark(c, ESIM_CK_COUNT);
         hipLaunchKernelGGL(k_chunk_count, dim3(COUNT_GRID), dim3(TPB), 0, c->stream, d);
         kd_mark(c, ESIM_CK_BOOKS);
@@ -956,23 +913,10 @@ void enqueue_vax_chunk(esim_ctx_impl *c, uint32_t limit_t)
     }
     kd_mark(c, ESIM_CK_VAX);
     hipLaunchKernelGGL(k_chunk_vax<false>, dim3(FREE_MAX + 1u), dim3(FIN_TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 0);   // (+ the census ahead)
-    // (persistent map: a rebuild has to be decided BEFORE the plan's cancellation records go into the map)
-    const bool pm = c->pmap && d.world == 1u;
-    if (pm && (!c->map_valid || c->pmap_since_rebuild >= c->pmap_rebuild_every)) {
-        kd_mark(c, ESIM_CK_MAP_CLEAR);
-        hipLaunchKernelGGL(k_map_clear, dim3(COUNT_GRID), dim3(TPB), 0, c->stream, d);
-        hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, c->stream, d);
-        (void)hipMemsetAsync(d.sch_ring, 0, sizeof(uint32_t) * (size_t)(d.n_sch ? d.n_sch : 1) * 2u * SCH_RING, c->stream);
-        c->pmap_since_rebuild = 0; c->map_valid = true;
-    }
-    if (pm) {                                     // (the plan's vaccinations of citizens the persistent map holds: noted for k_map_enter)
-        kd_mark(c, ESIM_CK_VAX_ADJ);
-        hipLaunchKernelGGL(k_chunk_vax_adj, dim3(FREE_MAX), dim3(TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1);
-    }
     kd_mark(c, ESIM_CK_DECIDE);
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1, 0);
     enqueue_chunk_front(c);
-    if (!pm && d.world == 1u && c->vax_repair && (c->repair_armed || c->vax_repair_always)) {
+    if (d.world == 1u && c->vax_repair && (c->repair_armed || c->vax_repair_always)) {
         // bus exposures of citizens the plan vaccinates later: the plan of the steps behind is repaired instead of the chunk being cut
         kd_mark(c, ESIM_CK_VAX_REPAIR);
         hipLaunchKernelGGL(k_chunk_lost, dim3(1), dim3(FIN_TPB), 0, c->stream, d);
@@ -1013,19 +957,11 @@ int run_chunk(esim_ctx_impl *c, uint32_t n_ahead, uint32_t *executed, Ctrl *stat
         enqueue_parallel_chunk(c, 0, 0u);
         if (tk) { HIP_TRY(c, hipEventRecord(c->cev[1], c->stream)); HIP_TRY(c, hipEventSynchronize(c->cev[1])); float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1])); c->chunk_ms += ms; }
         HIP_TRY(c, hipGetLastError());
-        // The chunk takes itself back when the persistent map cannot serve it (k_map_enter: a map built under a lockdown, and a
-        // schedule with working hours): what was executed is read, not assumed; the map is rebuilt and the chunk enqueued again.
+        // (what was executed is read, not assumed)
         Ctrl after;
         int rc2 = read_ctrl(c, &after);
         if (rc2) return rc2;
         if (after.error) return fail(c, -(int)after.error, "device-side error (raised at check " + std::to_string(after.err_where) + ")");
-        if (after.t == t0 && c->map_valid) {
-            c->map_valid = false;
-            hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, n_ahead, c->P.max_steps, 1, 0);
-            enqueue_parallel_chunk(c, 0, 0u);
-            if ((rc2 = read_ctrl(c, &after))) return rc2;
-            if (after.error) return fail(c, -(int)after.error, "device-side error (raised at check " + std::to_string(after.err_where) + ")");
-        }
         const uint32_t ran = after.t - t0;
         c->chunk_steps += ran; c->chunk_count += ran ? 1u : 0u;
         *executed = ran;
@@ -1093,7 +1029,6 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             if (h.finished && allow_early_stop) break;
             if (remaining == 0) break;
             if (done) { vax_fail = 0; continue; }                       // (cut chunks advance less; the next one starts at the cut)
-            c->map_valid = false;                                        // (no progress: whatever the reason, the map is rebuilt next)
             if (std::getenv("ESIM_DEBUG"))
                 std::fprintf(stderr, "[esim] vax burst without progress at t=%u: chunk_ok=%u parallel=%u vax_chunk=%u cut=%u pairs=%u fits_flag=%u elig=%u bursts=%u\n",
                              h.t, h.chunk_ok, h.chunk_parallel, h.vax_chunk, h.chunk_cut, h.chunk_pairs, 0u, h.elig_count, bursts);
@@ -1116,7 +1051,6 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             if (tiny_chunk(c)) {
                 // few Infected: every chunk of the burst is ONE launch of one workgroup (esim_kernels_tiny.h); a chunk that has
                 // outgrown that form does not advance, which the read-back below sees
-                c->map_valid = false;
                 for (uint32_t g = 0; g < bursts; ++g) {
                     kd_mark(c, ESIM_CK_TINY);
                     hipLaunchKernelGGL(k_chunk_tiny, dim3(1), dim3(FIN_TPB), 0, c->stream, d, g == 0u ? 1 : 0, g + 1u < bursts ? 1 : 0, (uint32_t)c->xf_n, limit_t);
@@ -1139,7 +1073,7 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             if (tk && done) { float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1])); c->chunk_ms += ms; c->chunk_steps += done; c->chunk_count += (done + (uint32_t)c->xf_n - 1u) / (uint32_t)c->xf_n; }
             c->host_t = h.t; total += done; remaining -= done;
             if (h.finished) break;
-            if (done == 0) { backoff = std::min<uint32_t>(64u, backoff ? backoff * 2u : 1u); sync_chunks_left = backoff; probing = true; c->map_valid = false; }   // (e.g. a map built under a lockdown: rebuilt next)
+            if (done == 0) { backoff = std::min<uint32_t>(64u, backoff ? backoff * 2u : 1u); sync_chunks_left = backoff; probing = true; }
             else { backoff = 0; probing = done < std::min<uint32_t>(remaining + done, bursts * (uint32_t)c->xf_n); }
             if (done < std::min<uint32_t>(remaining + done, bursts * (uint32_t)c->xf_n)) stalled = true;   // something other than a full time-parallel chunk is next
             continue;
@@ -1598,9 +1532,9 @@ int enqueue_sharded_chunk(esim_ctx_impl *c, uint32_t limit_t, bool vax)
     if ((rc = exchange(c, 2))) return rc;
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1, 1);
     hipLaunchKernelGGL(k_chunk_marks, dim3(c->grid_chunk), dim3(TPB), 0, c->stream, d);
-    hipLaunchKernelGGL(k_chunk_fold<false>, dim3(c->grid_chunk), dim3(TPB), 0, c->stream, d);
-    hipLaunchKernelGGL(k_chunk_draw<false>, dim3(c->grid_chunk * c->draw_mult), dim3(TPB), 0, c->stream, d, c->grid_chunk * (TPB / 64u));
-    hipLaunchKernelGGL(k_chunk_units<false>, dim3(c->grid_chunk * c->units_mult), dim3(TPB), 0, c->stream, d);
+    hipLaunchKernelGGL(k_chunk_fold, dim3(c->grid_chunk), dim3(TPB), 0, c->stream, d);
+    hipLaunchKernelGGL(k_chunk_draw, dim3(c->grid_chunk * c->draw_mult), dim3(TPB), 0, c->stream, d, c->grid_chunk * (TPB / 64u));
+    hipLaunchKernelGGL(k_chunk_units, dim3(c->grid_chunk * c->units_mult), dim3(TPB), 0, c->stream, d);
     if (vax && c->vax_repair && (c->repair_armed || c->vax_repair_always)) {
         // the repair of the plan (DESIGN.md 3.13 v), sharded: the shards agree on the step to walk again from (buffer L), exchange
         // the liveness of the candidates as it truly stood (buffer V a second time) and walk the same steps again
@@ -1657,13 +1591,6 @@ extern "C" int esim_run_sharded(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_don
     // different steps would issue different collectives): a flag an earlier esim_run left on the device is cleared
     static const uint32_t zero = 0u;
     HIP_TRY(c, hipMemcpyAsync(&d.ctrl->stop_when_done, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
-    if (c->pmap_used) {                              // (a persistent map left by esim_run: the chunk pass of sharded runs builds its own per chunk)
-        hipLaunchKernelGGL(k_map_clear, dim3(COUNT_GRID), dim3(TPB), 0, c->stream, d);
-        hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, c->stream, d);
-        (void)hipMemsetAsync(d.sch_ring, 0, sizeof(uint32_t) * (size_t)(d.n_sch ? d.n_sch : 1) * 2u * SCH_RING, c->stream);
-        c->pmap_used = false;
-    }
-    c->map_valid = false;
     // (a communicator on an unsharded context -- one rank -- still makes its collectives: the sums over one rank change nothing,
     // which is how the RCCL path is exercised on a one-GPU box)
     const bool ex = d.n_shards > 1 || c->nccl || c->comm_fn;
@@ -1813,16 +1740,6 @@ extern "C" int esim_set_pipeline(esim_ctx *ctx, int enable)
     c->pipeline = enable != 0;            // 0: sequential steps only
     c->time_parallel = enable >= 2;       // 1: one kernel per step (k_pipe); 2: all steps of a chunk in one pass
     c->vax_chunks = enable >= 3;          // 3 (default): ... also while a vaccination programme runs, its vaccinations planned per chunk
-    if (enable >= 4 && !c->pmap) { c->pmap = true; c->map_valid = false; }   // 4: ... on the persistent item map (unsharded contexts)
-    if (enable < 4 && c->pmap && !std::getenv("ESIM_PMAP")) {                // back to the per-chunk map: whatever the persistent one holds is emptied first
-        if (c->pmap_used && c->uploaded) {
-            hipLaunchKernelGGL(k_map_clear, dim3(COUNT_GRID), dim3(TPB), 0, c->stream, c->d);
-            hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, c->stream, c->d);
-            (void)hipMemsetAsync(c->d.sch_ring, 0, sizeof(uint32_t) * (size_t)(c->d.n_sch ? c->d.n_sch : 1) * 2u * SCH_RING, c->stream);
-            c->pmap_used = false;
-        }
-        c->pmap = false; c->map_valid = false;
-    }
     return ESIM_OK;
 }
 
@@ -1901,7 +1818,7 @@ extern "C" int esim_debug_counters(esim_ctx *ctx, uint32_t out[16])
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     Ctrl h;
     HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
-    const uint32_t v[16] = { h.t, h.chunk_ok, h.chunk_parallel, h.chunk_pairs, h.n_items, h.items_per_wave, h.n_units, h.n_route_pairs,
+    const uint32_t v[16] = { h.t, h.chunk_ok, h.chunk_parallel, h.chunk_pairs, h.n_items, h.items_per_wave, h.n_units, 0u,
                              h.n_route_pairs_big, h.n_newexp, h.log_len, h.n_susceptible, h.lockdown, h.mask, h.at_work, h.bus_dir };
     std::memcpy(out, v, sizeof v);
     return ESIM_OK;
@@ -2189,9 +2106,8 @@ extern "C" int esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t by
     if (h.t != k.host_t || h.log_len != k.log_len || h.error != 0u || h.steps_done + 1u != k.host_t || h.n_susceptible > k.n || h.n_vaccinated > k.n)
         return fail(c, ESIM_EINVAL, "esim_checkpoint_restore: the control block does not match the checkpoint's header (corrupt file)");
     h.chunk_ok = 0; h.chunk_parallel = 0; h.chunk_done = 0; h.n_items = 0; h.n_newexp = 0; h.n_units = 0; h.unit_next = 0;
-    h.n_route_pairs = 0; h.n_route_pairs_big = 0; h.prev_n_items = 0; h.prev_per_wave = 0; h.items_per_wave = 0; h.small_done = 0;
+    h.n_route_pairs_big = 0; h.prev_n_items = 0; h.prev_per_wave = 0; h.items_per_wave = 0; h.small_done = 0;
     h.free_base = 0; h.n_riders = 0; h.peer_error = 0;
-    h.map_t = 0; h.pmap_chunk = 0; h.prev_pmap = 0; h.n_neg = 0; h.n_cancel = 0; h.map_work = 0;        // (the item map is derived state: the next chunk rebuilds it)
     for (int z = 0; z < 5; ++z) h.counts[z] = 0;
     // marks of the last step are only ever cleared, never read, by the step after it: start without them
     for (uint32_t z = 0; z < MARK_SLOTS; ++z) { h.n_touched_bld[z] = 0; h.n_touched_room[z] = 0; h.n_touched_route[z] = 0; h.n_touched_route_big[z] = 0; }

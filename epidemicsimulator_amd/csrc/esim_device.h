@@ -11,8 +11,6 @@
 // bits 17..11  vax : only inside a time-parallel chunk that runs under a vaccination programme: 127 - j when the citizen
 //                   is set Vaccinated at the END of step j of the chunk (simulator.rs:524-553), 0 = not in this chunk.  The
 //                   earliest such step wins by atomicMax; k_chunk_scatter turns it into te = TE_VACCINATED and clears it.
-// bit  9       in_map : the persistent item map holds this citizen's records (set when it is entered, k_map_enter; meaningless while
-//                   Ctrl::map_t does not equal the chunk's first step: a rebuild clears the bits of everybody it may concern)
 // bit  10      plan_skip : the citizen is Susceptible and WILL be exposed on public transport in the step at ctrl->t (a chunk was
 //                   cut there, k_chunk_vax): it leaves citizens_eligible_for_vaccine in that step, so the next plan must not
 //                   choose it.  Any exposure drops the bit.
@@ -30,7 +28,6 @@
 #define CW_KEEP        (CW_FLAGS | CW_VAX_MASK)            // what an exposure inside a chunk leaves as it is
 #define CW_VAX_NONE    0xFFFFFFFFu
 #define CW_PLAN_SKIP   (1u << 10)
-#define CW_IN_MAP      (1u << 9)    // persistent item map (k_map_enter): the citizen's records have been entered into the items it stands in
 // step of the chunk at whose end the citizen becomes Vaccinated (CW_VAX_NONE: not in this chunk)
 #define CW_VAX_REL(w)  ((((w) >> CW_VAX_SHIFT) & 0x7Fu) ? 127u - (((w) >> CW_VAX_SHIFT) & 0x7Fu) : CW_VAX_NONE)
 #define CW_VAX_FIELD(j) ((127u - (j)) << CW_VAX_SHIFT)
@@ -92,15 +89,13 @@ struct Ctrl {
     uint32_t n_items;           // marked (building | room | route, step) entries of the chunk
     uint32_t n_newexp;          // citizens exposed in the chunk
     uint32_t n_units, unit_next; // deferred units of the last chunk (diagnostics; the queues' own counters live in Dev::hot)
-    uint32_t n_route_pairs;     // (unused: those pairs are counted per wavefront, Dev::pair_cnt)
-    uint32_t n_route_pairs_big; // ... routes of more riders
+    uint32_t n_route_pairs_big; // (route, bus step) pairs of routes of more than 64 riders (those of shorter routes are counted per wavefront, Dev::pair_cnt)
     uint32_t chunk_done;        // the books of the last time-parallel chunk were written (k_chunk_books)
     uint32_t prev_t0, prev_n_items, prev_per_wave; // that chunk, for k_chunk_scatter
     // time-parallel chunks under a vaccination programme (k_chunk_vax)
     uint32_t vax_chunk;         // 1: the chunk in preparation has its vaccinations planned (events in Dev::vax_ev, fields in the words)
     uint32_t chunk_cut;         // first step of the chunk (relative) that must NOT be committed: a citizen exposed on a bus there had been
                                 // planned for vaccination at or after it (it left the eligible set, simulator.rs:447-449) -- FREE_MAX + 1: none
-    uint32_t need_seq;          // (unused: the step of a cut needs no special form, see CW_PLAN_SKIP)
     uint32_t prev_cut;          // the chunk k_chunk_scatter is finishing was cut at prev_n_eff
     uint32_t prev_n, prev_n_eff, prev_vax; // the chunk k_chunk_scatter is finishing: its length, the steps committed, whether it was planned
     uint32_t vax_cuts;          // diagnostics: chunks that were cut short
@@ -108,15 +103,6 @@ struct Ctrl {
     uint32_t xs_need;           // sharded chunks: the most commuter records THIS shard saw in one segment of the chunk last prepared
     uint32_t xs_need_all;       // ... any shard did (summed by slot in the status exchange: the segments grow by the same factor everywhere)
     uint32_t vax_fail;          // sharded plans: steps whose candidates beyond the exchanged window would have been needed (plan void)
-    // persistent item map: valid for a chunk that starts at step map_t -- every form that advances the clock
-    // without maintaining the map (sequential steps, k_pipe chunks, a restore) leaves map_t behind and so invalidates it
-    uint32_t map_t;
-    uint32_t chunk_e0;          // log entries [chunk_e0, chunk_i1): exposure steps that BECOME Infected in some step of the chunk (k_decide)
-    uint32_t n_neg;             // cancellation records appended for this chunk's plan (Dev::neg_list)
-    uint32_t n_cancel;          // planned vaccinations of citizens the map holds (Dev::cancel_list), noted by k_chunk_vax_adj
-    uint32_t pmap_chunk;        // the chunk in flight runs on the persistent map (k_map_enter decided)
-    uint32_t prev_pmap;         // ... and the chunk k_chunk_scatter is finishing did
-    uint32_t map_work;          // the map holds work buildings, rooms and routes too (it was built for a schedule with working hours)
     uint32_t err_where;         // diagnostics: which check raised `error` (ERR_AT_*), reported in esim_last_error
     uint32_t peer_error;        // sharded runs: the error fields of ALL shards, summed (ERR_FIELD): every rank takes its return code
                                 // from this word, so that all leave esim_run_sharded together (k_status_unpack)
@@ -211,18 +197,9 @@ struct Dev {
     uint32_t *ovf;              // [ovf_n = ovf_room_base + room_off[n_room] + 1]
     uint32_t ovf_n;
     uint32_t n_wrk_idx, n_room_idx;   // lengths of wrk_idx / room_idx (what a member range read from a chunk table is checked against)
-    // persistent item map: per-sub-list cursors of the slots listed for k_map_fold (those with records in `ovf`), the addresses of
-    // this chunk's cancellation records (so that those of uncommitted steps can be taken back)
-    uint32_t *pbig_cnt;         // [SUBQ]
-    uint32_t *neg_list;         // [NEG_CAP][2] word index (bit 31: in `ovf`, else in `slot_iv`), step of the chunk
-    uint32_t *cancel_list;      // [NEG_CAP][2] citizen, step of the chunk
-    // school buildings of the persistent map: instead of one record per Infected member (hundreds in one list when the epidemic
-    // sits in a few catchments), two histograms of exposure steps per school -- everybody, and those who ride public transport --
-    // in rings of SCH_RING steps: how many members are Infected in a step is a window sum over them, like the census
     const int32_t *sch_of_bld;  // [n_bld] dense school index, -1: not a school
-    uint32_t *sch_ring;         // [n_sch][2][SCH_RING]
     uint32_t n_sch;
-    // school buildings of the per-chunk map: everybody Infected in one adds its stretch of the chunk to a DIFFERENCE array of the
+    // school buildings: everybody Infected in one adds its stretch of the chunk to a DIFFERENCE array of the
     // school (+1 at its first step, -1 behind its last; a second array for those who ride public transport) instead of one
     // counter atomic per step; SD_REPL copies by adding wavefront, so that the hundreds of Infected of one school do not queue
     // on one address; k_chunk_fold sums them up into the slot's `vec` and zeroes them
@@ -230,7 +207,6 @@ struct Dev {
     // what k_chunk_marks needs of a citizen / of a building in one 16- / 32-byte record (one memory request instead of four / three)
     const uint4 *where4;        // [n] home building, work building, room, route (as home / work / room / route_of)
     const struct BldRec *bld8;  // [n_bld]
-    uint32_t ovf_route_base;    // records of a route's Infected riders: ovf[2 * (ovf_route_base + route_off[r]) ...)
     uint32_t *big_list;         // [SUBQ][big_qcap][3] slots with records in `ovf`, where those start and how many fit, listed by the first
                                 // to put one there; 64 lists by listing wavefront & 63, lengths in hot[HOT_BIG ...]
     uint32_t big_qcap;
@@ -315,18 +291,15 @@ struct Dev {
 #define HOT_UNITS 64u              // [SUBQ] deferred units, by producing wavefront & 63
 #define HOT_BIGPAIRS 128u          // (route, bus step) pairs of routes with more than 64 riders
 #define HOT_BIG 129u               // [SUBQ] slots listed for k_chunk_fold, by listing wavefront & 63
-#define HOT_RPAIRS 193u            // [SUBQ] persistent map: (route of <= 64 riders, bus step) pairs k_chunk_draw registered for k_chunk_units, by wavefront & 63
+                                   // (193 .. 256: unused)
 #define HOT_PREV_NEWEXP 257u       // [SUBQ] copy of HOT_NEWEXP of the chunk whose log entries k_chunk_scatter is writing
 #define HOT_RESET 257u             // counters k_decide zeroes for a new chunk
 #define HOT_LOST 321u               // citizens exposed on a bus while the chunk's plan had a vaccination for them (Dev::lost_list; zeroed by k_chunk_vax)
 #define HOT_COUNT 322u
 // where a device-side error was raised (Ctrl::err_where)
 #define RAISE(ctrl, code, where) do { (ctrl)->error = (uint32_t)(-(code)); (ctrl)->err_where = (where); } while (0)
-enum { ERR_AT_OVF_FULL = 1, ERR_AT_BIG_LIST, ERR_AT_NEG_LIST, ERR_AT_ITEM_IDS, ERR_AT_HASH_FULL, ERR_AT_ITEM_CHECK, ERR_AT_ROUTE_ITEM, ERR_AT_MAP_STATE,
-       ERR_AT_CANCEL_SLOT, ERR_AT_BIGPAIRS, ERR_AT_SCHOOL };
-#define SCH_RING 1024u             // >= exposed_time + infected_time + 2 + 2 * FREE_MAX
-#define PBIG_STRIDE 4u             // words per entry of the persistent map's fold list: slot, overflow base, capacity | school flag, school
-#define NEG_CAP (1u << 18)          // cancellation records per chunk (a chunk plans at most 96 x 8192 vaccinations, few of them of Infected citizens)
+// (the numbers stay what they were when they were written to logs: 1, 3, 4, 5, 8 and 9 were checks of the persistent item map)
+enum { ERR_AT_BIG_LIST = 2, ERR_AT_ITEM_CHECK = 6, ERR_AT_ROUTE_ITEM = 7, ERR_AT_BIGPAIRS = 10, ERR_AT_SCHOOL = 11 };
 #define UNIT_NOOP 0xFFFFFFFFu
 #ifndef LOST_CAP
 #define LOST_CAP 8192u              // entries of Dev::lost_list (more: k_chunk_lost looks at everybody exposed in the chunk instead; -DLOST_CAP=2 tested)

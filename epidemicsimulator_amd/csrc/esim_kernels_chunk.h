@@ -88,7 +88,7 @@ __device__ __forceinline__ void decide_body(const Dev &d, uint32_t max_ahead, ui
     // under a vaccination programme only a chunk whose vaccinations are planned may run (k_chunk_vax); the Infected census ahead
     // then loses those the plan vaccinates before (prefix sums of xf_adj)
     const bool vax = ld(&ctrl->have_elig) != 0u;
-    const bool ok = (vax ? (ld(&ctrl->vax_chunk) != 0u && ld(&ctrl->vax_fail) == 0u) : !ld(&ctrl->vacc_active)) && !ld(&ctrl->need_seq) && !ld(&ctrl->finished) && !ld(&ctrl->error) && ld(&ctrl->free_base) == t0;
+    const bool ok = (vax ? (ld(&ctrl->vax_chunk) != 0u && ld(&ctrl->vax_fail) == 0u) : !ld(&ctrl->vacc_active)) && !ld(&ctrl->finished) && !ld(&ctrl->error) && ld(&ctrl->free_base) == t0;
     uint32_t adj[2] = { 0u, 0u };
     if (vax && ok && !adj_folded) {                       // (sharded: folded into buffer F before its all-reduce, k_shard_prep)
         uint32_t carry = 0u;
@@ -219,17 +219,12 @@ __device__ __forceinline__ void decide_body(const Dev &d, uint32_t max_ahead, ui
         const int hi_te = (int)(t0 + n_ok + TE_BIAS) - (int)d.exposed_time - 2;
         ctrl->chunk_i0 = (hi_te < 0 || n_ok == 0u) ? 0u : ld(&d.log_off[lo_te < 0 ? 0 : lo_te]);
         ctrl->chunk_i1 = (hi_te < 0 || n_ok == 0u) ? 0u : ld(&d.log_off[hi_te + 1]);
-        // ... and of those that TURN Infected in it (exposure steps from the one whose stretch starts in step 0): what the
-        // persistent map has to enter
-        const int e_te = (int)(t0 + TE_BIAS) - (int)d.exposed_time - 1;
-        ctrl->chunk_e0 = (hi_te < 0 || n_ok == 0u) ? 0u : ld(&d.log_off[e_te < 0 ? 0 : e_te]);
-        ctrl->pmap_chunk = 0u;
         // riders are on a bus in at most CHUNK_BUS_STEPS steps of a one-pass chunk (two a day unless a lockdown froze them
         // there, Q8): that bounds the (route, bus step) pairs a wavefront of k_chunk_marks can register.  The same on all shards.
         const uint32_t bus_steps = (uint32_t)(__popcll(bus_m0) + __popcll(bus_m1));
         ctrl->chunk_parallel = (allow_parallel && ld(&d.xf[d.xf_n]) == 0u && bus_steps <= CHUNK_BUS_STEPS) ? 1u : 0u;
         ctrl->chunk_bus = bus_steps;
-        ctrl->n_items = 0u; ctrl->n_newexp = 0u; ctrl->n_units = 0u; ctrl->unit_next = 0u; ctrl->n_route_pairs = 0u; ctrl->n_route_pairs_big = 0u;
+        ctrl->n_items = 0u; ctrl->n_newexp = 0u; ctrl->n_units = 0u; ctrl->unit_next = 0u; ctrl->n_route_pairs_big = 0u;
     }
     d.cursor[lane] = 0u;
     if (lane < FREE_MAX - 64u) d.cursor[64u + lane] = 0u;
@@ -252,7 +247,7 @@ __global__ __launch_bounds__(64) void k_decide(Dev d, uint32_t max_ahead, uint32
 // k_finish does, notes the chosen citizens (Dev::vax_ev) and leaves "Vaccinated at the end of step j" in their words
 // (earliest step wins, atomicMax on the vax field).  Everything downstream reads the field: an Infected citizen stops
 // marking after that step (k_chunk_marks), a Susceptible one takes no draw after it (member_pairs), the census moves
-// (k_chunk_vax_adj for the Infected counts the decisions need, k_chunk_count for the records).  The plan is speculative in
+// (xf_adj for the Infected counts the decisions need, k_chunk_count for the records).  The plan is speculative in
 // one respect only: a citizen it chose for step j may be exposed on a bus in a step s <= j of this very chunk, which removes
 // it from the set before its turn.  k_chunk_count finds the earliest such step s* (Ctrl::chunk_cut); the chunk is then
 // committed up to s* - 1 and the next chunk starts AT s*.  What happens in step s* itself does not depend on the plan from s*
@@ -346,7 +341,7 @@ __global__ __launch_bounds__(64) void k_lost_global(Dev d)
     }
 }
 
-// REPAIR (k_chunk_vax<true>, after the draws of the chunk, before its counts; unsharded contexts on the per-chunk map): a citizen the
+// REPAIR (k_chunk_vax<true>, after the draws of the chunk, before its counts; unsharded contexts): a citizen the
 // plan vaccinates at the end of step f was exposed on a bus in step e <= f.  It left the eligible set with that exposure, so in
 // every step from e on in which it was among the chosen the walk takes the next eligible candidate instead -- and nothing else
 // changes: the chosen stay in the set (Q10), so every step's walk is a function of the words alone.  Round 2 cut the chunk at e
@@ -382,7 +377,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_vax(Dev d, uint32_t max_ahead
     const uint32_t n_ahead = REPAIR ? n_chunk : (t0 > limit_t ? 0u : (limit_t - t0 + 1u < max_ahead ? limit_t - t0 + 1u : max_ahead));
     // (every workgroup -- and, sharded, every shard -- takes the same decision from the same words; nothing here writes them)
     const uint32_t elig_all = sharded ? d.xv[0] : ctrl->elig_count, riders_all = sharded ? d.xv[1] : d.n_pt;
-    const bool plan = ctrl->have_elig && !ctrl->finished && !ctrl->error && !ctrl->need_seq && !(sharded && d.xv[2]) &&
+    const bool plan = ctrl->have_elig && !ctrl->finished && !ctrl->error && !(sharded && d.xv[2]) &&
                       elig_all > d.vaccination_rate + riders_all;      // the set cannot shrink to the "whole set" case inside the chunk
     if (REPAIR) { if (tid == 0) { d.vax_cnt[j] = 0u; d.vax_now[j] = 0u; n_local = 0u; } }
     else if (tid == 0) {
@@ -393,7 +388,6 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_vax(Dev d, uint32_t max_ahead
             d.hot[HOT_LOST * HOT_STRIDE] = 0u; ctrl->replan_from = FREE_MAX + 1u; ctrl->repair_ran = 0u;
             ctrl->vax_chunk = plan ? 1u : 0u;
             ctrl->vax_planned = plan ? n_ahead : 0u;
-            ctrl->n_neg = 0u; ctrl->n_cancel = 0u;
             if (!sharded) ctrl->vax_fail = 0u;
             ctrl->chunk_cut = FREE_MAX + 1u;
             for (uint32_t z = FREE_MAX; z < FREE_MAX + 2u; ++z) for (uint32_t q = 0; q < 4u; ++q) d.vax_delta[q * (FREE_MAX + 2u) + z] = 0u;
@@ -459,7 +453,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_vax(Dev d, uint32_t max_ahead
                             // vaccinates before leave it: the stretch of the chunk in which this citizen would have been Infected behind
                             // step j goes into the difference array xf_adj (k_decide adds its prefix sums to F) -- for the step that WINS:
                             // a step that takes the citizen over from a later one takes that one's stretch out again (round 3: a
-                            // kernel of its own did this from the final words, k_chunk_vax_adj).
+                            // kernel of its own did this from the final words).
                             const int a = (int)CW_TE(cw[q]) - (int)TE_BIAS + (int)d.exposed_time + 1 - (int)t0, hi = min(a + (int)d.infected_time, (int)n_ahead - 1);
                             const int lo = max(a, (int)j + 1);
                             if (lo <= hi) { atomicSub(&d.xf_adj[lo], 1u); atomicAdd(&d.xf_adj[hi + 1], 1u); }
@@ -498,34 +492,6 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_vax(Dev d, uint32_t max_ahead
     }
     __syncthreads();
     if (tid == 0) { d.vax_cnt[j] = n_local; d.vax_now[j] = already; }
-}
-
-__device__ __forceinline__ void map_cancel(const Dev &d, Ctrl *ctrl, uint32_t c, uint32_t w, uint32_t t0, uint32_t j);
-// The Infected census ahead (buffer F) counts everybody whose exposure step makes it Infected; those the plan vaccinates
-// before leave it.  One thread per planned citizen: if its own step is the one that won, and the citizen is Infected in some
-// later step of the chunk, that stretch goes into the difference array xf_adj (k_decide adds its prefix sums to F).
-__global__ __launch_bounds__(TPB) void k_chunk_vax_adj(Dev d, uint32_t max_ahead, uint32_t limit_t, int pmap)
-{
-    const Ctrl *ctrl = d.ctrl;
-    if (!ctrl->vax_chunk || ctrl->vax_fail) return;
-    const uint32_t t0 = ctrl->t;
-    const uint32_t n_ahead = t0 > limit_t ? 0u : (limit_t - t0 + 1u < max_ahead ? limit_t - t0 + 1u : max_ahead);
-    const uint32_t j = blockIdx.x;
-    if (j >= n_ahead) return;
-    const uint32_t cnt = d.vax_cnt[j];
-    for (uint32_t i = threadIdx.x; i < cnt; i += TPB) {
-        const uint32_t cz = d.vax_ev[(size_t)j * VACC_MAX_RATE + i];
-        const uint32_t w = d.cit[cz], te = CW_TE(w);
-        if (CW_VAX_REL(w) != j || te >= TE_RECOVERED) continue;                // not the winning step / never exposed
-        const int a = (int)te - (int)TE_BIAS + (int)d.exposed_time + 1 - (int)t0;   // Infected in steps [a, a + infected_time] of the chunk
-        // persistent map: a citizen it holds already (k_map_enter handles those that turn Infected in this chunk) and whose stretch
-        // reaches beyond step j is cancelled from step j + 1 on -- to the end of its stretch, whatever the chunk's length
-        // (noted here, entered by k_map_enter once the chunk's length is known: a step beyond its end is not committed by it)
-        if (pmap && (w & CW_IN_MAP) && ctrl->map_t == t0 && a + (int)d.infected_time > (int)j) {
-            const uint32_t q = atomicAdd(&const_cast<Ctrl *>(ctrl)->n_cancel, 1u);
-            if (q < NEG_CAP) { d.cancel_list[2u * q] = cz; d.cancel_list[2u * q + 1u] = j; } else RAISE(const_cast<Ctrl *>(ctrl), ESIM_ERANGE, ERR_AT_NEG_LIST);
-        }
-    }
 }
 
 // ---------------------------------------------------------------------- sharded chunks: the commuter exchange
@@ -716,331 +682,6 @@ __device__ __forceinline__ void schedule_masks(uint32_t lane, uint32_t n, const 
 {
     AW = M96{ __ballot(lane < n && q0.at_work != 0u), (uint32_t)__ballot(64u + lane < n && q1.at_work != 0u) };
     BUS = M96{ __ballot(lane < n && q0.bus_dir != 0u), (uint32_t)__ballot(64u + lane < n && q1.bus_dir != 0u) };
-}
-
-// ------------------------------------------------------------------------------- persistent item map
-// k_chunk_marks rebuilds the map of items from the exposure log in every chunk, and k_chunk_scatter tears it down again -- although
-// an Infected citizen stands in the same buildings for its whole stretch of infected_time + 1 steps, three to four chunks.  In the
-// persistent form an item's records are ABSOLUTE: the citizen's exposure step (from which its Infected stretch
-// follows in any chunk) instead of a stretch relative to one chunk's first step.  A citizen is entered ONCE, by the chunk in which
-// it turns Infected (k_map_enter walks the log slice of those only; CW_IN_MAP in its word), and never taken out: a record whose
-// stretch has passed contributes nothing.  A vaccination planned for an Infected citizen (k_chunk_vax) adds a CANCELLATION
-// record -- same citizen, negative, from the step after the vaccination on -- instead of searching for the record: it stays for
-// good when the step is committed and is zeroed through Dev::neg_list when it is not.  Routes are items like the others: their
-// records are their Infected riders, and the draw pass finds the bus steps with an Infected rider from them.  Everything that
-// advances the clock without maintaining the map invalidates it (Ctrl::map_t); the next chunk then starts with k_map_clear and
-// enters everybody who is Infected in it -- which is also how dead items are shed every few chunks.
-//   record: bits 0-12 exposure step + TE_BIAS | 13-25 cancellation: absent AFTER this step (absolute; only with PIV_NEG) |
-//           26 rides public transport | 27 has a work place | 28 stands in its work building / room | 29 rider record of a route |
-//           30 cancellation | 31 valid
-#define PIV_VALID   0x80000000u
-#define PIV_NEG     (1u << 30)
-#define PIV_ROUTE   (1u << 29)
-#define PIV_AS_WORK (1u << 28)
-#define PIV_HW      (1u << 27)
-#define PIV_PT      (1u << 26)
-#define PIV_CUT_SHIFT 13u
-// slot_state of a persistent slot: records appended so far | listed as an item | every record in `ovf` (a school building: its
-// rooms read its per-step counters only)
-#define PSLOT_COUNT   0x00FFFFFFu
-#define PSLOT_LISTED  0x40000000u
-#define PSLOT_ALL_OVF 0x20000000u
-struct ChunkT { int te0; int it; int t0; uint32_t n; };      // te0: the exposure step (+ TE_BIAS) that turns Infected in step 0 of the chunk
-__device__ __forceinline__ ChunkT chunk_t(const Dev &d, uint32_t t0, uint32_t n)
-{
-    return ChunkT{ (int)(t0 + TE_BIAS) - (int)d.exposed_time - 1, (int)d.infected_time, (int)t0, n };
-}
-// The steps of the chunk in which the citizen of a persistent record stands where the record was left.
-__device__ __forceinline__ M96 piv_steps(uint32_t iv, const ChunkT &ct, const M96 &AW, const M96 &BUS)
-{
-    if (!(iv & PIV_VALID)) return M96{ 0ull, 0u };
-    int a = (int)(iv & 0x1FFFu) - ct.te0;
-    const int b = min(a + ct.it, (int)ct.n - 1);
-    if (iv & PIV_NEG) a = max(a, (int)((iv >> PIV_CUT_SHIFT) & 0x1FFFu) - ct.t0 + 1);
-    a = max(a, 0);
-    if (a > b) return M96{ 0ull, 0u };
-    const M96 I = m96_range((uint32_t)a, (uint32_t)b);
-    if (iv & PIV_ROUTE) return m96_and(I, BUS);
-    const M96 rest = (iv & PIV_PT) ? m96_andn(I, BUS) : I;
-    const M96 atw = (iv & PIV_HW) ? m96_and(rest, AW) : M96{ 0ull, 0u };
-    return (iv & PIV_AS_WORK) ? atw : m96_andn(rest, atw);
-}
-__device__ __forceinline__ void piv_count(uint32_t iv, uint32_t lane, const ChunkT &ct, const M96 &AW, const M96 &BUS, uint32_t &c0, uint32_t &c1)
-{
-    const M96 at = piv_steps(iv, ct, AW, BUS);
-    const uint32_t b0 = (uint32_t)(at.lo >> lane) & 1u, b1 = lane < 32u ? (at.hi >> lane) & 1u : 0u;
-    if (iv & PIV_NEG) { c0 -= b0; c1 -= b1; } else { c0 += b0; c1 += b1; }     // (a cancellation never outruns what it cancels: sums stay >= 0)
-}
-
-
-// The map is emptied (a rebuild follows): the slots of every listed item, the spilled per-step counters, the in-map bits of
-// everybody the log holds from the earliest exposure step that can still be Infected.  Ctrl::map_t = 0xFFFFFFFF says "empty".
-__global__ __launch_bounds__(TPB) void k_map_clear(Dev d)
-{
-    Ctrl *ctrl = d.ctrl;
-    const uint32_t tid = blockIdx.x * TPB + threadIdx.x, nth = gridDim.x * TPB;
-    const uint32_t per = d.items_cap / SUBQ;
-    for (uint32_t s = 0; s < SUBQ; ++s) {
-        const uint32_t cnt = min(d.used_cnt[s], per);
-        for (uint32_t k = tid; k < cnt; k += nth) {
-            const uint32_t v = s * per + k, h = d.hitems[v];
-            if (h >= d.hcap) continue;
-            // (the per-step counters need no zeroing: on the persistent map k_map_fold STORES them before anybody reads them)
-            d.hkey[h] = HKEY_EMPTY; d.slot_state[h] = 0u; d.hitems[v] = ITEM_UNUSED;
-        }
-    }
-    const int lo_te = (int)(ctrl->t + TE_BIAS) - (int)d.exposed_time - 1 - (int)d.infected_time;
-    const uint32_t i0 = d.log_off[lo_te < 0 ? 0 : lo_te], i1 = ctrl->log_len;
-    for (uint32_t i = i0 + tid; i < i1; i += nth) { const uint32_t c = d.log[i], w = d.cit[c]; if (w & CW_IN_MAP) d.cit[c] = w & ~CW_IN_MAP; }   // (nothing else runs)
-}
-__global__ __launch_bounds__(64) void k_map_reset(Dev d)
-{
-    const uint32_t lane = threadIdx.x;
-    d.used_cnt[lane] = 0u; d.pbig_cnt[lane] = 0u;
-    if (lane == 0) { d.ctrl->map_t = 0xFFFFFFFFu; d.ctrl->n_neg = 0u; }
-}
-
-// One record of a citizen into one slot of the persistent map; returns nothing the caller has to wait for.  kind 0 home building,
-// 1 work building, 2 room, 3 route; all_ovf: a school building (every record in `ovf`).  A first record in `ovf` lists the slot
-// for k_map_fold; a cancellation record notes its address in Dev::neg_list.
-__device__ __forceinline__ void map_list(const Dev &d, Ctrl *ctrl, uint32_t slot, uint32_t base2, uint32_t cap2, uint32_t sch, uint32_t wave)
-{
-    const uint32_t r = wave & (SUBQ - 1u), at = atomicAdd(&d.pbig_cnt[r], 1u), cap = d.big_qcap * 3u / PBIG_STRIDE;
-    if (at < cap) { uint32_t *bl = d.big_list + ((size_t)r * cap + at) * PBIG_STRIDE; bl[0] = slot; bl[1] = base2; bl[2] = cap2 | (sch != 0xFFFFFFFFu ? 0x80000000u : 0u); bl[3] = sch; }
-    else RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIG_LIST);
-}
-__device__ __forceinline__ void map_append(const Dev &d, Ctrl *ctrl, uint32_t slot, uint32_t pos, uint32_t rec, uint32_t base2, uint32_t cap2, bool all_ovf,
-                                            uint32_t wave, uint32_t neg_step)
-{
-    uint32_t where;
-    if (!all_ovf && pos < ITEM_RECS) { where = slot * SLOT_IV_STRIDE + pos; d.slot_iv[where] = rec; }
-    else {
-        const uint32_t q = all_ovf ? pos : pos - ITEM_RECS;
-        if (q >= cap2) { RAISE(ctrl, ESIM_ERANGE, ERR_AT_OVF_FULL); return; }     // (a member leaves one record and at most one cancellation per item)
-        d.ovf[base2 + q] = rec;
-        where = 0x80000000u | (base2 + q);
-        if (q == 0u && !all_ovf) map_list(d, ctrl, slot, base2, cap2, 0xFFFFFFFFu, wave);     // (a school is listed by its first member, see k_map_enter)
-    }
-    if (rec & PIV_NEG) {
-        const uint32_t i = atomicAdd(&ctrl->n_neg, 1u);
-        if (i < NEG_CAP) { d.neg_list[2u * i] = where; d.neg_list[2u * i + 1u] = neg_step; } else RAISE(ctrl, ESIM_ERANGE, ERR_AT_NEG_LIST);
-    }
-}
-
-// Find (or, with `insert`, make) the slot of a key in the open-addressing map.  Returns ITEM_UNUSED when it is not there.
-__device__ __forceinline__ uint32_t map_slot(const Dev &d, Ctrl *ctrl, unsigned long long key, bool insert)
-{
-    uint32_t h = hash64(key) & (d.hcap - 1u);
-    for (uint32_t probe = 0; probe < d.hcap; ++probe) {
-        unsigned long long seen = d.hkey[h];
-        if (seen == HKEY_EMPTY) { if (!insert) return ITEM_UNUSED; seen = atomicCAS(&d.hkey[h], HKEY_EMPTY, key); if (seen == HKEY_EMPTY) return h; }
-        if (seen == key) return h;
-        h = (h + 1u) & (d.hcap - 1u);
-    }
-    RAISE(ctrl, ESIM_ERANGE, ERR_AT_HASH_FULL);
-    return ITEM_UNUSED;
-}
-
-// Where the records of key `kind` of citizen c go beyond the slot's own: (base, capacity) of its stretch of `ovf`, two places per
-// member (a record and a cancellation).
-__device__ __forceinline__ void map_ovf_range(const Dev &d, uint32_t kind, uint32_t id, uint32_t &base2, uint32_t &cap2)
-{
-    uint32_t base, cap;
-    if (kind < 2u) { base = d.ovf_off[id]; cap = d.ovf_off[id + 1u] - base; }
-    else if (kind == 2u) { const uint32_t o = d.room_off[id]; base = d.ovf_room_base + o; cap = d.room_off[id + 1u] - o; }
-    else { const uint32_t o = d.route_off[id]; base = d.ovf_route_base + o; cap = d.route_off[id + 1u] - o; }
-    base2 = 2u * base; cap2 = 2u * cap;
-}
-
-// generate_exposures for the persistent map: one LANE per citizen that TURNS Infected in the chunk (a rebuild: per citizen that is
-// Infected in it at all).  The citizen leaves one record with each item it can ever stand in while Infected -- its home, its
-// work building and room, its route -- whatever this chunk's schedule is: the records outlive the chunk.
-__global__ __launch_bounds__(TPB) void k_map_enter(Dev d)
-{
-    Ctrl *ctrl = d.ctrl;
-    const uint32_t t0 = ctrl->chunk_t0, n = ctrl->chunk_ok;
-    if (!ctrl->chunk_parallel || n == 0u) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (blockIdx.x * TPB + threadIdx.x) >> 6, n_waves = (gridDim.x * TPB) >> 6;
-    const uint32_t map_t = ctrl->map_t;
-    const bool rebuild = map_t != t0;
-    if (rebuild && map_t != 0xFFFFFFFFu) { if (wave == 0 && lane == 0) RAISE(ctrl, ESIM_ESTATE, ERR_AT_MAP_STATE); return; }   // (the host clears before a rebuild)
-    {
-        const uint32_t q = (t0 + MARK_SLOTS - 1u) & (MARK_SLOTS - 1u);        // marks a sequential step left (see k_chunk_marks)
-        const uint32_t tid = blockIdx.x * TPB + threadIdx.x, nth = gridDim.x * TPB;
-        const uint32_t ob = ctrl->n_touched_bld[q], orr = ctrl->n_touched_room[q], ort = ctrl->n_touched_route[q], orb = ctrl->n_touched_route_big[q];
-        for (uint32_t i = tid; i < ob; i += nth) d.cnt_bld[q][d.touched_bld[q][i]] = 0u;
-        for (uint32_t i = tid; i < orr; i += nth) d.cnt_room[q][d.touched_room[q][i]] = 0u;
-        for (uint32_t i = tid; i < ort; i += nth) d.route_flag[q][d.touched_route[q][i]] = 0u;
-        for (uint32_t i = tid; i < orb; i += nth) d.route_flag[q][d.touched_route_big[q][i]] = 0u;
-    }
-    const uint32_t per = d.items_cap / SUBQ;
-    // Work building, room and route are entered only into a map that is built for a schedule with working hours: under a lockdown
-    // (everybody at home for the whole chunk, Q8) a rebuild enters the homes alone -- half the items --, and a chunk whose schedule
-    // needs the others cannot run on such a map: it is a no-op, the host sees no progress and rebuilds.
-    const Decision q0 = lane < n ? d.dec[lane] : Decision{ 0u, 0u, 0u, 0u };
-    const Decision q1 = 64u + lane < n ? d.dec[64u + lane] : Decision{ 0u, 0u, 0u, 0u };
-    const bool needs_work = __ballot(lane < n && (q0.at_work | q0.bus_dir) != 0u) != 0ull || __ballot(64u + lane < n && (q1.at_work | q1.bus_dir) != 0u) != 0ull;
-    const bool map_work = rebuild ? needs_work : ctrl->map_work != 0u;
-    if (needs_work && !map_work) { if (wave == 0 && lane == 0) ctrl->chunk_parallel = 0u; return; }
-    if (wave == 0 && lane == 0) { ctrl->items_per_wave = per; ctrl->n_items = per * SUBQ; ctrl->pmap_chunk = 1u; ctrl->map_work = map_work ? 1u : 0u; }
-    const uint32_t i0 = rebuild ? ctrl->chunk_i0 : ctrl->chunk_e0, i1 = ctrl->chunk_i1;
-    const ChunkT ct = chunk_t(d, t0, n);
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const uint32_t sub = wave & (SUBQ - 1u);
-    // the plan's vaccinations of citizens the map holds already (k_chunk_vax_adj noted them), those inside the chunk
-    if (!rebuild) {
-        const uint32_t nc = min(ctrl->n_cancel, NEG_CAP);
-        for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < nc; i += gridDim.x * TPB) {
-            const uint32_t cz = d.cancel_list[2u * i], j = d.cancel_list[2u * i + 1u];
-            if (j < n && cz < d.n) map_cancel(d, ctrl, cz, d.cit[cz], t0, j);
-        }
-    }
-    WORK_TALLY;
-    const uint32_t E = i1 - i0;
-    for (uint32_t round = 0; wave + n_waves * (round * 64u) < E; ++round) {
-        const uint32_t idx = wave + n_waves * (round * 64u + lane);
-        bool act = idx < E;
-        uint32_t c = 0u, w = 0u;
-        if (act) { c = d.log[i0 + idx]; w = d.cit[c]; }
-        const uint32_t te = CW_TE(w);
-        const int a = (int)te - ct.te0;                                        // first Infected step, relative to the chunk
-        // a vaccination the plan places inside this chunk (one beyond its end is not committed by it: the next plan decides again)
-        const uint32_t vrel = CW_VAX_REL(w) < n ? CW_VAX_REL(w) : CW_VAX_NONE;
-        // not (any more) Infected in this chunk; entered already; or Vaccinated (by the chunk's plan) before it would turn Infected
-        if (te >= TE_RECOVERED || (w & CW_IN_MAP) || a > (int)n - 1 || a + ct.it < 0 || (vrel != CW_VAX_NONE && (int)vrel < a)) act = false;
-        if (act) WORK_ADD(WK_ENTRIES, 1);
-        const bool school = w & FL_WORK_SCHOOL, has_work = (w & FL_HAS_WORK) && map_work;
-        uint32_t id[4] = { 0u, 0u, 0u, 0u };
-        bool use[4] = { act, act && has_work, act && has_work && school, false };
-        if (act) id[0] = d.home[c];
-        if (use[1]) id[1] = d.work[c];
-        if (use[2]) { id[2] = d.room[c]; if (id[2] == 0xFFFFFFFFu) use[2] = false; }
-        if (act && map_work && (w & FL_USES_PT)) { id[3] = d.route_of[c]; use[3] = id[3] != NO_ROUTE; }
-        // find or make the slots: the first probes of all four keys go out together (a look before the compare-and-swap)
-        unsigned long long key[4], seen[4];
-        uint32_t slot[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            key[k] = (unsigned long long)id[k] + (k == 2u ? d.n_bld : k == 3u ? d.n_bld + d.n_room : 0u);
-            slot[k] = hash64(key[k]) & (d.hcap - 1u);
-            seen[k] = key[k];
-            if (use[k]) { WORK_ADD(WK_KEYS, 1); seen[k] = d.hkey[slot[k]]; }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) if (use[k] && seen[k] == HKEY_EMPTY) { seen[k] = atomicCAS(&d.hkey[slot[k]], HKEY_EMPTY, key[k]); if (seen[k] == HKEY_EMPTY) seen[k] = key[k]; }
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k)
-            if (use[k] && seen[k] != key[k]) {                                  // somebody else's key in the slot: linear probing from the next one
-                uint32_t h = slot[k];
-                bool found = false;
-                for (uint32_t probe = 1; probe < d.hcap && !found; ++probe) {
-                    h = (h + 1u) & (d.hcap - 1u);
-                    unsigned long long o = d.hkey[h];
-                    if (o == HKEY_EMPTY) { o = atomicCAS(&d.hkey[h], HKEY_EMPTY, key[k]); if (o == HKEY_EMPTY) o = key[k]; }
-                    found = o == key[k];
-                }
-                if (!found) { RAISE(ctrl, ESIM_ERANGE, ERR_AT_HASH_FULL); use[k] = false; }
-                slot[k] = h;
-            }
-        // the record(s): the citizen's exposure step and what decides where it stands; a plan that vaccinates it at the end of step
-        // vrel cancels it from the step after
-        const uint32_t fl = PIV_VALID | te | ((w & FL_USES_PT) ? PIV_PT : 0u) | ((w & FL_HAS_WORK) ? PIV_HW : 0u);
-        const bool neg = act && vrel != CW_VAX_NONE && (int)vrel < a + ct.it;   // (to the end of its stretch, whatever the chunk's length)
-        const uint32_t cut = neg ? ((t0 + vrel) << PIV_CUT_SHIFT) | PIV_NEG : 0u;
-        // a school building keeps no record per member: the member joins the school's histograms of exposure steps (k_map_fold
-        // sums windows of them); only a cancellation is a record there
-        const bool ring = use[1] && school;
-        int32_t sch = -1;
-        if (ring) {
-            sch = d.sch_of_bld[id[1]];
-            if (sch < 0) { RAISE(ctrl, ESIM_ESTATE, ERR_AT_ITEM_CHECK); use[1] = false; }
-            else {
-                atomicAdd(&d.sch_ring[((size_t)sch * 2u) * SCH_RING + (te & (SCH_RING - 1u))], 1u);
-                if (w & FL_USES_PT) atomicAdd(&d.sch_ring[((size_t)sch * 2u + 1u) * SCH_RING + (te & (SCH_RING - 1u))], 1u);
-            }
-        }
-        uint32_t old[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k)
-            if (use[k]) {
-                // (a school's members -- hundreds in a chunk -- all meet in ONE slot: they look at it with a plain load, and only a
-                // cancellation, which needs a place, or whoever sees it unlisted pays for a returning atomic)
-                if (k == 1u && ring) old[k] = neg ? atomicAdd(&d.slot_state[slot[k]], 1u) : d.slot_state[slot[k]];
-                else old[k] = atomicAdd(&d.slot_state[slot[k]], neg ? 2u : 1u);
-            }
-        // whoever finds a slot that is not listed as an item lists it: the next ids of this wavefront's sub-list
-        bool lists[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            lists[k] = false;
-            if (use[k] && !(old[k] & PSLOT_LISTED)) lists[k] = !(atomicOr(&d.slot_state[slot[k]], PSLOT_LISTED) & PSLOT_LISTED);
-        }
-        uint32_t before = 0u, n_claims = 0u;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) { const unsigned long long cm = __ballot(lists[k]); before += (uint32_t)__popcll(cm & lt); n_claims += (uint32_t)__popcll(cm); }
-        uint32_t first_id = 0u;
-        if (n_claims) {
-            if (lane == 0) first_id = atomicAdd(&d.used_cnt[sub], n_claims);
-            first_id = FX(first_id, 0);
-            if (first_id + n_claims > per) { if (lane == 0) RAISE(ctrl, ESIM_ERANGE, ERR_AT_ITEM_IDS); n_claims = 0u; }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            if (lists[k] && n_claims) {
-                WORK_ADD(WK_CLAIMS, 1);
-                const uint32_t v = sub * per + first_id + before++;
-                d.hitems[v] = slot[k];
-                ItemRec rec = { (uint32_t)key[k], 0u, 0u, 0u, 0u, 0u, k == 2u ? slot[1] : 0xFFFFFFFFu, 0u };
-                if (k < 2u) {
-                    rec.a_lo = d.res_off[id[k]]; rec.a_hi = d.res_off[id[k] + 1u];
-                    rec.b_lo = d.wrk_off[id[k]]; rec.b_hi = d.wrk_off[id[k] + 1u];
-                    rec.aux = (uint32_t)d.bld_type[id[k]];
-                } else if (k == 2u) { rec.a_lo = d.room_off[id[2]]; rec.a_hi = d.room_off[id[2] + 1u]; rec.aux = d.room_bld[id[2]]; }
-                else { rec.a_lo = d.route_off[id[3]]; rec.a_hi = d.route_off[id[3] + 1u]; }
-                d.item_rec[v] = rec;
-            }
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            if (!use[k]) continue;
-            uint32_t base2, cap2;
-            map_ovf_range(d, k, id[k], base2, cap2);
-            const uint32_t rec = fl | (k == 3u ? PIV_ROUTE : (k == 0u ? 0u : PIV_AS_WORK));
-            const uint32_t pos = old[k] & PSLOT_COUNT;
-            if (k == 1u && ring) {
-                if (lists[k]) map_list(d, ctrl, slot[k], base2, cap2, (uint32_t)sch, wave);      // (who lists the item lists the school for the fold)
-                if (neg) map_append(d, ctrl, slot[k], pos, rec | cut, base2, cap2, true, wave, vrel);
-                continue;
-            }
-            WORK_ADD(WK_RECORDS, 1);
-            map_append(d, ctrl, slot[k], pos, rec, base2, cap2, false, wave, 0u);
-            if (neg) map_append(d, ctrl, slot[k], pos + 1u, rec | cut, base2, cap2, false, wave, vrel);
-        }
-        if (act) d.cit[c] = w | CW_IN_MAP;                                    // (nobody else writes the word of a citizen that turns Infected here)
-    }
-    WORK_FLUSH(d);
-}
-
-// A vaccination planned for the end of step j of the chunk, of a citizen whose records the map holds already: a cancellation record
-// from step j + 1 on with each of its items (k_chunk_vax_adj calls this for the citizens whose own step won).
-__device__ __forceinline__ void map_cancel(const Dev &d, Ctrl *ctrl, uint32_t c, uint32_t w, uint32_t t0, uint32_t j)
-{
-    const uint32_t te = CW_TE(w);
-    const bool mw = ctrl->map_work != 0u;                                     // (a map built under a lockdown holds the homes alone)
-    const bool school = w & FL_WORK_SCHOOL, has_work = (w & FL_HAS_WORK) && mw;
-    const uint32_t fl = PIV_VALID | PIV_NEG | ((t0 + j) << PIV_CUT_SHIFT) | te | ((w & FL_USES_PT) ? PIV_PT : 0u) | ((w & FL_HAS_WORK) ? PIV_HW : 0u);
-    uint32_t id[4] = { d.home[c], has_work ? d.work[c] : 0u, (has_work && school) ? d.room[c] : 0xFFFFFFFFu, (mw && (w & FL_USES_PT)) ? d.route_of[c] : NO_ROUTE };
-    const bool use[4] = { true, has_work, has_work && school && id[2] != 0xFFFFFFFFu, id[3] != NO_ROUTE };
-    for (uint32_t k = 0; k < 4u; ++k) {
-        if (!use[k]) continue;
-        const uint32_t slot = map_slot(d, ctrl, (unsigned long long)id[k] + (k == 2u ? d.n_bld : k == 3u ? d.n_bld + d.n_room : 0u), false);
-        if (slot == ITEM_UNUSED) { RAISE(ctrl, ESIM_ESTATE, ERR_AT_CANCEL_SLOT); continue; }     // (its record is there: CW_IN_MAP)
-        uint32_t base2, cap2;
-        map_ovf_range(d, k, id[k], base2, cap2);
-        const uint32_t pos = atomicAdd(&d.slot_state[slot], 1u) & PSLOT_COUNT;
-        map_append(d, ctrl, slot, pos, fl | (k == 3u ? PIV_ROUTE : (k == 0u ? 0u : PIV_AS_WORK)), base2, cap2, k == 1u && school, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, j);
-    }
 }
 
 // generate_exposures (simulator.rs:181-198) for every step of the chunk: one LANE per citizen that is Infected somewhere in
@@ -1356,9 +997,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
 // The interval records k_chunk_marks put into `ovf` (slots with more than ITEM_RECS of them: schools, large work places),
 // summed into the slots' per-step counters before the draw pass reads them.  One wavefront per listed slot, 64 records at a
 // time; each lane turns its record into the set of steps in which that citizen stands there, one ballot per step counts them.
-// PM: the persistent map -- the listed slots are those of Dev::pbig_cnt (they stay listed), their records are absolute, the
-// sums are STORED (nobody else adds to them), and the prefix sums are those of the SUBQ sub-lists the item ids are handed out from.
-template <bool PM>
 __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
 {
     Ctrl *ctrl = d.ctrl;
@@ -1367,19 +1005,18 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * TPB + threadIdx.x) >> 6, n_waves = (gridDim.x * TPB) >> 6;
     const uint32_t per_wave = ld(&ctrl->items_per_wave);
-    const uint32_t n_own = PM ? SUBQ : n_waves;                              // owners of item id ranges
-    if ((unsigned long long)per_wave * n_own > d.items_cap) return;
+    if ((unsigned long long)per_wave * n_waves > d.items_cap) return;
     if (blockIdx.x == 0) {
         // for k_chunk_draw: used_pref[k] = ids handed out by the wavefronts before k
         __shared__ uint32_t s_pref[CHUNK_WAVES_MAX + 1u];
         __shared__ uint32_t s_wtot[TPB / 64];
         const uint32_t pf0 = PROF_NOW();
         constexpr uint32_t RUN = CHUNK_WAVES_MAX / TPB;
-        const uint32_t run = (n_own + TPB - 1u) / TPB, b = threadIdx.x * run;   // <= RUN
+        const uint32_t run = (n_waves + TPB - 1u) / TPB, b = threadIdx.x * run;   // <= RUN
         uint32_t cnt[RUN];
         uint32_t sum = 0u;
 #pragma unroll
-        for (uint32_t k = 0; k < RUN; ++k) { cnt[k] = (k < run && b + k < n_own) ? min(d.used_cnt[b + k], per_wave) : 0u; sum += cnt[k]; }
+        for (uint32_t k = 0; k < RUN; ++k) { cnt[k] = (k < run && b + k < n_waves) ? min(d.used_cnt[b + k], per_wave) : 0u; sum += cnt[k]; }
         uint32_t x = sum;
         for (uint32_t o = 1; o < 64u; o <<= 1) { const uint32_t y = __shfl_up(x, o, 64); if (lane >= o) x += y; }
         if (lane == 63u) s_wtot[threadIdx.x >> 6] = x;
@@ -1389,18 +1026,16 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
         uint32_t acc = x - sum;
         for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k) acc += s_wtot[k];
 #pragma unroll
-        for (uint32_t k = 0; k < RUN; ++k) if (k < run && b + k < n_own) { acc += cnt[k]; s_pref[b + k + 1u] = acc; }
+        for (uint32_t k = 0; k < RUN; ++k) if (k < run && b + k < n_waves) { acc += cnt[k]; s_pref[b + k + 1u] = acc; }
         __syncthreads();
         const uint32_t pf2 = PROF_NOW();
-        for (uint32_t w = threadIdx.x; w <= n_own; w += TPB) d.used_pref[w] = s_pref[w];
+        for (uint32_t w = threadIdx.x; w <= n_waves; w += TPB) d.used_pref[w] = s_pref[w];
         BOOKS_PROF(d, 8, pf1 - pf0); BOOKS_PROF(d, 9, pf2 - pf1); BOOKS_PROF(d, 10, PROF_NOW() - pf2);
         (void)pf0; (void)pf1; (void)pf2;
     }
     // list `wave & 63`, every (n_waves / 64)-th entry of it
     const uint32_t qr = wave & (SUBQ - 1u), first = wave >> 6, step = n_waves >> 6;
-    const uint32_t l_stride = PM ? PBIG_STRIDE : 3u, l_cap = PM ? d.big_qcap * 3u / PBIG_STRIDE : d.big_qcap;
-    const uint32_t n_list = step ? min(PM ? d.pbig_cnt[qr] : ld(&d.hot[(HOT_BIG + qr) * HOT_STRIDE]), l_cap) : 0u;
-    const ChunkT ct = chunk_t(d, ctrl->chunk_t0, n);
+    const uint32_t n_list = step ? min(ld(&d.hot[(HOT_BIG + qr) * HOT_STRIDE]), d.big_qcap) : 0u;
 #ifdef ESIM_PROFILE_FOLD
     const uint32_t pq0 = PROF_NOW();
     uint32_t pq_rec = 0u, pq_n = 0u;
@@ -1408,8 +1043,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
 #endif
     if (first >= n_list) return;
     WORK_TALLY;
-    const uint32_t *bl = d.big_list + (size_t)qr * l_cap * l_stride;
-    __shared__ uint32_t s_win[TPB / 64][2][TE_BIAS + FREE_MAX + 64u];        // (persistent map: a school's window sums, per wavefront)
+    const uint32_t *bl = d.big_list + (size_t)qr * d.big_qcap * 3u;
     const Decision q0 = lane < n ? d.dec[lane] : Decision{ 0u, 0u, 0u, 0u };
     const Decision q1 = 64u + lane < n ? d.dec[64u + lane] : Decision{ 0u, 0u, 0u, 0u };
     const M96 AW = { __ballot(lane < n && q0.at_work != 0u), (uint32_t)__ballot(64u + lane < n && q1.at_work != 0u) };
@@ -1420,18 +1054,16 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
         uint32_t slot_l = 0u, base_l = 0u, n_ov_l = 0u, sch_l = 0xFFFFFFFFu;
         const uint32_t mine = g + lane * step;
         if (mine < n_list) {
-            slot_l = bl[l_stride * mine]; base_l = bl[l_stride * mine + 1u];
-            const uint32_t cap_l = bl[l_stride * mine + 2u] & 0x7FFFFFFFu, all_ovf = bl[l_stride * mine + 2u] >> 31;   // (bit 31: a school building of the persistent map)
-            if (PM && all_ovf) { sch_l = bl[l_stride * mine + 3u]; if (sch_l >= d.n_sch) { sch_l = 0xFFFFFFFFu; RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIG_LIST); } }
-            if (!PM && all_ovf) {
+            slot_l = bl[3u * mine]; base_l = bl[3u * mine + 1u];
+            const uint32_t cap_l = bl[3u * mine + 2u] & 0x7FFFFFFFu, all_ovf = bl[3u * mine + 2u] >> 31;
+            if (all_ovf) {
                 // a school building (k_chunk_marks: capacity word 0xFFFFFFFF, the school's number where the records would start)
                 sch_l = base_l; base_l = 0u;
                 if (sch_l >= d.n_sch || slot_l >= d.hcap) { sch_l = 0xFFFFFFFFu; slot_l = 0u; RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIG_LIST); }
             } else
             if (slot_l < d.hcap && base_l <= d.ovf_n && cap_l <= d.ovf_n - base_l) {
                 const uint32_t state = d.slot_state[slot_l];
-                if (PM) { const uint32_t cnt = state & PSLOT_COUNT, inl = all_ovf ? 0u : ITEM_RECS; n_ov_l = min(cnt > inl ? cnt - inl : 0u, cap_l); }
-                else n_ov_l = min((state > ITEM_RECS && state < SLOT_COUNTERS_ONLY) ? state - ITEM_RECS : 0u, cap_l);
+                n_ov_l = min((state > ITEM_RECS && state < SLOT_COUNTERS_ONLY) ? state - ITEM_RECS : 0u, cap_l);
             } else { slot_l = 0u; base_l = 0u; ctrl->error = (uint32_t)(-ESIM_ERANGE); }   // (no list entry k_chunk_marks wrote looks like this)
         }
         const uint32_t m = min(64u, (n_list - g + step - 1u) / step);
@@ -1448,44 +1080,8 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
             uint32_t iv = ivs[u];
             uint32_t c0 = 0u, c1 = 0u;
             WORK_ADD(WK_FOLDED, lane == 0 ? n_ov : 0);
-            if (PM && FX(sch_l, i) != 0xFFFFFFFFu) {
-                // A school building: its members that are Infected in step j of the chunk are those with exposure steps te0 + j -
-                // infected_time .. te0 + j -- a window sum over its histogram of exposure steps (prefix sums through LDS) --; they
-                // stand there while those with a work place are at work, the riders among them not while riders are on a bus.
-                const uint32_t sch = FX(sch_l, i), wv = threadIdx.x >> 6;
-                const uint32_t *ring = d.sch_ring + (size_t)sch * 2u * SCH_RING;
-                const int base_te = ct.te0 - ct.it;                               // exposure step of the window's low end in step 0
-                const uint32_t len = (uint32_t)ct.it + n;                         // entries base_te .. base_te + len - 1 are needed
-                uint32_t carry0 = 0u, carry1 = 0u;
-                for (uint32_t r0 = 0; r0 < len; r0 += 64u) {
-                    const int te = base_te + (int)(r0 + lane);
-                    uint32_t x0 = (r0 + lane < len && te >= 0) ? ring[(uint32_t)te & (SCH_RING - 1u)] : 0u;
-                    uint32_t x1 = (r0 + lane < len && te >= 0) ? ring[SCH_RING + ((uint32_t)te & (SCH_RING - 1u))] : 0u;
-                    for (uint32_t o = 1; o < 64u; o <<= 1) { const uint32_t y0 = __shfl_up(x0, o, 64), y1 = __shfl_up(x1, o, 64); if (lane >= o) { x0 += y0; x1 += y1; } }
-                    s_win[wv][0][r0 + lane + 1u] = x0 + carry0; s_win[wv][1][r0 + lane + 1u] = x1 + carry1;     // [k + 1] = sum of entries 0 .. k
-                    carry0 += __shfl(x0, 63, 64); carry1 += __shfl(x1, 63, 64);
-                }
-                if (lane == 0) { s_win[wv][0][0] = 0u; s_win[wv][1][0] = 0u; }
-                __builtin_amdgcn_wave_barrier();
-                // step j: entries j .. j + infected_time of the window
-                if (lane < n) {
-                    const uint32_t all = s_win[wv][0][lane + (uint32_t)ct.it + 1u] - s_win[wv][0][lane], pt = s_win[wv][1][lane + (uint32_t)ct.it + 1u] - s_win[wv][1][lane];
-                    c0 = ((AW.lo >> lane) & 1ull) ? all - (((BUS.lo >> lane) & 1ull) ? pt : 0u) : 0u;
-                }
-                if (64u + lane < n) {
-                    const uint32_t j = 64u + lane;
-                    const uint32_t all = s_win[wv][0][j + (uint32_t)ct.it + 1u] - s_win[wv][0][j], pt = s_win[wv][1][j + (uint32_t)ct.it + 1u] - s_win[wv][1][j];
-                    c1 = ((AW.hi >> lane) & 1u) ? all - (((BUS.hi >> lane) & 1u) ? pt : 0u) : 0u;
-                }
-                __builtin_amdgcn_wave_barrier();
-                // the ring's cells below the window are free again for exposure steps SCH_RING later
-                for (uint32_t z = lane; z < 2u * FREE_MAX; z += 64u) {
-                    const int te = base_te - 1 - (int)z;
-                    if (te >= 0) { d.sch_ring[(size_t)sch * 2u * SCH_RING + ((uint32_t)te & (SCH_RING - 1u))] = 0u; d.sch_ring[((size_t)sch * 2u + 1u) * SCH_RING + ((uint32_t)te & (SCH_RING - 1u))] = 0u; }
-                }
-            }
-            if (!PM && FX(sch_l, i) != 0xFFFFFFFFu) {
-                // A school building of the per-chunk map: the prefix sums of its difference arrays are its Infected per step -- all of
+            if (FX(sch_l, i) != 0xFFFFFFFFu) {
+                // A school building: the prefix sums of its difference arrays are its Infected per step -- all of
                 // them, and the riders among them --; they stand there while those with a work place are at work, the riders not
                 // while riders are on a bus (what k_chunk_marks' `atw` says per citizen).  The arrays are zeroed for the next chunk.
                 uint32_t *dd = d.sch_diff + (size_t)FX(sch_l, i) * SD_REPL * 2u * FREE_MAX;
@@ -1519,36 +1115,24 @@ __global__ __launch_bounds__(TPB) void k_chunk_fold(Dev d)
                 if (nb <= 12u) {
                     // few records (a class room): one after the other, its set of steps in scalar registers, lanes = steps
                     for (uint32_t k = 0; k < nb; ++k) {
-                        if (PM) { piv_count(FX(iv, k), lane, ct, AW, BUS, c0, c1); continue; }
                         const M96 at = iv_steps(FX(iv, k), AW, BUS);
                         c0 += (uint32_t)(at.lo >> lane) & 1u;
                         c1 += lane < 32u ? (at.hi >> lane) & 1u : 0u;
                     }
                     continue;
                 }
-                // many: lanes = records, one ballot per step (persistent map: cancellation records count negative)
-                const M96 at = PM ? piv_steps(iv, ct, AW, BUS) : iv_steps(iv, AW, BUS);
-                const bool negr = PM && (iv & PIV_NEG);
-                const bool any_neg = PM && __any(negr);
+                // many: lanes = records, one ballot per step
+                const M96 at = iv_steps(iv, AW, BUS);
                 for (uint32_t j = 0; j < n && j < 64u; ++j) {
-                    const bool here = (at.lo >> j) & 1ull;
-                    uint32_t k = (uint32_t)__popcll(__ballot(here && !negr));
-                    if (any_neg) k -= (uint32_t)__popcll(__ballot(here && negr));
+                    const uint32_t k = (uint32_t)__popcll(__ballot((at.lo >> j) & 1ull));
                     if (lane == j) c0 += k;
                 }
                 for (uint32_t j = 64u; j < n; ++j) {
-                    const bool here = (at.hi >> (j - 64u)) & 1u;
-                    uint32_t k = (uint32_t)__popcll(__ballot(here && !negr));
-                    if (any_neg) k -= (uint32_t)__popcll(__ballot(here && negr));
+                    const uint32_t k = (uint32_t)__popcll(__ballot((at.hi >> (j - 64u)) & 1u));
                     if (lane == j - 64u) c1 += k;
                 }
             }
             uint32_t *v = d.vec + (size_t)slot * FREE_MAX;
-            if (PM) {                                                         // (the map's counters belong to this kernel alone)
-                if (lane < n) v[lane] = c0;
-                if (64u + lane < n) v[64u + lane] = c1;
-                continue;
-            }
             // (added, not stored: commuters from other shards may have counted themselves there; atomics, because nobody has
             // to wait for them)
             if (lane < n && c0) atomicAdd(&v[lane], c0);
@@ -1736,8 +1320,6 @@ __device__ __forceinline__ uint32_t item_steps_regs(uint32_t c0, uint32_t c1, ui
 __device__ __forceinline__ uint32_t fetch_slot(const Dev &d, uint32_t slot, uint32_t lane);
 __device__ __forceinline__ void item_counts(const Dev &d, uint32_t x, uint32_t slot, uint32_t lane, uint32_t n, const M96 &AW,
                                             const M96 &BUS, uint32_t &c0, uint32_t &c1);
-__device__ __forceinline__ void pitem_counts(const Dev &d, uint32_t x, uint32_t slot, uint32_t lane, const ChunkT &ct, const M96 &AW,
-                                             const M96 &BUS, bool vec_only, uint32_t &c0, uint32_t &c1);
 __device__ __forceinline__ void school_counts(const Dev &d, uint32_t s_sch, uint32_t lane, uint32_t n, const Decision &q0, const Decision &q1, WaveScratch &ws)
 {
     // s_sch: the hash slot of the room's school (k_chunk_marks left it in the room's record): infected in the whole school, per
@@ -1827,34 +1409,14 @@ __device__ __forceinline__ void item_counts(const Dev &d, uint32_t x, uint32_t s
     }
 }
 
-// The same for a slot of the persistent map: its records are absolute (piv_count); beyond ITEM_RECS of them (or all of them:
-// vec_only, a school building) k_map_fold has left the sums in `vec`.
-__device__ __forceinline__ void pitem_counts(const Dev &d, uint32_t x, uint32_t slot, uint32_t lane, const ChunkT &ct, const M96 &AW,
-                                             const M96 &BUS, bool vec_only, uint32_t &c0, uint32_t &c1)
-{
-    const uint32_t cnt = FX(x, LANE_STATE) & PSLOT_COUNT;
-    c0 = 0u; c1 = 0u;
-    if (vec_only || cnt > ITEM_RECS) {                                     // (a school: k_map_fold stores its counters in every chunk it is listed for)
-        if (lane < ct.n) c0 = d.vec[(size_t)slot * FREE_MAX + lane];
-        if (64u + lane < ct.n) c1 = d.vec[(size_t)slot * FREE_MAX + 64u + lane];
-    }
-    if (vec_only) return;
-    const uint32_t n_rec = cnt < ITEM_RECS ? cnt : ITEM_RECS;
-    for (uint32_t k = 0; k < n_rec; ++k) piv_count(FX(x, 8u + k), lane, ct, AW, BUS, c0, c1);
-}
-
-template <bool PM>
-__device__ __forceinline__ ItemFetch decode_item(const Dev &d, uint32_t x, uint32_t lane, uint32_t n, const ChunkT &ct, const M96 &AW, const M96 &BUS)
+__device__ __forceinline__ ItemFetch decode_item(const Dev &d, uint32_t x, uint32_t lane, uint32_t n, const M96 &AW, const M96 &BUS)
 {
     ItemFetch f;
     f.slot = FX(x, LANE_HSLOT); f.id = FX(x, 0); f.a_lo = FX(x, 1); f.a_hi = FX(x, 2); f.b_lo = FX(x, 3); f.b_hi = FX(x, 4); f.aux = FX(x, 5); f.link = FX(x, 6);
     f.c0 = 0u; f.c1 = 0u;
     if (f.slot < d.hcap) {
-        if (PM) pitem_counts(d, x, f.slot, lane, ct, AW, BUS, false, f.c0, f.c1);
-        else {
-            item_counts(d, x, f.slot, lane, n, AW, BUS, f.c0, f.c1);
-            iv_count(FX(x, 7), lane, AW, BUS, f.c0, f.c1);
-        }
+        item_counts(d, x, f.slot, lane, n, AW, BUS, f.c0, f.c1);
+        iv_count(FX(x, 7), lane, AW, BUS, f.c0, f.c1);
     }
     return f;
 }
@@ -1963,10 +1525,6 @@ __device__ __forceinline__ void route_pair_big(const Dev &d, Ctrl *ctrl, const C
     __syncthreads();
 }
 
-// PM: the items are those of the persistent map -- ids handed out from SUBQ sub-lists (n_mw = SUBQ), counts from absolute records,
-// routes are items among the others (their records are their Infected riders: the bus steps with any are ranked right here, longer
-// routes go to k_chunk_units' list), and there is no list of (route, step) pairs.
-template <bool PM>
 __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
 {
     __shared__ ChunkShared sm;
@@ -2028,7 +1586,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
     const uint32_t w_base = wave % n_mw, w_rep = wave / n_mw;
     uint32_t code_l = 0u, off_l = 0u, sz_l = 0u;
     bool have = false;
-    if (!PM) {
+    {
         const uint32_t k = lane * G + w_rep;
         if (k < K) {
             const uint32_t src = (w_base + n_mw - (uint32_t)(((unsigned long long)k * PAIR_SPREAD) % n_mw)) % n_mw;
@@ -2046,7 +1604,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
     M96 AW, BUS;
     schedule_masks(lane, n, q0, q1, AW, BUS);
     const M96 EV = { __ballot(lane < n && q0.mask == ESIM_MASK_EVERYWHERE), (uint32_t)__ballot(64u + lane < n && q1.mask == ESIM_MASK_EVERYWHERE) };
-    const ChunkT ct = chunk_t(d, t0, n);
     if (d_lo < d_hi) sl_cur = fetch_slot(d, FX(id_cur, LANE_HSLOT), lane);
     if (have) { const uint32_t r = code_l >> 7; off_l = d.route_off[r]; sz_l = d.route_off[r + 1] - off_l; }
 #ifdef ESIM_WAVE_PROFILE
@@ -2061,49 +1618,10 @@ __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
         if (v + 2u < d_hi) id_nxt = fetch_item(d, id_of(v + 2u), lane);
         if (v + 1u < d_hi) sl_cur = fetch_slot(d, FX(id_cur, LANE_HSLOT), lane);
         const uint32_t pq0 = PROF_NOW();
-        const ItemFetch it = decode_item<PM>(d, x, lane, n, ct, AW, BUS);
+        const ItemFetch it = decode_item(d, x, lane, n, AW, BUS);
         if (it.slot == ITEM_UNUSED) continue;
         if (!item_ok(d, it)) { if (lane == 0) RAISE(ctrl, ESIM_ERANGE, ERR_AT_ITEM_CHECK); continue; }
-        // (persistent map: an item whose records all lie outside the chunk -- recovered, or at home under a lockdown -- is left
-        // here, before any member is fetched)
-        if (PM && !__any((it.c0 | it.c1) != 0u)) continue;
-        if (it.id >= route_base) {
-            if (PM) {
-                // the bus steps in which an Infected rider of this route is on the bus: c0 / c1 count them per step
-                const uint32_t r = it.id - route_base, sz = it.a_hi - it.a_lo;
-                if (r >= d.n_routes || it.a_hi < it.a_lo || it.a_hi > d.n_pt) { if (lane == 0) RAISE(ctrl, ESIM_ERANGE, ERR_AT_ROUTE_ITEM); continue; }
-                const unsigned long long m_lo = __ballot(it.c0 != 0u) & BUS.lo;
-                const uint32_t m_hi = (uint32_t)__ballot(lane < FREE_MAX - 64u && it.c1 != 0u) & BUS.hi;
-                if (sz <= 64u) {
-                    // (registered for k_chunk_units, which deals the pairs of all wavefronts out evenly -- ranked right here they
-                    // made the slowest wavefront twice the median --; a stretch that is full: ranked here after all)
-                    const uint32_t np = (uint32_t)__popcll(m_lo) + (uint32_t)__popc(m_hi), rp_cap = 2u * d.items_cap / SUBQ, qr = wave & (SUBQ - 1u);
-                    uint32_t at = 0u;
-                    if (lane == 0) at = atomicAdd(&d.hot[(HOT_RPAIRS + qr) * HOT_STRIDE], np);      // (one reservation per route item, 64 lists)
-                    at = FX(at, 0);
-                    uint32_t *list = d.route_pairs + (size_t)qr * rp_cap;
-                    uint32_t i = 0u;
-                    for (unsigned long long m = m_lo; m; m &= m - 1ull, ++i) {
-                        const uint32_t j = (uint32_t)__builtin_ctzll(m);
-                        if (at + i < rp_cap) { if (lane == 0) list[at + i] = (r << 7) | j; } else route_pair_small(d, ctrl, sm, it.a_lo, sz, j, t0, lane WORK_PASS);
-                    }
-                    for (uint32_t m = m_hi; m; m &= m - 1u, ++i) {
-                        const uint32_t j = 64u + (uint32_t)__builtin_ctz(m);
-                        if (at + i < rp_cap) { if (lane == 0) list[at + i] = (r << 7) | j; } else route_pair_small(d, ctrl, sm, it.a_lo, sz, j, t0, lane WORK_PASS);
-                    }
-                } else {
-                    const uint32_t np = (uint32_t)__popcll(m_lo) + (uint32_t)__popc(m_hi);
-                    uint32_t at = 0u;
-                    if (lane == 0) at = atomicAdd(&d.hot[HOT_BIGPAIRS * HOT_STRIDE], np);
-                    at = FX(at, 0);
-                    if (at + np > 2u * d.items_cap) { if (lane == 0) RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIGPAIRS); continue; }
-                    uint32_t i = 0u;
-                    for (unsigned long long m = m_lo; m; m &= m - 1ull, ++i) if (lane == 0) d.route_pairs_big[at + i] = (r << 7) | (uint32_t)__builtin_ctzll(m);
-                    for (uint32_t m = m_hi; m; m &= m - 1u, ++i) if (lane == 0) d.route_pairs_big[at + i] = (r << 7) | (64u + (uint32_t)__builtin_ctz(m));
-                }
-            }
-            continue;
-        }
+        if (it.id >= route_base) continue;
         const uint32_t pi0 = PROF_NOW();
         pst[0] += pi0 - pq0;
         (void)pi0; ++p_items; WORK_ADD(WK_ITEMS, lane == 0 ? 1 : 0);
@@ -2145,7 +1663,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
     const uint32_t pt2 = PROF_NOW();
     // (2) routes of <= 64 riders: one wavefront per (route, bus step) with an Infected rider (the pairs dealt to this wavefront --
     // see the first look above --, taken one by one)
-    for (uint32_t k0 = 0; !PM && k0 * G < K; k0 += 64u) {
+    for (uint32_t k0 = 0; k0 * G < K; k0 += 64u) {
         if (k0) {                                                             // (beyond the 64 looked at up front: many Infected)
             const uint32_t kk = (k0 + lane) * G + w_rep;
             have = false;
@@ -2177,7 +1695,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_draw(Dev d, uint32_t n_mw)
 
 // The deferred units of long member lists, dealt to the wavefronts round-robin.
 // Then the routes of more than 64 riders: one workgroup per (route, bus step), ranks through LDS.
-template <bool PM>
 __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
 {
     __shared__ ChunkShared sm;
@@ -2195,10 +1712,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
     const uint32_t qr = wave & (SUBQ - 1u), first = wave / SUBQ, step = n_waves / SUBQ;
     const uint32_t n_units = step ? min(ld(&d.hot[(HOT_UNITS + qr) * HOT_STRIDE]), d.unit_qcap) : 0u;
     const uint32_t n_pairs = min(ld(&d.hot[HOT_BIGPAIRS * HOT_STRIDE]), 2u * d.items_cap);
-    // (persistent map: the pairs of routes of <= 64 riders that k_chunk_draw registered are dealt out here, see below)
-    const uint32_t rp_cap = 2u * d.items_cap / SUBQ;
-    const uint32_t n_rp = (PM && step) ? min(ld(&d.hot[(HOT_RPAIRS + qr) * HOT_STRIDE]), rp_cap) : 0u;
-    if (__syncthreads_or(first < n_units || first < n_rp) == 0 && n_pairs == 0u) return;
+    if (__syncthreads_or(first < n_units) == 0 && n_pairs == 0u) return;
     for (uint32_t i = threadIdx.x; i < n; i += TPB) sm.dec[i] = d.dec[i];
     for (uint32_t i = threadIdx.x; i < 512u; i += TPB) sm.thr[i] = d.thr[i];
     __syncthreads();
@@ -2209,7 +1723,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
     M96 AW, BUS;
     schedule_masks(lane, n, q0, q1, AW, BUS);
     const M96 EV = { __ballot(lane < n && q0.mask == ESIM_MASK_EVERYWHERE), (uint32_t)__ballot(64u + lane < n && q1.mask == ESIM_MASK_EVERYWHERE) };
-    const ChunkT ct = chunk_t(d, t0, n);
     // Per unit: its record (lanes 0..7 of one register); then, together, the slot's interval records, the school's, and the
     // ids of the first members its pairs touch; then those members' words.  The record of the unit after next and the
     // second stage of the next are in flight while this one draws.
@@ -2241,11 +1754,11 @@ __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
         const uint32_t kind = code >> 30, p_lo = code & 0x3FFFFFFFu, slot = FX(u, 0), link = FX(u, 1), lo = FX(u, 2), n_mem = FX(u, 3), own = FX(u, 5), mf = FX(u, 6);
         const uint32_t mw = (mf + lane < n_mem) ? d.cit[mid] : 0u;
         uint32_t c0, c1;
-        if (PM) pitem_counts(d, xs, slot, lane, ct, AW, BUS, false, c0, c1);
-        else { item_counts(d, xs, slot, lane, n, AW, BUS, c0, c1); iv_count(own, lane, AW, BUS, c0, c1); }
+        item_counts(d, xs, slot, lane, n, AW, BUS, c0, c1);
+        iv_count(own, lane, AW, BUS, c0, c1);
         if (kind == 2u) {
             uint32_t s0 = 0u, s1 = 0u;
-            if (link != 0xFFFFFFFFu) { if (PM) pitem_counts(d, ys, link, lane, ct, AW, BUS, true, s0, s1); else item_counts(d, ys, link, lane, n, AW, BUS, s0, s1); }
+            if (link != 0xFFFFFFFFu) item_counts(d, ys, link, lane, n, AW, BUS, s0, s1);
             ws.sch[lane] = s0;
             if (lane < FREE_MAX - 64u) ws.sch[64u + lane] = s1;
         }
@@ -2264,18 +1777,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
     PROF_PUT(d, 0, pu0); PROF_PUT(d, 1, pu1); PROF_PUT(d, 2, pu2); PROF_PUT(d, 4, pu_n); PROF_PUT(d, 5, pu_max); PROF_PUT(d, 7, pu_it);
 #endif
     (void)pu0; (void)pu1; (void)pu2; (void)pu_n; (void)pu_max; (void)pu_it;
-    if (PM) {
-        // list `wave & 63` of the (route, bus step) pairs k_chunk_draw registered, every (n_waves / 64)-th entry of it; the next
-        // pair's route is looked up while this one is ranked
-        const uint32_t *list = d.route_pairs + (size_t)qr * rp_cap;
-        uint32_t code = first < n_rp ? list[first] : 0u, off = 0u, sz = 0u;
-        if (first < n_rp && (code >> 7) < d.n_routes) { off = d.route_off[code >> 7]; sz = d.route_off[(code >> 7) + 1u] - off; }
-        for (uint32_t q = first; q < n_rp; q += step) {
-            const uint32_t c_code = code, c_off = off, c_sz = sz;
-            if (q + step < n_rp) { code = list[q + step]; if ((code >> 7) < d.n_routes) { off = d.route_off[code >> 7]; sz = d.route_off[(code >> 7) + 1u] - off; } else sz = 0u; }
-            if ((c_code >> 7) < d.n_routes && (c_code & 127u) < n && c_sz <= 64u) route_pair_small(d, ctrl, sm, c_off, c_sz, c_code & 127u, t0, lane WORK_PASS);
-        }
-    }
     for (uint32_t q = blockIdx.x; q < n_pairs; q += gridDim.x) route_pair_big<TPB>(d, ctrl, sm, rs, d.route_pairs_big[q], t0, n WORK_PASS);
     WORK_FLUSH(d);
 }
@@ -2368,7 +1869,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_scatter(Dev d)
     }
     // the hash slots (and spilled count vectors) of the ids that were handed out: a thread per (wavefront of k_chunk_marks,
     // k-th id of its range), so that the whole clean-up is three dependent loads deep
-    if (ctrl->prev_pmap) return;                                              // (the persistent map stays)
     const uint32_t per_wave = ctrl->prev_per_wave, n_mw = per_wave ? n_items / per_wave : 0u;
     const uint32_t tid = blockIdx.x * TPB + threadIdx.x, nth = gridDim.x * TPB;
     for (uint32_t i = tid; i < n_mw * per_wave; i += nth) {
@@ -2392,16 +1892,6 @@ __global__ __launch_bounds__(TPB) void k_chunk_vax_final(Dev d)
     Ctrl *ctrl = d.ctrl;
     if (!ctrl->prev_vax) return;
     const uint32_t n_eff = ctrl->prev_n_eff;
-    // persistent map: the cancellation records of steps that were not committed are taken back (zeroed where they stand); those of
-    // committed steps stay for good.  (n_neg is reset by the plan kernel of the next chunk: other workgroups still read it here.)
-    {
-        const uint32_t n_neg = min(ctrl->n_neg, NEG_CAP);
-        for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < n_neg; i += gridDim.x * TPB) {
-            const uint32_t where = d.neg_list[2u * i], j = d.neg_list[2u * i + 1u];
-            if (j < n_eff) continue;
-            if (where & 0x80000000u) d.ovf[where & 0x7FFFFFFFu] = 0u; else d.slot_iv[where] = 0u;
-        }
-    }
     // (the plan may reach beyond the chunk: the decisions can end a chunk early, k_decide)
     const uint32_t n = ctrl->prev_planned;
     for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {
@@ -2612,11 +2102,11 @@ __device__ __forceinline__ void books_body(const Dev &d, int fused, int do_next,
     if (!fused) {
         // k_chunk_scatter runs after this kernel, i.e. after the next chunk's decisions have reset what it reads: keep a copy
         if (tid < SUBQ) d.hot[(HOT_PREV_NEWEXP + tid) * HOT_STRIDE] = n_new;   // (thread r < 64 read sub-list r's length above)
-        if (tid == 0) { ctrl->prev_t0 = t0; ctrl->prev_n_items = n_items; ctrl->prev_per_wave = ld(&ctrl->items_per_wave); ctrl->prev_pmap = ld(&ctrl->pmap_chunk);
+        if (tid == 0) { ctrl->prev_t0 = t0; ctrl->prev_n_items = n_items; ctrl->prev_per_wave = ld(&ctrl->items_per_wave);
                         ctrl->prev_n = n; ctrl->prev_n_eff = n_eff; ctrl->prev_vax = vax ? 1u : 0u; ctrl->prev_planned = ld(&ctrl->vax_planned); ctrl->vax_chunk = 0u; }
         // (its per-step write cursors were set above, a row per EXP_ROWS-th workgroup)
     }
-    if (tid == 0) { ctrl->chunk_done = 1u; if (ld(&ctrl->pmap_chunk)) ctrl->map_t = t0 + n_eff; }   // the map now stands at the step the next chunk starts with
+    if (tid == 0) ctrl->chunk_done = 1u;
     if (tid < 64u) {
         // totals of the split lists, for esim_debug_counters
         uint32_t a = ld(&d.hot[(HOT_NEWEXP + tid) * HOT_STRIDE]), b = ld(&d.hot[(HOT_UNITS + tid) * HOT_STRIDE]);
@@ -2633,7 +2123,7 @@ __device__ __forceinline__ void books_body(const Dev &d, int fused, int do_next,
         }
         // the ids each wavefront of k_chunk_marks handed out: thread t looks after the wavefronts t, t + 1024, ...; all loads
         // of a round are in flight together (this loop is nothing but memory latency)
-        const uint32_t per_wave = ld(&ctrl->items_per_wave), n_mw = (per_wave && !ld(&ctrl->pmap_chunk)) ? n_items / per_wave : 0u;   // (the persistent map stays)
+        const uint32_t per_wave = ld(&ctrl->items_per_wave), n_mw = per_wave ? n_items / per_wave : 0u;
         for (uint32_t w0 = tid; w0 < n_mw; w0 += 4u * FIN_TPB) {
             uint32_t used[4], h[4][4];
 #pragma unroll

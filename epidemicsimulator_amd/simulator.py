@@ -337,7 +337,8 @@ class Simulator:
         _lib.check(self.lib.esim_set_tiny_chunk_limit(self._ctx, int(max_pairs)), self._ctx)
 
     def set_pipeline(self, level):
-        """0: sequential steps only; 1: chunks as one kernel per step; 2 (default): time-parallel chunks."""
+        """0: sequential steps only; 1: chunks as one kernel per step; 2: time-parallel chunks; 3 (default): also under a vaccination
+        programme.  Any level above 3 runs as 3."""
         _lib.check(self.lib.esim_set_pipeline(self._ctx, int(level)), self._ctx)
 
     def chunk_timing(self):

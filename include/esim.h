@@ -165,11 +165,10 @@ int  esim_exchange_buffer(esim_ctx *ctx, int which /* 0 = A, 1 = B, 2 = F */, vo
  * writing the census ahead of the chunk after it into F -- and calls esim_free_collect(&done) once: done = steps the
  * burst advanced (the same on all shards).
  * esim_set_pipeline(ctx, level): 0 = sequential steps only; 1 = chunks run as one kernel per step (k_pipe);
- * 3 (default) = as 2, and chunks keep running under a vaccination programme (esim_vax_chunk_stats); 4 = as 3 on the persistent
- * item map (a citizen is entered into the items it stands in once, when it turns Infected, instead of in every chunk; unsharded contexts);
  * 2 = additionally to 1, when the chunk's marks fit the hash map, ALL steps of a chunk are drawn in one
  * pass (a citizen's exposure step is the earliest step at which any of its draws succeeds -- one atomicMin on
- * the citizen word per successful draw).  esim_chunk_timing: device time (ms), steps and number of such chunks
+ * the citizen word per successful draw); 3 (default) = as 2, and chunks keep running under a vaccination programme
+ * (esim_vax_chunk_stats).  Any level above 3 runs as 3.  esim_chunk_timing: device time (ms), steps and number of such chunks
  * since the last call (measured while kernel timing is enabled). */
 /* ---- the exchange between shards, owned by the library ("library owns streams / RCCL communicators") ----
  * esim_comm_unique_id     -- ncclGetUniqueId on one rank (cap >= 128 bytes); the caller carries it to the other ranks
@@ -219,7 +218,9 @@ int  esim_chunk_timing(esim_ctx *ctx, double *total_ms, uint64_t *steps, uint64_
  * "Generate Exposures" = marks + fold, "Apply Exposures" = draw + units, "Apply Interventions" = everything else (plan,
  * decisions, counts, books, scatter) -- apportioned: a chunk pass works on up to 96 steps at once.  ESIM_CK_TINY: a whole chunk
  * with few Infected in one launch (census ahead, decisions, marks, draws, books): the Python binding shares it out over the
- * three labels by the kernel's own stage timers (entries and keys 10 %, draws 40 %, census, decisions and books 50 %). */
+ * three labels by the kernel's own stage timers (entries and keys 10 %, draws 40 %, census, decisions and books 50 %).
+ * ESIM_CK_VAX_ADJ and ESIM_CK_MAP_CLEAR always report 0 (their kernels served the persistent item map, which is gone; the
+ * indices are kept so that the others keep theirs). */
 enum { ESIM_CK_MARKS = 0, ESIM_CK_FOLD, ESIM_CK_DRAW, ESIM_CK_UNITS, ESIM_CK_COUNT, ESIM_CK_BOOKS, ESIM_CK_SCATTER, ESIM_CK_VAX, ESIM_CK_VAX_ADJ,
        ESIM_CK_VAX_FINAL, ESIM_CK_DECIDE, ESIM_CK_FUTURE, ESIM_CK_MAP_CLEAR, ESIM_CK_TINY, ESIM_CK_VAX_REPAIR, ESIM_CK_N };
 int  esim_enable_chunk_kernel_timing(esim_ctx *ctx, int enable);
@@ -301,7 +302,7 @@ int  esim_set_tiny_chunk_limit(esim_ctx *ctx, uint32_t max_pairs);
 int  esim_pipeline_timing(esim_ctx *ctx, double *mean_step_ms, uint64_t *steps_timed, uint64_t *steps_run);
 
 /* Diagnostics: the control block's view of the last chunk (t, chunk_ok, chunk_parallel, chunk_pairs, n_items,
- * items_per_wave, n_units, n_route_pairs, n_route_pairs_big, n_newexp, log_len, n_susceptible, lockdown, mask,
+ * items_per_wave, n_units, 0 (was n_route_pairs), n_route_pairs_big, n_newexp, log_len, n_susceptible, lockdown, mask,
  * at_work, bus_dir). */
 int  esim_debug_counters(esim_ctx *ctx, uint32_t out[16]);
 

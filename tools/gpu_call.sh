@@ -24,28 +24,12 @@ for step in $steps; do
             echo -n "york grid 1024: "; timeout -k 10 300 python tools/run_preset.py york | grep us/step | cut -c1-140
             echo -n "york grid 64:   "; ESIM_GRID_CHUNK=64 timeout -k 10 300 python tools/run_preset.py york | grep us/step | cut -c1-140
             echo -n "york grid 16:   "; ESIM_GRID_CHUNK=16 timeout -k 10 300 python tools/run_preset.py york | grep us/step | cut -c1-140 ;;
-    pmap) ESIM_PMAP_REBUILD=1 timeout -k 10 300 python tools/fuzz_parity.py 2000 40 > gpurun_out/fuzz_pm1_$tag.log 2>&1; rc=$?; tail -3 gpurun_out/fuzz_pm1_$tag.log; [ $rc -eq 0 ] || exit $rc
-          timeout -k 10 300 python tools/fuzz_parity.py 2000 40 > gpurun_out/fuzz_pm4_$tag.log 2>&1; rc=$?; tail -3 gpurun_out/fuzz_pm4_$tag.log; [ $rc -eq 0 ] || exit $rc
-          ESIM_PMAP_REBUILD=1000 timeout -k 10 300 python tools/fuzz_parity.py 3000 40 > gpurun_out/fuzz_pmx_$tag.log 2>&1; rc=$?; tail -3 gpurun_out/fuzz_pmx_$tag.log; [ $rc -eq 0 ] || exit $rc ;;
-    pmab) for i in 1 2; do
-            echo -n "rebuilt per chunk (old): "; ESIM_PMAP=0 timeout -k 10 200 python tools/run_preset.py uk64m | grep us/step | cut -c1-110 || exit 5
-            for r in 1 2 4 8 1000; do echo -n "persistent, rebuild every $r: "; ESIM_PMAP_REBUILD=$r timeout -k 10 200 python tools/run_preset.py uk64m | grep us/step | cut -c1-110 || exit 5; done
-          done
-          for p in york syn3m5 yh_census; do echo -n "$p old: "; ESIM_PMAP=0 timeout -k 10 200 python tools/run_preset.py $p | grep us/step | cut -c1-110; echo -n "$p persistent: "; timeout -k 10 200 python tools/run_preset.py $p | grep us/step | cut -c1-110; done ;;
-    bigfuzz) timeout -k 10 400 python tools/fuzz_parity.py 9000 16 --big > gpurun_out/fuzz_big_$tag.log 2>&1; rc=$?; tail -2 gpurun_out/fuzz_big_$tag.log; [ $rc -eq 0 ] || exit $rc
-          ESIM_PMAP_REBUILD=1000 timeout -k 10 400 python tools/fuzz_parity.py 9100 16 --big > gpurun_out/fuzz_bigx_$tag.log 2>&1; rc=$?; tail -2 gpurun_out/fuzz_bigx_$tag.log; [ $rc -eq 0 ] || exit $rc
-          ESIM_GRID_CHUNK=16 ESIM_PMAP_REBUILD=3 timeout -k 10 300 python tools/fuzz_parity.py 12000 20 --big > gpurun_out/fuzz_g16_$tag.log 2>&1; rc=$?; tail -1 gpurun_out/fuzz_g16_$tag.log; [ $rc -eq 0 ] || exit $rc ;;
     kt) timeout -k 10 200 python tools/kernel_times.py uk64m || exit 5 ;;
     ktgrid) for v in "1024 4" "768 4" "512 8"; do set -- $v; echo -n "grid $1 draw mult $2: "; ESIM_GRID_CHUNK=$1 ESIM_DRAW_MULT=$2 ESIM_UNITS_MULT=$2 timeout -k 10 200 python tools/kernel_times.py uk64m | cut -c40-330 || exit 5; done ;;
-    ktimes) ESIM_PMAP=0 timeout -k 10 200 python tools/kernel_times.py uk64m || exit 5
-            ESIM_PMAP_REBUILD=1 timeout -k 10 200 python tools/kernel_times.py uk64m || exit 5
-            ESIM_PMAP_REBUILD=4 timeout -k 10 200 python tools/kernel_times.py uk64m || exit 5 ;;
-    wavepm) ESIM_PMAP=0 ESIM_DRAW_MULT=1 ESIM_UNITS_MULT=1 timeout -k 10 300 python tools/wave_profile.py uk64m 2880 3840 2>&1 | grep -E "draw:|marks" | cut -c1-330
-            ESIM_PMAP_REBUILD=4 ESIM_DRAW_MULT=1 ESIM_UNITS_MULT=1 timeout -k 10 300 python tools/wave_profile.py uk64m 2880 3840 2>&1 | grep -E "draw:|marks" | cut -c1-330 ;;
-    counts) ESIM_PMAP=0 timeout -k 10 300 python tools/work_counts.py cnt_old uk64m | cut -c1-900 || exit 5
-            timeout -k 10 300 python tools/work_counts.py cnt_pm uk64m | cut -c1-900 || exit 5 ;;
-    waveu) ESIM_PMAP=0 timeout -k 10 300 python tools/wave_profile_units.py uk64m 2880 3840 2>&1 | cut -c1-330
-           timeout -k 10 300 python tools/wave_profile_units.py uk64m 2880 3840 2>&1 | cut -c1-330 ;;
+    ktimes) timeout -k 10 200 python tools/kernel_times.py uk64m || exit 5 ;;
+    wavepm) ESIM_DRAW_MULT=1 ESIM_UNITS_MULT=1 timeout -k 10 300 python tools/wave_profile.py uk64m 2880 3840 2>&1 | grep -E "draw:|marks" | cut -c1-330 ;;
+    counts) timeout -k 10 300 python tools/work_counts.py cnt uk64m | cut -c1-900 || exit 5 ;;
+    waveu) timeout -k 10 300 python tools/wave_profile_units.py uk64m 2880 3840 2>&1 | cut -c1-330 ;;
     presets) for p in york syn3m5 yh_census uk64m; do timeout -k 10 200 python tools/run_preset.py $p | grep us/step | cut -c1-150 || exit 5; done ;;
     smallgrid) for v in "0 1" "64 1" "64 4" "128 4" "256 1" "32 8"; do set -- $v; for i in 1 2; do echo -n "small grid $1 mult $2: "; ESIM_SMALL_GRID=$1 ESIM_SMALL_MULT=$2 timeout -k 10 200 python tools/run_preset.py york | grep us/step | cut -c1-110 || exit 5; done; done
             for v in "0 1" "64 4"; do set -- $v; echo -n "bench20 small grid $1 mult $2: "; ESIM_SMALL_GRID=$1 ESIM_SMALL_MULT=$2 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-extra-runs --cpu-seconds 0 | python -c "import sys,json; d=json.loads(sys.stdin.read()); t=d['config']['timed_region']; print(t['wall_us_per_step']*20, t['chunk_passes_device_ms']*1e3)" || exit 6; done ;;
