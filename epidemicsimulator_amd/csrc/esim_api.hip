@@ -329,11 +329,11 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     const uint32_t n_routes = (uint32_t)route_off.size();
     route_off.push_back((uint32_t)pairs.size());
     bool any_big = false;
-    uint32_t max_route = 0;
+    uint32_t max_route = 0, n_big_routes = 0;
     for (uint32_t r = 0; r < n_routes; ++r) {
         const uint32_t sz = route_off[r + 1] - route_off[r];
         max_route = std::max(max_route, sz);
-        if (sz > 64) { any_big = true; for (uint32_t q = route_off[r]; q < route_off[r + 1]; ++q) fl[riders[q]] |= FL_BIG_ROUTE; }
+        if (sz > 64) { any_big = true; ++n_big_routes; for (uint32_t q = route_off[r]; q < route_off[r + 1]; ++q) fl[riders[q]] |= FL_BIG_ROUTE; }
     }
     { std::vector<std::pair<uint64_t, uint32_t>>().swap(pairs); }
 
@@ -435,10 +435,15 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
         d.unit_qcap = (uint32_t)std::max<size_t>(1024, units * 2u / SUBQ);
         if ((rc = dev_alloc(c, &d.units, (size_t)d.unit_qcap * SUBQ))) return rc;
         if ((rc = dev_alloc(c, &d.route_pairs, (size_t)d.items_cap * (CHUNK_BUS_STEPS / 4u)))) return rc;   // (PAIR_K: up to CHUNK_BUS_STEPS / 4 per item id)
-        if ((rc = dev_alloc(c, &d.route_pairs_big, (size_t)d.items_cap * 2u))) return rc;
+        // A (big route, bus step) pair is registered once a chunk, by the entry that first sets the step's bit on the route's item:
+        // at most CHUNK_BUS_STEPS pairs per route item (k_decide), and at most one route item per entry -- items_cap / 4 of them
+        // (k_chunk_marks' id-range check) and no more than there are big routes.  (2 * items_cap, the size before, is exceeded by a
+        // lockdown that freezes riders on a bus: 32 bus steps in a chunk with more than items_cap / 16 big routes carrying an Infected.)
+        d.big_pairs_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)d.items_cap / 4u, n_big_routes) * CHUNK_BUS_STEPS);
+        if ((rc = dev_alloc(c, &d.route_pairs_big, d.big_pairs_cap))) return rc;
         HIP_TRY(c, hipMemset(d.units, 0xFF, sizeof(UnitRec) * (size_t)d.unit_qcap * SUBQ));     // code == UNIT_NOOP
         HIP_TRY(c, hipMemset(d.route_pairs, 0, sizeof(uint32_t) * (size_t)d.items_cap * (CHUNK_BUS_STEPS / 4u)));
-        HIP_TRY(c, hipMemset(d.route_pairs_big, 0, sizeof(uint32_t) * (size_t)d.items_cap * 2u));
+        HIP_TRY(c, hipMemset(d.route_pairs_big, 0, sizeof(uint32_t) * (size_t)d.big_pairs_cap));
         {
             // (a school building's records are those of everybody who works or learns there: its members are in the room lists)
             std::vector<uint32_t> sch_members((size_t)B + 1, 0);
@@ -1591,6 +1596,7 @@ extern "C" int esim_run_sharded(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_don
     // different steps would issue different collectives): a flag an earlier esim_run left on the device is cleared
     static const uint32_t zero = 0u;
     HIP_TRY(c, hipMemcpyAsync(&d.ctrl->stop_when_done, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
+    c->stop_flag_dev = 0u;                                        // (esim_run compares against it before it writes the flag)
     // (a communicator on an unsharded context -- one rank -- still makes its collectives: the sums over one rank change nothing,
     // which is how the RCCL path is exercised on a one-GPU box)
     const bool ex = d.n_shards > 1 || c->nccl || c->comm_fn;
@@ -1818,7 +1824,7 @@ extern "C" int esim_debug_counters(esim_ctx *ctx, uint32_t out[16])
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     Ctrl h;
     HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
-    const uint32_t v[16] = { h.t, h.chunk_ok, h.chunk_parallel, h.chunk_pairs, h.n_items, h.items_per_wave, h.n_units, 0u,
+    const uint32_t v[16] = { h.t, h.chunk_ok, h.chunk_parallel, h.chunk_pairs, h.n_items, h.items_per_wave, h.n_units, h.chunk_bus,
                              h.n_route_pairs_big, h.n_newexp, h.log_len, h.n_susceptible, h.lockdown, h.mask, h.at_work, h.bus_dir };
     std::memcpy(out, v, sizeof v);
     return ESIM_OK;
@@ -2119,6 +2125,7 @@ extern "C" int esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t by
     if ((rc = push(d.exp_step, sizeof(uint32_t) * 2u * ((size_t)k.host_t + 1u)))) return rc;
     if ((rc = push(d.records, sizeof(esim_step_result) * (size_t)k.host_t))) return rc;
     HIP_TRY(c, hipMemcpy(d.ctrl, &h, sizeof h, hipMemcpyHostToDevice));
+    c->stop_flag_dev = h.stop_when_done;                          // (the saved block's flag is now the device's: esim_run compares against it)
     c->host_t = k.host_t;
     c->last_chunk_pairs = h.chunk_pairs;
     c->elig_seen = h.have_elig != 0u;

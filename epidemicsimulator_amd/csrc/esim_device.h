@@ -185,11 +185,12 @@ struct Dev {
     uint32_t *vec;              // [hcap][FREE_MAX] per-step counts of the Infected that found no record free
     uint32_t items_cap;
     struct UnitRec *units;      // [SUBQ][unit_qcap] deferred units of long member lists
-    uint32_t *route_pairs;      // [2 * items_cap] route << 7 | step of the chunk, routes of <= 64 riders: wavefront w of
-                                // k_chunk_marks owns entries [w * 2 * items_per_wave, ...), pair_cnt[w] of them are filled
+    uint32_t *route_pairs;      // [items_cap * CHUNK_BUS_STEPS / 4] route << 7 | step of the chunk, routes of <= 64 riders: wavefront w
+                                // of k_chunk_marks owns entries [w * PAIR_K, ...), pair_cnt[w] of them are filled
     uint32_t *pair_cnt;         // [wavefronts of k_chunk_marks]
     uint32_t *used_cnt;         // [wavefronts of k_chunk_marks] item ids the wavefront handed out
-    uint32_t *route_pairs_big;  // [2 * items_cap] the same for longer routes, one shared list
+    uint32_t *route_pairs_big;  // [big_pairs_cap] the same for longer routes, one shared list
+    uint32_t big_pairs_cap;     // min(items_cap / 4, routes of more than 64 riders) * CHUNK_BUS_STEPS (esim_upload_population)
     // interval records beyond a slot's ITEM_RECS: a building's go to ovf[ovf_off[b] ...) (room for one per resident and worker), a
     // room's to ovf[ovf_room_base + room_off[r] ...); k_chunk_fold sums them into `vec` before the draw pass
     const uint32_t *ovf_off;    // [n_bld + 1] res_off + wrk_off

@@ -224,7 +224,7 @@ __device__ __forceinline__ void decide_body(const Dev &d, uint32_t max_ahead, ui
         const uint32_t bus_steps = (uint32_t)(__popcll(bus_m0) + __popcll(bus_m1));
         ctrl->chunk_parallel = (allow_parallel && ld(&d.xf[d.xf_n]) == 0u && bus_steps <= CHUNK_BUS_STEPS) ? 1u : 0u;
         ctrl->chunk_bus = bus_steps;
-        ctrl->n_items = 0u; ctrl->n_newexp = 0u; ctrl->n_units = 0u; ctrl->unit_next = 0u; ctrl->n_route_pairs_big = 0u;
+        ctrl->n_items = 0u; ctrl->n_newexp = 0u; ctrl->n_units = 0u; ctrl->unit_next = 0u;   // (n_route_pairs_big: the last chunk's, esim_debug_counters)
     }
     d.cursor[lane] = 0u;
     if (lane < FREE_MAX - 64u) d.cursor[64u + lane] = 0u;
@@ -710,6 +710,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
     if (d.world > 1u) for (uint32_t r = 0; r < d.world; ++r) if (r != d.rank) n_remote += min(d.xs[(size_t)r * (1u + 3u * d.xs_cap)], d.xs_cap);
     const uint32_t per_wave = 4u * ((i1 - i0 + n_remote + n_waves - 1u) / n_waves + (n_remote ? 1u : 0u));
     if (wave == 0 && lane == 0) { ctrl->items_per_wave = per_wave; ctrl->n_items = per_wave * n_waves; }
+    // (cannot fail on one shard: per_wave * n_waves <= 4 * E + 4 * CHUNK_WAVES_MAX <= 4 * E + 65 536 <= items_cap, future_body; E <= pairs)
     if ((unsigned long long)per_wave * n_waves > d.items_cap) { if (lane == 0) ctrl->error = (uint32_t)(-ESIM_ERANGE); return; }
     uint32_t next_id = wave * per_wave;
     const Decision q0 = lane < n ? d.dec[lane] : Decision{ 0u, 0u, 0u, 0u };
@@ -825,6 +826,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
                     if (old == HKEY_EMPTY) { claimed[k] = true; found = true; }
                     else if (old == key[k]) { pending[k] = true; found = true; }
                 }
+                // (cannot fail: at most 4 keys per entry, <= items_cap = hcap / 4 of them -- load <= 1/4)
                 if (!found) { ctrl->error = (uint32_t)(-ESIM_ERANGE); key[k] = HKEY_EMPTY; h = 0u; }
                 slot[k] = h;
             }
@@ -934,6 +936,8 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
                 if (first[1] && pos < d.big_qcap) { bl[3u * pos] = slot[1]; bl[3u * pos + 1u] = first_base[1]; bl[3u * pos + 2u] = first_cap[1]; }
                 pos = at0 + (uint32_t)__popcll(f0) + (uint32_t)__popcll(f1) + (uint32_t)__popcll(f2 & lt);
                 if (first[2] && pos < d.big_qcap) { bl[3u * pos] = slot[2]; bl[3u * pos + 1u] = first_base[2]; bl[3u * pos + 2u] = first_cap[2]; }
+                // (cannot fail: a wavefront lists <= 3 slots per entry, <= 3/4 per_wave; queue r serves n_waves / SUBQ wavefronts (grids are
+                // whole groups of 64 wavefronts), so <= 3/4 * items_cap / SUBQ < big_qcap)
                 if (at0 + n_first > d.big_qcap && lane == 0) ctrl->error = (uint32_t)(-ESIM_ERANGE);
             }
         }
@@ -965,7 +969,8 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
             if (n_big) {
                 if (lane == 0) big_base = atomicAdd(&d.hot[HOT_BIGPAIRS * HOT_STRIDE], n_big);
                 big_base = __shfl(big_base, 0, 64);
-                if (big_base + n_big > 2u * d.items_cap) { if (lane == 0) ctrl->error = (uint32_t)(-ESIM_ERANGE); n_big = 0u; big_base = 0xFFFFFFFFu; }
+                // (cannot fail: big_pairs_cap bounds the distinct (big route, bus step) pairs of any chunk, esim_upload_population)
+                if (big_base + n_big > d.big_pairs_cap) { if (lane == 0) ctrl->error = (uint32_t)(-ESIM_ERANGE); n_big = 0u; big_base = 0xFFFFFFFFu; }
             }
             uint32_t i = 0u;
             auto put = [&](uint32_t j) {
@@ -973,6 +978,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
                 const unsigned long long ms = __ballot(f && !big), mb = __ballot(f && big);
                 if (f && !big) {
                     const uint32_t pos = my_pairs + (uint32_t)__popcll(ms & lt);
+                    // (cannot fail: <= per_wave / 4 entries x chunk_bus pairs <= K; equal when each entry rides its own route every bus step)
                     if (pos < K) list[pos] = (rt << 7) | j; else ctrl->error = (uint32_t)(-ESIM_ERANGE);
                 }
                 if (f && big && big_base != 0xFFFFFFFFu) d.route_pairs_big[big_base + (uint32_t)__popcll(mb & lt)] = (rt << 7) | j;
@@ -1711,7 +1717,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_units(Dev d)
     // queue `wave & 63`, every (n_waves / 64)-th unit of it
     const uint32_t qr = wave & (SUBQ - 1u), first = wave / SUBQ, step = n_waves / SUBQ;
     const uint32_t n_units = step ? min(ld(&d.hot[(HOT_UNITS + qr) * HOT_STRIDE]), d.unit_qcap) : 0u;
-    const uint32_t n_pairs = min(ld(&d.hot[HOT_BIGPAIRS * HOT_STRIDE]), 2u * d.items_cap);
+    const uint32_t n_pairs = min(ld(&d.hot[HOT_BIGPAIRS * HOT_STRIDE]), d.big_pairs_cap);
     if (__syncthreads_or(first < n_units) == 0 && n_pairs == 0u) return;
     for (uint32_t i = threadIdx.x; i < n; i += TPB) sm.dec[i] = d.dec[i];
     for (uint32_t i = threadIdx.x; i < 512u; i += TPB) sm.thr[i] = d.thr[i];

@@ -15,7 +15,9 @@
 #define TINY_E 64u                 // Infected (log entries) of a chunk the one-workgroup form takes
 #define TINY_WAVES (FIN_TPB / 64u)
 #define TINY_INLINE 256u           // member lists of more (member, slot) pairs than this are cut into units of that many, which all wavefronts share
-#define TINY_TASKS 512u
+#define TINY_TASKS 512u           // (a full queue costs nothing but speed: the wavefront that finds it full draws the rest itself)
+#define TINY_BUS 8u                // bus steps of a chunk the form takes (k_chunk_tiny's guard on Ctrl::chunk_bus)
+#define TINY_BIG 512u              // (route of more than 64 riders, bus step) pairs of a chunk: at most one route per entry, one pair per bus step
 #define TINY_NONE 0xFFFFFFFFu
 // What one wavefront of the workgroup wrote to memory, the others read after this: the writes have reached the L2 (the workgroup's
 // waves share one CU and one L2: no write-back is needed), the readers drop what their L1 holds of it (a citizen word cached before
@@ -28,8 +30,9 @@ struct TinyShared {
     uint32_t uniq[4u * TINY_E];                           // the distinct keys
     uint32_t n_uniq, n_tasks, n_big;
     uint32_t task[TINY_TASKS][3];                         // units of long member lists: key, kind, first pair
-    uint32_t big[64];                             // (route of more than 64 riders, bus step) pairs: route << 7 | step
+    uint32_t big[TINY_BIG];                               // (route of more than 64 riders, bus step) pairs: route << 7 | step
 };
+static_assert(TINY_BIG >= TINY_E * TINY_BUS, "k_chunk_tiny: every entry's route on every bus step the guard admits must fit big[]");
 
 // Infected per step of the chunk in the item `key` (role 0: those who live there, 1: who work there, 2: the room; lanes = steps).
 __device__ __forceinline__ void tiny_counts(const TinyShared &ts, uint32_t E, uint32_t key, uint32_t lane, const M96 &AW, const M96 &BUS,
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
     const uint32_t E = i1 - i0;
     bool run = ld(&ctrl->chunk_parallel) != 0u && n != 0u;
     const unsigned long long key_space = (unsigned long long)d.n_bld + d.n_room + d.n_routes;
-    if (run && (i1 < i0 || E > TINY_E || ld(&ctrl->vax_chunk) != 0u || ld(&ctrl->have_elig) != 0u || d.world > 1u || ld(&ctrl->chunk_bus) > 8u || key_space >= 0xFFFFFFFFull || n > FREE_MAX)) {
+    if (run && (i1 < i0 || E > TINY_E || ld(&ctrl->vax_chunk) != 0u || ld(&ctrl->have_elig) != 0u || d.world > 1u || ld(&ctrl->chunk_bus) > TINY_BUS || key_space >= 0xFFFFFFFFull || n > FREE_MAX)) {
         // not a chunk for this form: nobody advances (books_body: "the chunk does not run"), the host enqueues the wide form
         __syncthreads();
         if (tid == 0) ctrl->chunk_parallel = 0u;
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
                     for (unsigned long long m = half ? (unsigned long long)ride.hi : ride.lo; m; m &= m - 1ull) {
                         const uint32_t j = 64u * half + (uint32_t)__builtin_ctzll(m);
                         if (sz <= 64u) route_pair_small(d, ctrl, sm, off, sz, j, t0, lane WORK_PASS);
-                        else if (lane == 0) { const uint32_t at = atomicAdd(&ts.n_big, 1u); if (at < 64u) ts.big[at] = (r << 7) | j; else RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIGPAIRS); }
+                        else if (lane == 0) { const uint32_t at = atomicAdd(&ts.n_big, 1u); if (at < TINY_BIG) ts.big[at] = (r << 7) | j; else RAISE(ctrl, ESIM_ERANGE, ERR_AT_BIGPAIRS); }
                     }
                 continue;
             }
@@ -263,7 +266,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
         __syncthreads();                                                      // (the wavefronts' scratch becomes the routes' LDS)
         TINY_PROF(d, 7);
         // (5) routes of more than 64 riders: the whole workgroup per (route, bus step)
-        const uint32_t n_big = min(ts.n_big, 64u);
+        const uint32_t n_big = min(ts.n_big, TINY_BIG);
         for (uint32_t q = 0; q < n_big; ++q) route_pair_big<FIN_TPB>(d, ctrl, sm, rs, ts.big[q], t0, n WORK_PASS);
         WORK_FLUSH(d);
         TINY_SYNC();

@@ -346,6 +346,12 @@ class Simulator:
         _lib.check(self.lib.esim_chunk_timing(self._ctx, C.byref(ms), C.byref(ns), C.byref(nc)), self._ctx)
         return {"chunk_ms": ms.value, "steps": ns.value, "chunks": nc.value}
 
+    def debug_counters(self):
+        """The control block's view of the last chunk (esim_debug_counters), by name."""
+        out = (C.c_uint32 * 16)()
+        _lib.check(self.lib.esim_debug_counters(self._ctx, out), self._ctx)
+        return dict(zip(_lib.DEBUG_COUNTERS, (int(x) for x in out)))
+
     def vax_chunk_stats(self):
         """Steps run as chunks under a vaccination programme and how many of those chunks were cut short."""
         ns, nc = C.c_uint64(0), C.c_uint64(0)

@@ -302,7 +302,8 @@ int  esim_set_tiny_chunk_limit(esim_ctx *ctx, uint32_t max_pairs);
 int  esim_pipeline_timing(esim_ctx *ctx, double *mean_step_ms, uint64_t *steps_timed, uint64_t *steps_run);
 
 /* Diagnostics: the control block's view of the last chunk (t, chunk_ok, chunk_parallel, chunk_pairs, n_items,
- * items_per_wave, n_units, 0 (was n_route_pairs), n_route_pairs_big, n_newexp, log_len, n_susceptible, lockdown, mask,
+ * items_per_wave, n_units, chunk_bus (steps of the chunk with riders on a bus), n_route_pairs_big (of the last chunk
+ * whose books ran; 0 after one of the one-workgroup form, which does not count them), n_newexp, log_len, n_susceptible, lockdown, mask,
  * at_work, bus_dir). */
 int  esim_debug_counters(esim_ctx *ctx, uint32_t out[16]);
 

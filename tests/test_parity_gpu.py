@@ -43,9 +43,7 @@ def run_both(pop, steps, check_state_every=None, small_limits=SMALL_LIMITS, **pa
             raise AssertionError("execution form %r: %s" % (lim, e)) from e
 
 
-def _run_both(pop, steps, check_state_every, small_limit, **params):
-    ep = _lib.default_params(**params)
-    sim = Simulator(pop, ep)
+def set_form(sim, small_limit):
     if small_limit == "vax":
         sim.set_pipeline(3)                       # time-parallel chunks, also under a vaccination programme (default)
     elif small_limit == "wide":
@@ -60,6 +58,12 @@ def _run_both(pop, steps, check_state_every, small_limit, **params):
         sim.set_pipeline(0)                       # sequential steps
         if small_limit is not None:
             sim.set_small_step_limit(small_limit)
+
+
+def _run_both(pop, steps, check_state_every, small_limit, **params):
+    ep = _lib.default_params(**params)
+    sim = Simulator(pop, ep)
+    set_form(sim, small_limit)
     orc = _oracle.Oracle(pop, _oracle.params_from_esim(ep))
     if check_state_every:
         done = 0
@@ -73,6 +77,50 @@ def _run_both(pop, steps, check_state_every, small_limit, **params):
         assert_same_state(sim, orc)
     sim.close()
     return orc
+
+
+class OracleRun:
+    """One oracle run kept for several forms: its records and its state at the end of every block of `block` steps
+    (run_forms).  stop_when_done: the run ends where the reference's loop would, in the block in which it ends."""
+
+    def __init__(self, pop, steps, block, stop_when_done=False, threads=16, **params):
+        self.pop, self.params, self.block, self.stop = pop, params, block, stop_when_done
+        orc = _oracle.Oracle(pop, _oracle.params_from_esim(_lib.default_params(**params)))
+        orc.set_threads(threads)
+        self.asked, self.records, self.states, done = [], [], [], 0
+        while done < steps:
+            n = min(block, steps - done)
+            r = orc.run(n, stop_when_done=stop_when_done)
+            self.asked.append(n); self.records.append(r); self.states.append(orc.state())
+            done += len(r)
+            if len(r) < n:
+                break
+        self.steps = done
+        orc.close()
+
+
+def run_forms(run, forms, observe=None):
+    """Every form in `forms` against the one oracle run `run`: records block by block, the full state at every block's end.
+    observe(form, sim, block_index) is called after each block (the capacity tests read the chunk counters there), and with
+    block_index -1 before the first."""
+    for lim in forms:
+        sim = Simulator(run.pop, _lib.default_params(**run.params))
+        set_form(sim, lim)
+        if observe:
+            observe(lim, sim, -1)
+        try:
+            for i, (n, want, st) in enumerate(zip(run.asked, run.records, run.states)):
+                got = sim.run(n, stop_when_done=run.stop)
+                assert_same_records(got, want)
+                g = sim.download_state()
+                for k in ("status", "timer", "current_building", "on_bus", "eligible"):
+                    assert (g[k] == st[k]).all(), "%s after block %d" % (k, i)
+                if observe:
+                    observe(lim, sim, i)
+        except AssertionError as e:
+            raise AssertionError("execution form %r: %s" % (lim, e)) from e
+        finally:
+            sim.close()
 
 
 AGGRESSIVE = dict(exposure_chance=0.004, vaccination_rate=40, vaccination_threshold=0.02,
@@ -125,7 +173,7 @@ def test_york_full_5000_steps_vaccination_85():
 def test_yh_census_config_1500_steps():
     # BASELINE.json configs[2]: Yorkshire & Humber (5 249 772 citizens, 17 246 Output Areas) on one GPU;
     # 1500 of the 5000 steps keeps the oracle within ~20 s
-    run_both(Population.synthetic("yh_census"), 1500, small_limits=("tp", "pipe"))
+    run_both(Population.synthetic("yh_census"), 1500, small_limits=("vax", "tp", "pipe"))
 
 
 def test_big_routes_and_u8_truncation():
@@ -176,6 +224,63 @@ def test_stop_when_done_matches_reference_loop():
     g, o = sim.run(600, stop_when_done=True), orc.run(600, stop_when_done=True)
     assert len(g) == len(o) == 337 and g["disease_exists"][-1] == 0
     assert_same_records(g, o)
+    sim.close()
+
+
+def _all_infected_at_start(n=64):
+    # everyone Infected at step 1, no susceptibles: the disease is gone after step 337 (test_stop_when_done_matches_reference_loop)
+    home = np.arange(n, dtype=np.uint32) // 4
+    return Population(home_building=home, work_building=home.copy(), flags=np.zeros(n, np.uint8),
+                      building_area=np.zeros(n // 4, np.uint32), building_type=np.zeros(n // 4, np.uint8),
+                      seeds=np.arange(n, dtype=np.uint32), n_areas=1)
+
+
+def test_resumed_checkpoint_keeps_running_when_asked_to(tmp_path):
+    # saved after run(stop_when_done=True), before extinction: the control block in the file carries the flag.  A run of the
+    # restored context with stop_when_done=False must go past extinction and return every step it was asked for (the host's
+    # copy of the flag was 0 after the reset, so the saved 1 stayed on the device and the run stopped at step 337).
+    pop = _all_infected_at_start()
+    ep = _lib.default_params(vaccination_threshold=2.0)
+    want = _oracle.Oracle(pop, _oracle.params_from_esim(ep)).run(700)
+    a = Simulator(pop, ep)
+    first = a.run(100, stop_when_done=True)
+    assert len(first) == 100
+    a.save_checkpoint(str(tmp_path / "c.bin"))
+    a.close()
+    b = Simulator(pop, ep)
+    b.load_checkpoint(str(tmp_path / "c.bin"))
+    rest = b.run(600, stop_when_done=False)
+    assert len(rest) == 600
+    assert_same_records(np.concatenate([first, rest]), want)
+    # ... and stops where the reference's loop does when asked to
+    c = Simulator(pop, ep)
+    c.load_checkpoint(str(tmp_path / "c.bin"))
+    assert len(c.run(600, stop_when_done=True)) == 337 - 100
+    b.close(); c.close()
+
+
+def test_stop_flag_after_a_sharded_run_of_one_rank():
+    # esim_run(stop) -> esim_run_sharded (which clears the device's flag) -> esim_run(stop) on one context with a communicator of
+    # one rank: the last call must write the flag again and stop at extinction like the oracle (it skipped the write, its host
+    # copy still saying 1, and ran on)
+    import ctypes as C
+    pop = _all_infected_at_start()
+    ep = _lib.default_params(vaccination_threshold=2.0)
+    want = _oracle.Oracle(pop, _oracle.params_from_esim(ep)).run(700, stop_when_done=True)
+    assert len(want) == 337
+    sim = Simulator(pop, ep)
+    uid = (C.c_uint8 * 128)()
+    _lib.check(sim.lib.esim_comm_unique_id(uid, 128))
+    _lib.check(sim.lib.esim_comm_init_rccl(sim._ctx, uid, 128, 0, 1), sim._ctx)
+    first = sim.run(10, stop_when_done=True)
+    n_done = C.c_uint32(0)
+    _lib.check(sim.lib.esim_run_sharded(sim._ctx, 10, C.byref(n_done)), sim._ctx)
+    assert n_done.value == 10
+    sim._steps += 10
+    mid = sim.records_so_far()[10:20]
+    rest = sim.run(680, stop_when_done=True)
+    assert len(rest) == 337 - 20
+    assert_same_records(np.concatenate([first, mid, rest]), want)
     sim.close()
 
 

@@ -2,7 +2,7 @@
 import ctypes as C, sys, time
 sys.path.insert(0, '.')
 from epidemicsimulator_amd import Population, Simulator, _lib
-names = ["t", "chunk_ok", "chunk_parallel", "chunk_pairs", "n_items", "items_per_wave", "n_units", "(unused)",
+names = ["t", "chunk_ok", "chunk_parallel", "chunk_pairs", "n_items", "items_per_wave", "n_units", "chunk_bus",
          "n_route_pairs_big", "n_newexp", "log_len", "n_susceptible", "lockdown", "mask", "at_work", "bus_dir"]
 pop = Population.synthetic(sys.argv[1] if len(sys.argv) > 1 else "uk64m")
 sim = Simulator(pop, _lib.default_params(max_steps=5000))
