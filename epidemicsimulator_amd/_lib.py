@@ -87,11 +87,9 @@ class SynthSpec(C.Structure):
 # every symbol include/esim.h declares (tests/test_abi.py checks the library exports them all)
 SYMBOLS = [
     "esim_default_params", "esim_create", "esim_upload_population", "esim_reset", "esim_step",
-    "esim_run", "esim_step_begin", "esim_step_exposures", "esim_step_finish",
-    "esim_exchange_buffer", "esim_future_infected", "esim_run_free", "esim_free_begin", "esim_free_enqueue", "esim_free_collect", "esim_set_pipeline", "esim_chunk_timing", "esim_enable_chunk_kernel_timing", "esim_chunk_kernel_timings", "esim_vax_chunk_stats", "esim_vax_repair_stats", "esim_pipeline_timing",
+    "esim_run", "esim_set_pipeline", "esim_chunk_timing", "esim_enable_chunk_kernel_timing", "esim_chunk_kernel_timings", "esim_vax_chunk_stats", "esim_vax_repair_stats", "esim_pipeline_timing",
     "esim_comm_unique_id", "esim_comm_init_rccl", "esim_comm_init_callback", "esim_comm_set_timeout", "esim_debug_inject_error", "esim_comm_stats", "esim_run_sharded", "esim_shard_stats",
-    "esim_read_records", "esim_stream", "esim_set_stream",
-    "esim_set_exchange_buffer", "esim_synchronize",
+    "esim_read_records", "esim_synchronize",
     "esim_download_state", "esim_download_exposure_log", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_enable_phase_timing", "esim_phase_timings",
     "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters",
     "esim_last_error", "esim_destroy",
@@ -123,10 +121,6 @@ def load():
         "esim_reset": (C.c_int, [vp]),
         "esim_step": (C.c_int, [vp, C.POINTER(StepResult)]),
         "esim_run": (C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(StepResult), C.POINTER(C.c_uint32)]),
-        "esim_step_begin": (C.c_int, [vp]),
-        "esim_step_exposures": (C.c_int, [vp]),
-        "esim_step_finish": (C.c_int, [vp, C.POINTER(StepResult)]),
-        "esim_exchange_buffer": (C.c_int, [vp, C.c_int, pvp, C.POINTER(C.c_size_t)]),
         "esim_comm_unique_id": (C.c_int, [vp, C.c_size_t]),
         "esim_comm_init_rccl": (C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int]),
         "esim_comm_init_callback": (C.c_int, [vp, ALLREDUCE_FN, vp, C.c_int, C.c_int]),
@@ -135,11 +129,6 @@ def load():
         "esim_comm_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "esim_run_sharded": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "esim_shard_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-        "esim_future_infected": (C.c_int, [vp]),
-        "esim_run_free": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint32)]),
-        "esim_free_begin": (C.c_int, [vp, C.c_uint32]),
-        "esim_free_enqueue": (C.c_int, [vp]),
-        "esim_free_collect": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "esim_set_pipeline": (C.c_int, [vp, C.c_int]),
         "esim_chunk_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "esim_enable_chunk_kernel_timing": (C.c_int, [vp, C.c_int]),
@@ -148,9 +137,6 @@ def load():
         "esim_vax_repair_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "esim_pipeline_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "esim_read_records": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(StepResult)]),
-        "esim_stream": (C.c_int, [vp, pvp]),
-        "esim_set_stream": (C.c_int, [vp, vp]),
-        "esim_set_exchange_buffer": (C.c_int, [vp, C.c_int, vp]),
         "esim_synchronize": (C.c_int, [vp]),
         "esim_download_state": (C.c_int, [vp, _u8p, _u16p, _u32p, _u8p, _u8p]),
         "esim_download_exposure_log": (C.c_int, [vp, _u32p, _u32p, _u8p, C.c_uint32, _u32p]),

@@ -25,7 +25,6 @@ struct esim_ctx_impl {
     Dev d;
     bool uploaded = false;
     hipStream_t stream = nullptr;
-    bool own_stream = true;
     std::string err;
     // host copies needed for reset
     std::vector<uint32_t> init_state;
@@ -35,7 +34,6 @@ struct esim_ctx_impl {
     uint32_t n_routes = 0;
     size_t xa_n = 0, xb_n = 0, xf_n = 0;
     uint32_t last_chunk_pairs = 0;               // Infected during the chunk last looked at (picks the form of the chunk's book-keeping)
-    uint32_t free_limit = 0, free_first = 0;     // open burst of decoupled chunks: last step it may reach, first step
     uint32_t host_t = 1;          // next time step to enqueue
     uint64_t pop_hash = 0;        // of the uploaded population arrays: a checkpoint only goes back into the population it came from
     // device allocations
@@ -43,7 +41,6 @@ struct esim_ctx_impl {
     // timing
     bool phase_timing = false, kernel_timing = false;
     uint32_t kernel_timing_stride = 16;
-    bool timing_this_step = false;
     hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     double phase_s[3] = { 0, 0, 0 };
     std::vector<hipEvent_t> kev;       // two per timed step: before k_infected, after k_finish
@@ -72,8 +69,6 @@ struct esim_ctx_impl {
     uint32_t *xr = nullptr; size_t xr_n = 0;      // records exchange (sharded chunks)
     uint64_t shard_chunk_steps = 0, shard_step_steps = 0;
     uint64_t comm_calls = 0;
-    bool xs_a2a = true;                 // the commuter exchange as an all-to-all of owner-addressed segments (ESIM_XS_MODE=gather: all-gather)
-    uint32_t *xs_out = nullptr, *shared_mask = nullptr;
     // pinned host mirrors: the control block and the records of the call in flight come back with ONE stream wait (two blocking
     // copies into pageable memory cost more than a small chunk's kernels)
     Ctrl *pin_ctrl = nullptr;
@@ -89,7 +84,6 @@ struct esim_ctx_impl {
     std::vector<hipEvent_t> kdev; std::vector<int> kd_kind; size_t kd_used = 0;
     double kd_ms[ESIM_CK_N] = { 0 }; uint64_t kd_calls[ESIM_CK_N] = { 0 };
     double comm_timeout_s = 60.0;      // deadline of a host wait on a stream that holds collectives (esim_comm_set_timeout)
-    std::vector<hipEvent_t> fev; size_t fev_used = 0;                               // chunks of an open decoupled burst
     std::vector<hipEvent_t> pkev; size_t pkev_used = 0; uint64_t pipe_steps = 0;   // sampled k_pipe launches
     uint32_t small_max = 128;          // infected-slice length up to which the persistent single-workgroup kernel runs a step
     hipEvent_t sev[2] = { nullptr, nullptr };   // k_small timing
@@ -140,12 +134,13 @@ void free_device(esim_ctx_impl *c)
     c->uploaded = false;
 }
 
-// one allocation back (buffers that are re-sized: the commuter segments, the records exchange)
+// one allocation back (buffers that are re-sized: the commuter segments, the records exchange); every device pointer of a
+// context is one of its own allocations: any other pointer is left alone
 void dev_free(esim_ctx_impl *c, void *p)
 {
-    if (!p) return;
     auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
-    if (it != c->allocs.end()) c->allocs.erase(it);
+    if (it == c->allocs.end()) return;
+    c->allocs.erase(it);
     (void)hipFree(p);
 }
 
@@ -240,12 +235,11 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     for (auto &ev : c->kev) (void)hipEventDestroy(ev);
     for (auto &ev : c->sev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->pkev) (void)hipEventDestroy(ev);
-    for (auto &ev : c->fev) (void)hipEventDestroy(ev);
     for (auto &ev : c->cev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : c->kdev) (void)hipEventDestroy(ev);
     if (c->pin_ctrl) (void)hipHostFree(c->pin_ctrl);
     if (c->pin_rec) (void)hipHostFree(c->pin_rec);
-    if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -633,7 +627,6 @@ extern "C" int esim_reset(esim_ctx *ctx)
     c->host_t = 1;
     c->stop_flag_dev = 0;
     c->pin_track = false;
-    c->free_limit = 0;
     c->last_chunk_pairs = (uint32_t)c->init_log.size();
     c->phase_s[0] = c->phase_s[1] = c->phase_s[2] = 0;
     c->kev_used = 0;
@@ -708,11 +701,6 @@ bool want_kernel_timing(esim_ctx_impl *c)
     return true;
 }
 
-int fail_dev(esim_ctx_impl *c, uint32_t err)
-{
-    return fail(c, -(int)err, "device-side error (S underflow / vaccination window exhausted / a chunk table overflowed)");
-}
-
 static inline void ht_mark(esim_ctx_impl *c, const char *what)
 {
     if (!c->host_trace) return;
@@ -720,13 +708,25 @@ static inline void ht_mark(esim_ctx_impl *c, const char *what)
     c->ht.emplace_back(what, ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3);
 }
 
-// The control block through the pinned mirror: an asynchronous copy and one wait.
+// The control block through the pinned mirror: an asynchronous copy and one wait.  Every read-back of it goes through the
+// mirror (burst_readback and sync_status fill it alongside other work), so that no copy is ever aimed at memory the call
+// does not own.
 int read_ctrl(esim_ctx_impl *c, Ctrl *h)
 {
     HIP_TRY(c, hipMemcpyAsync(c->pin_ctrl, c->d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *h = *c->pin_ctrl;
     return ESIM_OK;
+}
+
+// The sticky device-side error of a control block read back, as the call's return code.  A sharded run returns the lowest code
+// any shard raised (Ctrl::peer_error, summed by k_status_unpack), the same on every rank.
+int ctrl_error(esim_ctx_impl *c, const Ctrl &h)
+{
+    if (!h.error) return ESIM_OK;
+    const int code = -(int)(h.peer_error ? err_decode(h.peer_error) : h.error);
+    return fail(c, code, "device-side error " + std::to_string(code) + " (S underflow / vaccination window exhausted / a chunk table check; raised at check " +
+                         std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
 }
 
 void kd_resolve(esim_ctx_impl *c);
@@ -750,53 +750,13 @@ int burst_readback(esim_ctx_impl *c, uint32_t first, uint32_t span, Ctrl *h)
     return ESIM_OK;
 }
 
+// The control block's error state as it stands.
 int device_error(esim_ctx_impl *c)
 {
     Ctrl h;
-    HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
-    if (h.error) return fail(c, -(int)h.error, "device-side error (S underflow / vaccination window exhausted / a chunk table check: " + std::to_string(h.err_where) + ")");
-    return ESIM_OK;
+    const int rc = read_ctrl(c, &h);
+    return rc ? rc : ctrl_error(c, h);
 }
-
-}  // namespace
-
-extern "C" int esim_step_begin(esim_ctx *ctx)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    int rc = check_budget(c, 1);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    c->timing_this_step = want_kernel_timing(c);
-    return enqueue_begin(c, c->timing_this_step);
-}
-
-extern "C" int esim_step_exposures(esim_ctx *ctx)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    return enqueue_exposures(c, c->timing_this_step);
-}
-
-extern "C" int esim_step_finish(esim_ctx *ctx, esim_step_result *out)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    int rc = enqueue_finish(c, c->timing_this_step);
-    c->timing_this_step = false;
-    if (rc) return rc;
-    if (out) {
-        HIP_TRY(c, hipMemcpyAsync(out, &c->d.records[c->host_t - 1], sizeof *out, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return device_error(c);
-    }
-    return ESIM_OK;
-}
-
-extern "C" int esim_step(esim_ctx *ctx, esim_step_result *out);
-
-namespace {
 
 // Sequential steps (three kernels per step, or the persistent single-workgroup kernel while few citizens
 // are Infected): the only form that can vaccinate.
@@ -813,11 +773,10 @@ int run_sequential(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, ui
             hipLaunchKernelGGL(k_small, dim3(1), dim3(FIN_TPB), 0, c->stream, d, remaining, c->small_max, 0);
             if (c->kernel_timing) HIP_TRY(c, hipEventRecord(c->sev[1], c->stream));
             Ctrl h;
-            HIP_TRY(c, hipMemcpyAsync(&h, d.ctrl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if ((rc = read_ctrl(c, &h))) return rc;
             if (c->kernel_timing && h.small_done) { float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->sev[0], c->sev[1])); c->small_ms += ms; c->small_steps += h.small_done; }
             c->host_t += h.small_done; total += h.small_done; remaining -= h.small_done;
-            if (h.error) return fail(c, -(int)h.error, "device-side error (S underflow / vaccination window exhausted / a chunk table check: " + std::to_string(h.err_where) + ")");
+            if ((rc = ctrl_error(c, h))) return rc;
             if (h.finished && allow_early_stop) break;
         }
         if (remaining == 0) break;
@@ -856,10 +815,9 @@ void kd_resolve(esim_ctx_impl *c)
 
 // The kernels of one time-parallel chunk; they take the chunk (first step, length, whether it may run this way)
 // from the control block as k_decide left it, and do nothing when it may not.
-// then_next: also prepare the chunk after it (census ahead + decisions: what k_future and k_decide do), for steps up to limit_t.
-// While few citizens are Infected the books, the log scatter, the clean-up and that preparation are ONE single-workgroup
-// kernel (a kernel boundary costs more than these steps); with many, the scatter and clean-up need the whole chip.
-// then_next: 0 nothing, 1 census ahead + decisions of the next chunk, 2 census ahead only.
+// then_next (0 / 1): also prepare the chunk after it (census ahead + decisions: what k_future and k_decide do), for steps up
+// to limit_t.  While few citizens are Infected the books, the log scatter, the clean-up and that preparation are ONE
+// single-workgroup kernel (a kernel boundary costs more than these steps); with many, the scatter and clean-up need the whole chip.
 // marks -> fold -> draw -> units of one chunk: the item map is built by k_chunk_marks and torn down by k_chunk_scatter.
 // A chunk with few Infected is nothing but the latency of its kernels: those run on 64 workgroups instead of 1024 then (measured
 // on york, whose chunks are all of that kind: 3.56 instead of 4.0 ms for the 5000 steps).  The choice follows what the last
@@ -938,19 +896,19 @@ void enqueue_vax_chunk(esim_ctx_impl *c, uint32_t limit_t)
     kd_mark(c, ESIM_CK_N);
 }
 
-// One pipelined chunk.  Precondition: k_future ran for the current step (and, when sharded, buffer F was
-// all-reduced).  k_decide finds how many of the next n_ahead steps can run before a vaccination programme
-// would start; those run as one k_pipe each and k_batch_finish writes their books.  *executed = steps run.
+// One pipelined chunk.  Precondition: k_future ran for the current step.  k_decide finds how many of the next n_ahead
+// steps can run before a vaccination programme would start; those run as one k_pipe each and k_batch_finish writes their
+// books.  *executed = steps run.
 int run_chunk(esim_ctx_impl *c, uint32_t n_ahead, uint32_t *executed, Ctrl *state_before)
 {
     Dev &d = c->d;
     c->ctrl_fresh = false;
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, n_ahead, c->P.max_steps, c->time_parallel ? 1 : 0, 0);
     Ctrl h;
-    HIP_TRY(c, hipMemcpyAsync(&h, d.ctrl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (state_before) *state_before = h;
-    if (h.error) return fail(c, -(int)h.error, "device-side error (raised at check " + std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
+    int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;
+    *state_before = h;
+    if ((rc = ctrl_error(c, h))) return rc;
     const uint32_t n = h.chunk_ok, t0 = h.t;
     c->last_chunk_pairs = h.chunk_pairs;
     *executed = 0;
@@ -964,9 +922,8 @@ int run_chunk(esim_ctx_impl *c, uint32_t n_ahead, uint32_t *executed, Ctrl *stat
         HIP_TRY(c, hipGetLastError());
         // (what was executed is read, not assumed)
         Ctrl after;
-        int rc2 = read_ctrl(c, &after);
-        if (rc2) return rc2;
-        if (after.error) return fail(c, -(int)after.error, "device-side error (raised at check " + std::to_string(after.err_where) + ")");
+        if ((rc = read_ctrl(c, &after))) return rc;
+        if ((rc = ctrl_error(c, after))) return rc;
         const uint32_t ran = after.t - t0;
         c->chunk_steps += ran; c->chunk_count += ran ? 1u : 0u;
         *executed = ran;
@@ -1023,7 +980,7 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             Ctrl h;
             if ((rc = burst_readback(c, first, std::min<uint32_t>(remaining, bursts * (uint32_t)c->xf_n), &h))) return rc;
             HIP_TRY(c, hipGetLastError());
-            if (h.error) return fail(c, -(int)h.error, "device-side error (raised at check " + std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
+            if ((rc = ctrl_error(c, h))) return rc;
             const uint32_t done = h.t - first;
             c->last_chunk_pairs = h.chunk_pairs;
             if (tk && done) { float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1])); c->chunk_ms += ms; c->chunk_steps += done; c->chunk_count += (done + (uint32_t)c->xf_n - 1u) / (uint32_t)c->xf_n; }
@@ -1072,7 +1029,7 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             Ctrl h;
             if ((rc = burst_readback(c, first, std::min<uint32_t>(remaining, bursts * (uint32_t)c->xf_n), &h))) return rc;
             HIP_TRY(c, hipGetLastError());
-            if (h.error) return fail(c, -(int)h.error, "device-side error (raised at check " + std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
+            if ((rc = ctrl_error(c, h))) return rc;
             const uint32_t done = h.t - first;
             c->last_chunk_pairs = h.chunk_pairs;
             if (tk && done) { float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1])); c->chunk_ms += ms; c->chunk_steps += done; c->chunk_count += (done + (uint32_t)c->xf_n - 1u) / (uint32_t)c->xf_n; }
@@ -1104,8 +1061,7 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
             total += one; remaining -= one;
             if (one == 0) break;
             Ctrl h;
-            HIP_TRY(c, hipMemcpyAsync(&h, d.ctrl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if ((rc = read_ctrl(c, &h))) return rc;
             if (h.have_elig) {                                            // that step started the programme
                 c->elig_seen = true;
                 if (vax_ok && remaining >= 8u) vax_regime = true; else sequential_only = true;
@@ -1114,8 +1070,7 @@ int run_steps(esim_ctx_impl *c, uint32_t n_steps, bool allow_early_stop, uint32_
         if (allow_early_stop && done > 0) {
             // a chunk may have ended the run (disease gone): k_batch_finish set `finished`
             Ctrl h;
-            HIP_TRY(c, hipMemcpyAsync(&h, d.ctrl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if ((rc = read_ctrl(c, &h))) return rc;
             if (h.finished) { c->host_t = h.t; break; }
         }
     }
@@ -1130,7 +1085,7 @@ extern "C" int esim_step(esim_ctx *ctx, esim_step_result *out)
     esim_ctx_impl *c = CTX(ctx);
     int rc = check_budget(c, 1);
     if (rc) return rc;
-    if (c->d.n_shards > 1) return fail(c, ESIM_ESTATE, "esim_step: a sharded population needs the split-phase calls and an all-reduce");
+    if (c->d.n_shards > 1) return fail(c, ESIM_ESTATE, "esim_step: a sharded population runs with esim_run_sharded");
     HIP_TRY(c, hipSetDevice(c->P.device));
     if ((rc = run_steps(c, 1, false, nullptr))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1144,7 +1099,7 @@ extern "C" int esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done, esi
     if (c && c->host_trace) { c->ht.clear(); ht_mark(c, "enter"); }
     int rc = check_budget(c, n_steps);
     if (rc) return rc;
-    if (c->d.n_shards > 1) return fail(c, ESIM_ESTATE, "esim_run: a sharded population needs the split-phase calls and an all-reduce");
+    if (c->d.n_shards > 1) return fail(c, ESIM_ESTATE, "esim_run: a sharded population runs with esim_run_sharded");
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint32_t first = c->host_t;
     const uint32_t flag = stop_when_done ? 1u : 0u;
@@ -1162,7 +1117,7 @@ extern "C" int esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done, esi
     Ctrl h;
     if (c->ctrl_fresh) h = *c->pin_ctrl;
     else if ((rc = read_ctrl(c, &h))) return rc;
-    if (h.error) return fail(c, -(int)h.error, "device-side error (S underflow / vaccination window exhausted / a chunk table check: " + std::to_string(h.err_where) + ")");
+    if ((rc = ctrl_error(c, h))) return rc;
     const uint32_t done = h.steps_done >= first ? h.steps_done - first + 1 : 0;
     if (std::getenv("ESIM_DEBUG"))
         std::fprintf(stderr, "[esim] esim_run(%u steps from %u): done %u, t=%u steps_done=%u finished=%u chunk_ok=%u parallel=%u, records mirrored %u, control block %s\n",
@@ -1203,7 +1158,6 @@ struct RcclApi {
     ncclResult_t (*GroupStart)() = nullptr;
     ncclResult_t (*GroupEnd)() = nullptr;
     ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
     const char *(*GetErrorString)(ncclResult_t) = nullptr;
     bool ok = false;
 };
@@ -1228,9 +1182,8 @@ RcclApi &rccl()
     api.GroupStart = (decltype(api.GroupStart))dlsym(h, "ncclGroupStart");
     api.GroupEnd = (decltype(api.GroupEnd))dlsym(h, "ncclGroupEnd");
     api.AllReduce = (decltype(api.AllReduce))dlsym(h, "ncclAllReduce");
-    api.AllGather = (decltype(api.AllGather))dlsym(h, "ncclAllGather");
     api.GetErrorString = (decltype(api.GetErrorString))dlsym(h, "ncclGetErrorString");
-    api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.CommAbort && api.AllReduce && api.AllGather && api.Send && api.Recv &&
+    api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.CommAbort && api.AllReduce && api.Send && api.Recv &&
              api.GroupStart && api.GroupEnd && api.GetErrorString;
     return api;
 }
@@ -1262,19 +1215,6 @@ int exchange_buf(esim_ctx_impl *c, int which, uint32_t *buf, size_t n)
         return ESIM_OK;
     }
     return fail(c, ESIM_ESTATE, "sharded run without a communicator (esim_comm_init_rccl / esim_comm_init_callback)");
-}
-
-// All-gather: every rank contributes the `per_rank` words at buf + rank * per_rank and receives everybody's.  Over a caller's
-// transport: a SUM all-reduce of the whole buffer, the other ranks' segments zeroed first (k_zero_segments).
-int exchange_gather(esim_ctx_impl *c, int which, uint32_t *buf, size_t per_rank)
-{
-    if (c->nccl) {
-        c->comm_calls++;
-        ncclResult_t r = rccl().AllGather(buf + (size_t)c->comm_rank * per_rank, buf, per_rank, ncclUint32, c->nccl, c->stream);
-        if (r != ncclSuccess) return fail(c, ESIM_ENODEVICE, std::string("ncclAllGather: ") + rccl().GetErrorString(r));
-        return ESIM_OK;
-    }
-    return exchange_buf(c, which, buf, per_rank * (size_t)c->comm_world);
 }
 
 int wait_stream(esim_ctx_impl *c);
@@ -1325,11 +1265,8 @@ int comm_buffers(esim_ctx_impl *c)
     Dev &d = c->d;
     int rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (d.xs) { dev_free(c, d.xs); d.xs = nullptr; }
-    if (c->xs_out) { dev_free(c, c->xs_out); c->xs_out = nullptr; }
-    if (c->shared_mask) { dev_free(c, c->shared_mask); c->shared_mask = nullptr; }
-    d.xs_out = nullptr; d.shared_mask = nullptr;
-    if (const char *e = std::getenv("ESIM_XS_MODE")) c->xs_a2a = std::string(e) != "gather";
+    dev_free(c, d.xs); dev_free(c, d.xs_out); dev_free(c, (void *)d.shared_mask);
+    d.xs = nullptr; d.xs_out = nullptr; d.shared_mask = nullptr;
     if (c->xr) { dev_free(c, c->xr); c->xr = nullptr; c->xr_n = 0; }
     d.rank = (uint32_t)c->comm_rank; d.world = (uint32_t)c->comm_world;
     const size_t n = (size_t)d.world * (1u + 3u * (size_t)XS_CAP_MAX);
@@ -1362,20 +1299,19 @@ int comm_buffers(esim_ctx_impl *c)
         next += q[1];
     }
     if (next != d.n_global) return fail(c, ESIM_EINVAL, "esim_comm_init: the ranks' shards do not add up to n_citizens_global (world size differs from the number of shards)");
-    if (c->xs_a2a && W > 1) {
-        // which shards have members in each shared building: every shard sets its own bit where it has, the bits are summed
-        if ((rc = dev_alloc(c, &c->shared_mask, (size_t)d.n_shared_bld + 1u))) return rc;
-        std::vector<uint32_t> bits((size_t)d.n_shared_bld + 1u, 0u);
-        std::vector<int32_t> local((size_t)d.n_shared_bld + 1u, -1);
-        if (d.n_shared_bld) HIP_TRY(c, hipMemcpy(local.data(), d.shared_bld, sizeof(int32_t) * d.n_shared_bld, hipMemcpyDeviceToHost));
-        for (uint32_t k = 0; k < d.n_shared_bld; ++k) bits[k] = local[k] >= 0 ? 1u << d.rank : 0u;
-        HIP_TRY(c, hipMemcpy(c->shared_mask, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
-        if ((rc = exchange_buf(c, 9, c->shared_mask, bits.size()))) return rc;
-        if ((rc = wait_stream(c))) return rc;
-        if ((rc = dev_alloc(c, &c->xs_out, n))) return rc;
-        HIP_TRY(c, hipMemset(c->xs_out, 0, sizeof(uint32_t) * n));
-        d.xs_out = c->xs_out; d.shared_mask = c->shared_mask;
-    }
+    // which shards have members in each shared building: every shard sets its own bit where it has, the bits are summed
+    uint32_t *mask = nullptr;
+    if ((rc = dev_alloc(c, &mask, (size_t)d.n_shared_bld + 1u))) return rc;
+    d.shared_mask = mask;
+    std::vector<uint32_t> bits((size_t)d.n_shared_bld + 1u, 0u);
+    std::vector<int32_t> local((size_t)d.n_shared_bld + 1u, -1);
+    if (d.n_shared_bld) HIP_TRY(c, hipMemcpy(local.data(), d.shared_bld, sizeof(int32_t) * d.n_shared_bld, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < d.n_shared_bld; ++k) bits[k] = local[k] >= 0 ? 1u << d.rank : 0u;
+    HIP_TRY(c, hipMemcpy(mask, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
+    if ((rc = exchange_buf(c, 9, mask, bits.size()))) return rc;
+    if ((rc = wait_stream(c))) return rc;
+    if ((rc = dev_alloc(c, &d.xs_out, n))) return rc;
+    HIP_TRY(c, hipMemset(d.xs_out, 0, sizeof(uint32_t) * n));
     return ESIM_OK;
 }
 
@@ -1422,16 +1358,10 @@ int sync_status(esim_ctx_impl *c, bool ex, Ctrl *h)
     hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(64), 0, c->stream, d);
     if (ex && (rc = exchange_buf(c, 7, d.xe, XE_WORDS))) return rc;
     hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(64), 0, c->stream, d);
-    HIP_TRY(c, hipMemcpyAsync(h, d.ctrl, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pin_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
     if ((rc = wait_stream(c))) return rc;
-    if (h->peer_error) {
-        const uint32_t code = err_decode(h->peer_error);
-        char msg[240];
-        std::snprintf(msg, sizeof msg, "device-side error %d on at least one shard (S underflow / vaccination window exhausted / a chunk table overflowed); every rank returns it",
-                      -(int)code);
-        return fail(c, -(int)code, msg);
-    }
-    return ESIM_OK;
+    *h = *c->pin_ctrl;
+    return ctrl_error(c, *h);       // (k_status_unpack raised any shard's error here too: every rank returns the same code)
 }
 
 }  // namespace
@@ -1507,7 +1437,7 @@ extern "C" int esim_comm_stats(esim_ctx *ctx, uint64_t *collectives)
 namespace {
 
 // One time-parallel chunk of a sharded run: what the shards exchange once per chunk instead of once per step --
-// the liveness of the plan's candidates (V), the Infected commuters to shared buildings (S, all-gathered), the Infected census
+// the liveness of the plan's candidates (V), the Infected commuters to shared buildings (S, all-to-all), the Infected census
 // ahead with the "cannot" word (F), the steps with a cut (C).  Kernels and collectives are enqueued on the context's stream.
 int enqueue_sharded_chunk(esim_ctx_impl *c, uint32_t limit_t, bool vax)
 {
@@ -1519,20 +1449,13 @@ int enqueue_sharded_chunk(esim_ctx_impl *c, uint32_t limit_t, bool vax)
         if ((rc = exchange_buf(c, 3, d.xv, XV_HEADER + (size_t)FREE_MAX * (PLAN_W / 32u)))) return rc;
         hipLaunchKernelGGL(k_chunk_vax<false>, dim3(FREE_MAX), dim3(FIN_TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1);
     }
+    // the commuter exchange, all-to-all: a record goes to the shards that have members in its building;
+    // segments of the same size between every pair of shards (their need is exchanged with the status, so they grow alike
+    // everywhere).  One rank sends nothing.
     const size_t seg = 1u + 3u * (size_t)d.xs_cap;
-    if (d.xs_out) {
-        // all-to-all: a record goes to the shards that have members in its building; segments of the same size
-        // between every pair of shards (their need is exchanged with the status, so they grow alike everywhere)
-        for (uint32_t r = 0; r < d.world; ++r) HIP_TRY(c, hipMemsetAsync(d.xs_out + (size_t)r * seg, 0, sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(k_shared_pack, dim3(256), dim3(TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t);
-        if ((rc = exchange_alltoall(c, 4, d.xs_out, d.xs, seg))) return rc;
-    } else {
-        HIP_TRY(c, hipMemsetAsync(d.xs + (size_t)d.rank * seg, 0, sizeof(uint32_t), c->stream));
-        if (c->comm_fn)          // (a caller's transport sums the whole buffer: the other ranks' segments must be zero)
-            for (uint32_t r = 0; r < d.world; ++r) if (r != d.rank) HIP_TRY(c, hipMemsetAsync(d.xs + (size_t)r * seg, 0, sizeof(uint32_t) * seg, c->stream));
-        hipLaunchKernelGGL(k_shared_pack, dim3(256), dim3(TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t);
-        if ((rc = exchange_gather(c, 4, d.xs, seg))) return rc;
-    }
+    for (uint32_t r = 0; r < d.world; ++r) HIP_TRY(c, hipMemsetAsync(d.xs_out + (size_t)r * seg, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_shared_pack, dim3(256), dim3(TPB), 0, c->stream, d, (uint32_t)c->xf_n, limit_t);
+    if ((rc = exchange_alltoall(c, 4, d.xs_out, d.xs, seg))) return rc;
     hipLaunchKernelGGL(k_shard_prep, dim3(1), dim3(128), 0, c->stream, d, (uint32_t)c->xf_n, limit_t);
     if ((rc = exchange(c, 2))) return rc;
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, d, (uint32_t)c->xf_n, limit_t, 1, 1);
@@ -1610,14 +1533,14 @@ extern "C" int esim_run_sharded(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_don
             const uint32_t bursts = stall ? 1u : std::min<uint32_t>((remaining + (uint32_t)c->xf_n - 1u) / (uint32_t)c->xf_n + (c->elig_seen ? 1u : 0u), 4u);
             for (uint32_t g = 0; g < bursts; ++g) if ((rc = enqueue_sharded_chunk(c, limit_t, c->elig_seen))) return rc;
             // every rank reads the same decision words: steps advanced (all shards run a chunk or none does), the summed error
-            // fields, the gathered segment need
+            // fields, the segment need of every shard
             if ((rc = sync_status(c, ex, &h))) return rc;
             const uint32_t done = h.t - t_first;
             c->host_t = h.t; remaining -= done;
             c->shard_chunk_steps += done;
             if (h.vax_cuts > c->vax_chunk_cuts) c->repair_armed = true;  // (cuts are decided from summed words: every rank arms in the same burst)
             c->vax_chunk_cuts = h.vax_cuts; c->vax_chunk_repairs = h.vax_repairs;
-            // the commuter segment follows the need (the same on every rank: the counts were gathered)
+            // the commuter segment follows the need (the same on every rank: the needs came with the status exchange)
             const uint32_t cap_before = d.xs_cap;
             while (d.xs_cap < XS_CAP_MAX && 2u * h.xs_need_all > d.xs_cap) d.xs_cap *= 2u;     // (xs_need_all: the maximum over the shards, from the status exchange)
             if (done) { local_ranges.emplace_back(t_first, done); stall = 0; continue; }
@@ -1658,84 +1581,6 @@ extern "C" int esim_shard_stats(esim_ctx *ctx, uint64_t *chunk_steps, uint64_t *
     if (!c) return ESIM_EINVAL;
     if (chunk_steps) *chunk_steps = c->shard_chunk_steps;
     if (coupled_steps) *coupled_steps = c->shard_step_steps;
-    return ESIM_OK;
-}
-
-extern "C" int esim_future_infected(esim_ctx *ctx)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    hipLaunchKernelGGL(k_future, dim3(1), dim3(FIN_TPB), 0, c->stream, c->d, (uint32_t)c->xf_n, c->free_limit ? c->free_limit : c->P.max_steps);
-    HIP_TRY(c, hipGetLastError());
-    return ESIM_OK;
-}
-
-// A burst of decoupled chunks without a host round trip per chunk: the caller repeats
-// { esim_future_infected; all-reduce F; esim_free_enqueue } and then collects once.
-extern "C" int esim_free_begin(esim_ctx *ctx, uint32_t n_steps)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    int rc = check_budget(c, n_steps);
-    if (rc) return rc;
-    if (n_steps == 0) return fail(c, ESIM_EINVAL, "esim_free_begin: no steps");
-    if (c->d.n_shared_bld || c->d.n_shared_room) return fail(c, ESIM_ESTATE, "esim_free_begin: shards that share buildings need the coupled steps");
-    if (!c->pipeline || !c->time_parallel) return fail(c, ESIM_ESTATE, "esim_free_begin: needs pipeline level 2");
-    c->free_limit = c->host_t + n_steps - 1u;
-    c->free_first = c->host_t;
-    return ESIM_OK;
-}
-
-extern "C" int esim_free_enqueue(esim_ctx *ctx)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded || !c->free_limit) return fail(c, ESIM_ESTATE, "esim_free_enqueue: no burst open (esim_free_begin)");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    bool tk = c->kernel_timing;
-    if (tk && c->fev_used + 2 > c->fev.size())
-        for (int i = 0; i < 2 && tk; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) tk = false; else c->fev.push_back(e); }
-    if (tk) HIP_TRY(c, hipEventRecord(c->fev[c->fev_used], c->stream));
-    hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, c->d, (uint32_t)c->xf_n, c->free_limit, 1, 0);
-    enqueue_parallel_chunk(c, 2, c->free_limit);                  // leaves the census ahead of the NEXT chunk in buffer F
-    if (tk) { HIP_TRY(c, hipEventRecord(c->fev[c->fev_used + 1], c->stream)); c->fev_used += 2; }
-    HIP_TRY(c, hipGetLastError());
-    return ESIM_OK;
-}
-
-extern "C" int esim_free_collect(esim_ctx *ctx, uint32_t *n_done)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded || !c->free_limit) return fail(c, ESIM_ESTATE, "esim_free_collect: no burst open (esim_free_begin)");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    c->free_limit = 0;
-    Ctrl h;
-    HIP_TRY(c, hipMemcpyAsync(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (h.error) return fail(c, -(int)h.error, "device-side error (raised at check " + std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
-    const uint32_t done = h.t - c->free_first;
-    c->last_chunk_pairs = h.chunk_pairs;
-    // device time of the chunks of the burst (k_future and the collective in front of each are not inside the pairs)
-    for (size_t i = 0; i + 1 < c->fev_used; i += 2) { float ms; HIP_TRY(c, hipEventElapsedTime(&ms, c->fev[i], c->fev[i + 1])); if (done) c->chunk_ms += ms; }
-    c->fev_used = 0;
-    c->chunk_steps += done;
-    c->chunk_count += (done + (uint32_t)c->xf_n - 1u) / (uint32_t)c->xf_n;
-    c->host_t = h.t;
-    if (n_done) *n_done = done;
-    return ESIM_OK;
-}
-
-extern "C" int esim_run_free(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_done)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    int rc = check_budget(c, n_steps);
-    if (rc) return rc;
-    if (n_steps > c->xf_n) return fail(c, ESIM_EINVAL, "esim_run_free: more steps than the future vector covers");
-    if (c->d.n_shared_bld || c->d.n_shared_room) return fail(c, ESIM_ESTATE, "esim_run_free: shards that share buildings need the coupled steps");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    uint32_t done = 0;
-    if ((rc = run_chunk(c, n_steps, &done, nullptr))) return rc;
-    c->host_t += done;
-    if (n_done) *n_done = done;
     return ESIM_OK;
 }
 
@@ -1821,9 +1666,9 @@ extern "C" int esim_debug_counters(esim_ctx *ctx, uint32_t out[16])
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !out) return ESIM_EINVAL;
     HIP_TRY(c, hipSetDevice(c->P.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     Ctrl h;
-    HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
+    const int rc = read_ctrl(c, &h);
+    if (rc) return rc;
     const uint32_t v[16] = { h.t, h.chunk_ok, h.chunk_parallel, h.chunk_pairs, h.n_items, h.items_per_wave, h.n_units, h.chunk_bus,
                              h.n_route_pairs_big, h.n_newexp, h.log_len, h.n_susceptible, h.lockdown, h.mask, h.at_work, h.bus_dir };
     std::memcpy(out, v, sizeof v);
@@ -1876,16 +1721,6 @@ extern "C" int esim_set_tiny_chunk_limit(esim_ctx *ctx, uint32_t max_pairs)
     return ESIM_OK;
 }
 
-extern "C" int esim_exchange_buffer(esim_ctx *ctx, int which, void **device_ptr, size_t *n_u32)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
-    if (which < 0 || which > 2) return fail(c, ESIM_EINVAL, "esim_exchange_buffer: which must be 0, 1 or 2");
-    if (device_ptr) *device_ptr = which == 2 ? (void *)c->d.xf : which ? (void *)c->d.xb : (void *)c->d.xa;
-    if (n_u32) *n_u32 = which == 2 ? c->xf_n + 1 : which ? c->xb_n : c->xa_n;
-    return ESIM_OK;
-}
-
 extern "C" int esim_read_records(esim_ctx *ctx, uint32_t first_step, uint32_t n, esim_step_result *out)
 {
     esim_ctx_impl *c = CTX(ctx);
@@ -1895,37 +1730,6 @@ extern "C" int esim_read_records(esim_ctx *ctx, uint32_t first_step, uint32_t n,
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out, &c->d.records[first_step], sizeof(esim_step_result) * n, hipMemcpyDeviceToHost));
     return device_error(c);
-}
-
-extern "C" int esim_stream(esim_ctx *ctx, void **stream)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !stream) return fail(c, ESIM_EINVAL, "esim_stream: null argument");
-    *stream = (void *)c->stream;
-    return ESIM_OK;
-}
-
-extern "C" int esim_set_stream(esim_ctx *ctx, void *stream)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c) return ESIM_EINVAL;
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
-    c->stream = (hipStream_t)stream;
-    c->own_stream = false;
-    return ESIM_OK;
-}
-
-extern "C" int esim_set_exchange_buffer(esim_ctx *ctx, int which, void *device_ptr)
-{
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
-    if (which < 0 || which > 2 || !device_ptr) return fail(c, ESIM_EINVAL, "esim_set_exchange_buffer: bad argument");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (which == 2) c->d.xf = (uint32_t *)device_ptr; else if (which) c->d.xb = (uint32_t *)device_ptr; else c->d.xa = (uint32_t *)device_ptr;
-    return ESIM_OK;
 }
 
 extern "C" int esim_synchronize(esim_ctx *ctx)
@@ -1967,9 +1771,9 @@ extern "C" int esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !n_out) return fail(c, ESIM_ESTATE, "no population uploaded");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     Ctrl h;
-    HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
+    const int rc = read_ctrl(c, &h);
+    if (rc) return rc;
     const uint32_t t_done = c->host_t - 1u;                       // steps run so far
     // log_off[TE_BIAS + s] = first entry of step s; the entries before step 1 are the seeds (simulator_builder.rs:1268-1287)
     std::vector<uint32_t> off((size_t)t_done + 2u);
@@ -2047,9 +1851,9 @@ extern "C" int esim_checkpoint_size(esim_ctx *ctx, size_t *bytes)
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !bytes) return fail(c, ESIM_ESTATE, "no population uploaded");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     Ctrl h;
-    HIP_TRY(c, hipMemcpy(&h, c->d.ctrl, sizeof h, hipMemcpyDeviceToHost));
+    const int rc = read_ctrl(c, &h);
+    if (rc) return rc;
     CkptHeader k;
     ckpt_header(c, h, &k);
     *bytes = ckpt_bytes(k);
@@ -2060,13 +1864,11 @@ extern "C" int esim_checkpoint_save(esim_ctx *ctx, void *buf, size_t cap)
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !buf) return fail(c, ESIM_ESTATE, "no population uploaded");
-    if (c->free_limit) return fail(c, ESIM_ESTATE, "esim_checkpoint_save: a burst of decoupled chunks is open");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     const Dev &d = c->d;
     Ctrl h;
-    HIP_TRY(c, hipMemcpy(&h, d.ctrl, sizeof h, hipMemcpyDeviceToHost));
-    if (h.error) return fail(c, -(int)h.error, "esim_checkpoint_save: the context is in a device-side error state");
+    int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
     CkptHeader k;
     ckpt_header(c, h, &k);
     if (cap < ckpt_bytes(k)) return fail(c, ESIM_ERANGE, "esim_checkpoint_save: buffer smaller than esim_checkpoint_size");
@@ -2074,7 +1876,6 @@ extern "C" int esim_checkpoint_save(esim_ctx *ctx, void *buf, size_t cap)
     std::memcpy(p, &k, sizeof k); p += sizeof k;
     std::memcpy(p, &h, sizeof h); p += sizeof h;
     auto pull = [&](const void *src, size_t bytes) -> int { if (bytes) HIP_TRY(c, hipMemcpy(p, src, bytes, hipMemcpyDeviceToHost)); p += bytes; return ESIM_OK; };
-    int rc;
     if ((rc = pull(d.hist, sizeof(uint32_t) * TE_SLOTS))) return rc;
     if ((rc = pull(d.log_off, sizeof(uint32_t) * (TE_SLOTS + 1)))) return rc;
     if ((rc = pull(d.cit, sizeof(uint32_t) * (size_t)d.n))) return rc;
@@ -2113,7 +1914,7 @@ extern "C" int esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t by
         return fail(c, ESIM_EINVAL, "esim_checkpoint_restore: the control block does not match the checkpoint's header (corrupt file)");
     h.chunk_ok = 0; h.chunk_parallel = 0; h.chunk_done = 0; h.n_items = 0; h.n_newexp = 0; h.n_units = 0; h.unit_next = 0;
     h.n_route_pairs_big = 0; h.prev_n_items = 0; h.prev_per_wave = 0; h.items_per_wave = 0; h.small_done = 0;
-    h.free_base = 0; h.n_riders = 0; h.peer_error = 0;
+    h.future_t0 = 0; h.n_riders = 0; h.peer_error = 0;
     for (int z = 0; z < 5; ++z) h.counts[z] = 0;
     // marks of the last step are only ever cleared, never read, by the step after it: start without them
     for (uint32_t z = 0; z < MARK_SLOTS; ++z) { h.n_touched_bld[z] = 0; h.n_touched_room[z] = 0; h.n_touched_route[z] = 0; h.n_touched_route_big[z] = 0; }

@@ -78,7 +78,7 @@ struct Ctrl {
     uint32_t n_touched_bld[MARK_SLOTS], n_touched_room[MARK_SLOTS], n_touched_route[MARK_SLOTS], n_touched_route_big[MARK_SLOTS];
     uint32_t counts[5];         // census of the step in flight (global when sharded, after unpack)
     uint32_t n_riders;
-    uint32_t free_base;         // first step of the current free-running batch (decoupled sharded mode)
+    uint32_t future_t0;         // first step of the census ahead in buffer F (k_future): k_decide runs a chunk only from that step
     uint32_t small_done;        // steps executed by the last k_small launch
     uint32_t chunk_ok;          // steps of the current chunk that may run pipelined (k_decide)
     uint32_t chunk_t0;          // first step of the current chunk
@@ -251,10 +251,10 @@ struct Dev {
     // sharded time-parallel chunks: what the shards exchange once per chunk
     uint32_t rank, world;
     uint32_t *xv;                       // [XV_HEADER + FREE_MAX * PLAN_W / 32] liveness of every step's first PLAN_W vaccination candidates
-    uint32_t *xs;                       // [world][1 + 3 * xs_cap] Infected commuters to shared buildings: (citizen word, shared building, shared room | -1)
+    uint32_t *xs;                       // [world][1 + 3 * xs_cap] Infected commuters to shared buildings each other shard sent this one: (citizen word, shared building, shared room | -1)
     uint32_t xs_cap;                    // records per shard in this chunk's exchange
     // the commuter exchange as an all-to-all: a record goes to the shards that have members in its building, and to no other
-    uint32_t *xs_out;                   // [world][1 + 3 * xs_cap] what this shard sends to each of the others (nullptr: the all-gather form)
+    uint32_t *xs_out;                   // [world][1 + 3 * xs_cap] what this shard sends to each of the others
     const uint32_t *shared_mask;        // [n_shared_bld] bit r: shard r has members in the shared building (summed at set-up)
     uint32_t *xc;                       // [FREE_MAX + 2] steps of the chunk with a cut (k_chunk_count)
     uint32_t *xl;                       // [FREE_MAX + 2] steps of the chunk in which a citizen of THIS shard left the eligible set on a bus with a planned

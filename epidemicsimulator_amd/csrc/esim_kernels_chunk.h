@@ -42,7 +42,7 @@ __device__ __forceinline__ void future_body(const Dev &d, uint32_t max_ahead, ui
         d.xf[tid] = hi - lo;
     }
     if (tid == 0) {
-        ctrl->free_base = t0;
+        ctrl->future_t0 = t0;
         // citizens Infected in at least one step of the chunk: exposure steps [first window's low end, last window's top]
         const uint32_t pairs = n_ahead ? win[n_ahead - 1u + (uint32_t)it] : 0u;
         ctrl->chunk_pairs = pairs;
@@ -88,7 +88,7 @@ __device__ __forceinline__ void decide_body(const Dev &d, uint32_t max_ahead, ui
     // under a vaccination programme only a chunk whose vaccinations are planned may run (k_chunk_vax); the Infected census ahead
     // then loses those the plan vaccinates before (prefix sums of xf_adj)
     const bool vax = ld(&ctrl->have_elig) != 0u;
-    const bool ok = (vax ? (ld(&ctrl->vax_chunk) != 0u && ld(&ctrl->vax_fail) == 0u) : !ld(&ctrl->vacc_active)) && !ld(&ctrl->finished) && !ld(&ctrl->error) && ld(&ctrl->free_base) == t0;
+    const bool ok = (vax ? (ld(&ctrl->vax_chunk) != 0u && ld(&ctrl->vax_fail) == 0u) : !ld(&ctrl->vacc_active)) && !ld(&ctrl->finished) && !ld(&ctrl->error) && ld(&ctrl->future_t0) == t0;
     uint32_t adj[2] = { 0u, 0u };
     if (vax && ok && !adj_folded) {                       // (sharded: folded into buffer F before its all-reduce, k_shard_prep)
         uint32_t carry = 0u;
@@ -497,14 +497,13 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_vax(Dev d, uint32_t max_ahead
 // ---------------------------------------------------------------------- sharded chunks: the commuter exchange
 // A building or school room whose members live on several shards is shared (esim_shard_population).  An Infected member
 // standing in it matters to every shard that has members there: per chunk, each shard sends the citizen words of its own
-// Infected whose work building is shared, with the building's and the room's index in the shared tables (k_shared_pack; the
-// segments are all-gathered), and k_chunk_marks enters the received ones into its map next to its own.  The slice walked is
+// Infected whose work building is shared, with the building's and the room's index in the shared tables (k_shared_pack; an
+// all-to-all delivers them), and k_chunk_marks enters the received ones into its map next to its own.  The slice walked is
 // the one of the longest chunk that can follow (the decisions come later); an entry whose stretch misses the chunk is dropped
 // by the receiver.
 __global__ __launch_bounds__(TPB) void k_shared_pack(Dev d, uint32_t max_ahead, uint32_t limit_t)
 {
     const Ctrl *ctrl = d.ctrl;
-    uint32_t *seg = d.xs + (size_t)d.rank * (1u + 3u * d.xs_cap);
     const uint32_t t0 = ctrl->t;
     const uint32_t n_ahead = t0 > limit_t ? 0u : (limit_t - t0 + 1u < max_ahead ? limit_t - t0 + 1u : max_ahead);
     if (n_ahead == 0u) return;
@@ -528,26 +527,18 @@ __global__ __launch_bounds__(TPB) void k_shared_pack(Dev d, uint32_t max_ahead, 
                 }
             }
         }
-        const unsigned long long m = __ballot(send);
-        if (!m) continue;
-        if (d.xs_out) {
-            // all-to-all: the record goes into the segment of every OTHER shard that has members in the building
-            const uint32_t to = send ? d.shared_mask[sb] & ~(1u << d.rank) : 0u;
-            for (uint32_t r = 0; r < d.world; ++r) {
-                const unsigned long long mr = __ballot((to >> r) & 1u);
-                if (!mr) continue;
-                uint32_t *out = d.xs_out + (size_t)r * (1u + 3u * d.xs_cap);
-                uint32_t pos = 0u;
-                if (lane == 0) pos = atomicAdd(&out[0], (uint32_t)__popcll(mr));
-                pos = __shfl(pos, 0, 64) + (uint32_t)__popcll(mr & ((1ull << lane) - 1ull));
-                if (((to >> r) & 1u) && pos < d.xs_cap) { out[1u + 3u * pos] = w; out[2u + 3u * pos] = sb; out[3u + 3u * pos] = sr; }
-            }
-            continue;
+        if (!__ballot(send)) continue;
+        // the record goes into the segment of every OTHER shard that has members in the building
+        const uint32_t to = send ? d.shared_mask[sb] & ~(1u << d.rank) : 0u;
+        for (uint32_t r = 0; r < d.world; ++r) {
+            const unsigned long long mr = __ballot((to >> r) & 1u);
+            if (!mr) continue;
+            uint32_t *out = d.xs_out + (size_t)r * (1u + 3u * d.xs_cap);
+            uint32_t pos = 0u;
+            if (lane == 0) pos = atomicAdd(&out[0], (uint32_t)__popcll(mr));       // one atomic per wavefront and destination
+            pos = __shfl(pos, 0, 64) + (uint32_t)__popcll(mr & ((1ull << lane) - 1ull));
+            if (((to >> r) & 1u) && pos < d.xs_cap) { out[1u + 3u * pos] = w; out[2u + 3u * pos] = sb; out[3u + 3u * pos] = sr; }
         }
-        uint32_t pos = 0u;
-        if (lane == 0) pos = atomicAdd(&seg[0], (uint32_t)__popcll(m));       // one atomic per wavefront
-        pos = __shfl(pos, 0, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (send && pos < d.xs_cap) { seg[1u + 3u * pos] = w; seg[2u + 3u * pos] = sb; seg[3u + 3u * pos] = sr; }
     }
 }
 
@@ -566,12 +557,14 @@ __global__ __launch_bounds__(128) void k_shard_prep(Dev d, uint32_t max_ahead, u
         if (cnt > d.xs_cap) overflow = true;
         if (r != d.rank) n_remote += min(cnt, d.xs_cap);
     }
-    // (what this shard saw: the segments it received -- and, in the all-to-all form, those it sent; the status exchange takes the
-    // maximum over the shards, so that the segments grow alike everywhere)
+    // (what this shard saw: the segments it received and those it sent; the status exchange takes the maximum over the shards,
+    // so that the segments grow alike everywhere)
     ctrl->xs_need = 0u;
     for (uint32_t r = 0; r < d.world; ++r) {
-        if (r != d.rank || !d.xs_out) ctrl->xs_need = max(ctrl->xs_need, d.xs[(size_t)r * (1u + 3u * d.xs_cap)]);
-        if (d.xs_out && r != d.rank) { const uint32_t o = d.xs_out[(size_t)r * (1u + 3u * d.xs_cap)]; ctrl->xs_need = max(ctrl->xs_need, o); if (o > d.xs_cap) overflow = true; }
+        if (r == d.rank) continue;
+        const uint32_t o = d.xs_out[(size_t)r * (1u + 3u * d.xs_cap)];
+        ctrl->xs_need = max(ctrl->xs_need, max(o, d.xs[(size_t)r * (1u + 3u * d.xs_cap)]));
+        if (o > d.xs_cap) overflow = true;
     }
     // (a shard in a device-side error state makes the chunk a no-op on EVERY shard: the word is summed)
     const bool fits = d.xf[d.xf_n] == 0u && !overflow && !ctrl->error && !ctrl->finished &&
@@ -741,7 +734,7 @@ __global__ __launch_bounds__(TPB) void k_chunk_marks(Dev d)
         uint32_t c = 0u, w = 0u, r_bld = 0xFFFFFFFFu, r_room = 0xFFFFFFFFu;
         if (act && !remote) { c = d.log[i0 + idx]; w = d.cit[c]; }
         if (remote) {
-            // Sharded: the Infected commuters the other shards sent (k_shared_pack, all-gathered): each stands in a building
+            // Sharded: the Infected commuters the other shards sent (k_shared_pack, all-to-all): each stands in a building
             // (and room) that has members here too; it enters the map like a local citizen's work building and room.
             uint32_t e = idx - E;
             const uint32_t *seg = nullptr;
@@ -2046,7 +2039,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_batch_finish(Dev d, uint32_t t0, ui
 //   exposures per step (statistics.rs:181) from the final citizen words of the newly exposed
 //   census, records, histogram, log offsets, control block (batch_finish_body)
 //   [scatter] the new log entries in step order; hash slots of the chunk's items emptied
-//   [next]    the census ahead and the decisions of the NEXT chunk (k_future + k_decide)
+//   [do_next] the census ahead and the decisions of the NEXT chunk (k_future + k_decide)
 // It takes (t0, n) from the control block, so that the host can enqueue chunk after chunk without waiting; chunk_done tells
 // k_chunk_scatter (the many-workgroup form of [scatter], used while many citizens are Infected) that the books were written.
 struct BooksShared { uint32_t e_cnt[2 * FREE_MAX]; uint32_t lo_s[FREE_MAX], cur_s[FREE_MAX]; uint32_t win[BF_WIN]; uint32_t wtmp[FIN_TPB / 64]; };
@@ -2062,9 +2055,6 @@ __device__ __forceinline__ void books_body(const Dev &d, int fused, int do_next,
             // a plan was made but the chunk does not run: k_chunk_vax_final takes the plan's fields out of the words again
             ctrl->prev_vax = ld(&ctrl->vax_chunk); ctrl->prev_n_eff = 0u; ctrl->prev_planned = ld(&ctrl->vax_planned); ctrl->vax_chunk = 0u;
         }
-        // a sharded burst all-reduces buffer F in place before every chunk: it must hold THIS shard's census again, whether
-        // or not the chunk ran
-        if (do_next == 2) future_body(d, max_ahead, limit_t, win, wtmp);
         return;
     }
     const uint32_t t0 = ctrl->chunk_t0, n = ctrl->chunk_ok;
@@ -2169,12 +2159,12 @@ __device__ __forceinline__ void books_body(const Dev &d, int fused, int do_next,
     }
     const uint32_t pb3 = PROF_NOW();
     if (do_next) {
-        // 1: the next chunk's census ahead and decisions; 2: the census ahead only (sharded runs all-reduce it before deciding)
+        // the next chunk's census ahead and decisions
         __syncthreads();
         future_body(d, max_ahead, limit_t, win, wtmp);
         __syncthreads();
         const uint32_t pb4 = PROF_NOW();
-        if (do_next == 1 && tid < 64u) decide_body(d, max_ahead, limit_t, 1);
+        if (tid < 64u) decide_body(d, max_ahead, limit_t, 1);
         BOOKS_PROF(d, 4, pb4 - pb3);
     }
     BOOKS_PROF(d, 0, pb1 - pb0); BOOKS_PROF(d, 1, pb2 - pb1); BOOKS_PROF(d, 2, pb3 - pb2); BOOKS_PROF(d, 3, PROF_NOW() - pb3);

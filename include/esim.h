@@ -132,38 +132,10 @@ int  esim_step(esim_ctx *ctx, esim_step_result *out);
 int  esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done,
               esim_step_result *out_array, uint32_t *n_done);
 
-/* Split-phase form of one step for sharded (multi-GPU) runs.  Between the phases the
- * caller SUM-all-reduces the exchange buffer (device memory, uint32) across shards:
- *   esim_step_begin     -- Citizen::execute_time_step for every citizen (generate_exposures,
- *                          simulator.rs:155-260); packs counts + shared infected counts
- *   [all-reduce A]
- *   esim_step_exposures -- apply_exposures (simulator.rs:262-405); packs vaccination liveness
- *   [all-reduce B]
- *   esim_step_finish    -- apply_interventions (simulator.rs:455-556), writes the record
- * With one shard the buffers need no reduction and esim_step() is exactly this sequence. */
-int  esim_step_begin(esim_ctx *ctx);
-int  esim_step_exposures(esim_ctx *ctx);
-int  esim_step_finish(esim_ctx *ctx, esim_step_result *out /* may be NULL */);
-int  esim_exchange_buffer(esim_ctx *ctx, int which /* 0 = A, 1 = B, 2 = F */, void **device_ptr, size_t *n_u32);
-/* Pipelined chunks.  A citizen exposed in step t is Infected no earlier than t + exposed_time + 1
- * (disease.rs:47-71).  Hence, while no vaccination programme runs, the Infected census -- and with it every
- * intervention decision (interventions.rs:110-184), the schedule (citizen.rs:176-206) and who marks which
- * building -- is known for the next n <= exposed_time + 1 steps (n = size of buffer F, at most 96).  esim_run
- * uses this by itself (one kernel per step, books written once per chunk).  Shards that share no building
- * (n_shared_* == 0) use it to run without per-step collectives:
- *   esim_future_infected -- writes this shard's Infected census of the next n steps into buffer F
- *   [SUM all-reduce of F over the shards]
- *   esim_run_free(k, &done) -- runs min(k, steps before the one that would start vaccinating) whole steps
- *                              with no exchange; records hold THIS shard's census; done < k means the next
- *                              step must be a coupled one (esim_step_begin / _exposures / _finish).
- * Buffer F holds n + 1 words: the census of the next n steps and one word counting the shards whose chunk does
- * not fit the one-pass form below (after the all-reduce every shard therefore takes the same form).
- * Bursts: esim_run_free waits for the device once per chunk.  To keep several chunks in flight the caller
- * opens a burst with esim_free_begin(k) (k = steps it may cover), calls esim_future_infected once and then repeats
- * { all-reduce F; esim_free_enqueue } as often as it likes -- each round enqueues one whole chunk, which is a no-op on
- * EVERY shard when it cannot run in the one-pass form or would reach the step that starts vaccinating, and which ends by
- * writing the census ahead of the chunk after it into F -- and calls esim_free_collect(&done) once: done = steps the
- * burst advanced (the same on all shards).
+/* Pipelined chunks.  A citizen exposed in step t is Infected no earlier than t + exposed_time + 1 (disease.rs:47-71).  Hence,
+ * while no vaccination programme runs, the Infected census -- and with it every intervention decision (interventions.rs:110-184),
+ * the schedule (citizen.rs:176-206) and who marks which building -- is known for the next n <= exposed_time + 1 steps (at most
+ * 96): esim_run and esim_run_sharded run such chunks of steps by themselves.
  * esim_set_pipeline(ctx, level): 0 = sequential steps only; 1 = chunks run as one kernel per step (k_pipe);
  * 2 = additionally to 1, when the chunk's marks fit the hash map, ALL steps of a chunk are drawn in one
  * pass (a citizen's exposure step is the earliest step at which any of its draws succeeds -- one atomicMin on
@@ -205,11 +177,6 @@ int  esim_run_sharded(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_done);
 /* How the steps of sharded runs were executed so far: as time-parallel chunks (one round of exchanges per chunk) / as coupled
  * steps (two exchanges per step). */
 int  esim_shard_stats(esim_ctx *ctx, uint64_t *chunk_steps, uint64_t *coupled_steps);
-int  esim_future_infected(esim_ctx *ctx);
-int  esim_run_free(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_done);
-int  esim_free_begin(esim_ctx *ctx, uint32_t n_steps);
-int  esim_free_enqueue(esim_ctx *ctx);
-int  esim_free_collect(esim_ctx *ctx, uint32_t *n_done);
 int  esim_set_pipeline(esim_ctx *ctx, int level);
 int  esim_chunk_timing(esim_ctx *ctx, double *total_ms, uint64_t *steps, uint64_t *chunks);
 /* Device time of the chunk pass per KERNEL (HIP events in front of every kernel of a chunk on the context's stream, resolved at
@@ -235,16 +202,9 @@ int  esim_vax_chunk_stats(esim_ctx *ctx, uint64_t *steps, uint64_t *cuts);
  * exposed later in the chunk.  Sharded runs do the same with two more exchanges per planned chunk (the steps in which a shard lost
  * a citizen, callback `which` 10; the candidates' liveness a second time, `which` 3).  ESIM_VAX_REPAIR=0 switches it off. */
 int  esim_vax_repair_stats(esim_ctx *ctx, uint64_t *repairs);
-/* Record log read-back for split-phase runs (records first..first+n-1, 1-based time steps). */
+/* Record log read-back: records first..first+n-1 (1-based time steps) of the steps run so far, by whichever call.
+ * esim_synchronize waits for all work of this context. */
 int  esim_read_records(esim_ctx *ctx, uint32_t first_step, uint32_t n, esim_step_result *out);
-/* The HIP stream all work of this context is enqueued on (hipStream_t as void*).  esim_set_stream
- * makes the context use a caller-owned stream instead (e.g. the one a collective library orders
- * its all-reduce against); esim_set_exchange_buffer replaces exchange buffer `which` by caller-owned
- * device memory of at least the size esim_exchange_buffer reports (e.g. a tensor the collective
- * library can address). */
-int  esim_stream(esim_ctx *ctx, void **stream);
-int  esim_set_stream(esim_ctx *ctx, void *stream);
-int  esim_set_exchange_buffer(esim_ctx *ctx, int which, void *device_ptr);
 int  esim_synchronize(esim_ctx *ctx);
 
 /* Per-citizen state in reference terms, for visualisation / lookup-table sync / checkpoints
@@ -266,8 +226,7 @@ int  esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint32_t *step
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
- * continues bit for bit as if it had not been interrupted.  Between calls, i.e. never inside esim_step_begin..finish or
- * an open burst. */
+ * continues bit for bit as if it had not been interrupted. */
 int  esim_checkpoint_size(esim_ctx *ctx, size_t *bytes);
 int  esim_checkpoint_save(esim_ctx *ctx, void *buf, size_t cap);
 int  esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t bytes);

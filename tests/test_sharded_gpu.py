@@ -56,18 +56,6 @@ def test_two_shards_match_oracle():
     assert all("ok" in o for o in outs)
 
 
-def test_two_and_three_shards_all_gather_exchange_match_oracle():
-    # the commuter exchange of the chunk form is an all-to-all of owner-addressed segments by default (a record goes to the shards
-    # that have members in its building); ESIM_XS_MODE=gather keeps round 2's all-gather of every shard's records to every shard
-    # for the A/B -- same records either way
-    cfg = dict(backend="gloo", cuts="even", spec=dict(n_citizens=12000, n_areas=40, citizens_per_school=2500, n_seeds=16),
-               params=AGGRESSIVE, steps=360, chunk=120, expect=dict(vaccinated=1),
-               env_by_rank={str(r): {"ESIM_XS_MODE": "gather"} for r in range(3)})
-    assert all("ok" in o for o in launch(2, cfg))
-    cfg3 = dict(cfg, spec=dict(n_citizens=9000, n_areas=13, citizens_per_school=3000, n_seeds=16), params=dict(AGGRESSIVE, seed=9), steps=240)
-    assert all("ok" in o for o in launch(3, cfg3))
-
-
 def test_two_shards_coupled_steps_only_match_oracle():
     # the form every step can take: three device phases around two exchanges per step (pipeline level 0)
     cfg = dict(backend="gloo", cuts="even", spec=dict(n_citizens=12000, n_areas=40, citizens_per_school=2500, n_seeds=16),
@@ -78,7 +66,7 @@ def test_two_shards_coupled_steps_only_match_oracle():
 
 def test_three_uneven_shards_match_oracle():
     cfg = dict(backend="gloo", cuts="even", spec=dict(n_citizens=9000, n_areas=13, citizens_per_school=3000, n_seeds=16),
-               params=dict(AGGRESSIVE, seed=9), steps=240, chunk=120)
+               params=dict(AGGRESSIVE, seed=9), steps=240, chunk=120, expect=dict(vaccinated=1))
     outs = launch(3, cfg)
     assert all("ok" in o for o in outs)
 
@@ -139,8 +127,9 @@ def test_a_rank_whose_chunks_never_fit_takes_every_rank_to_coupled_steps():
 
 
 def test_commuter_segment_grows_with_the_need():
-    # the all-gathered segment of Infected commuters starts at 2 records per rank here (ESIM_XS_CAP): every chunk that needs
-    # more is a no-op on all ranks, the segment doubles (the need is gathered too, so all ranks agree) and the chunk runs again
+    # the all-to-all segment of Infected commuters between two ranks starts at 2 records here (ESIM_XS_CAP): every chunk that
+    # needs more is a no-op on all ranks, the segment doubles (the need comes with the status exchange, so all ranks agree) and
+    # the chunk runs again
     cfg = dict(backend="gloo", cuts="even", spec=dict(n_citizens=12000, n_areas=40, citizens_per_school=2500, n_seeds=16),
                params=AGGRESSIVE, steps=360, chunk=120, expect=dict(vaccinated=1),
                env_by_rank={"0": {"ESIM_XS_CAP": 2}, "1": {"ESIM_XS_CAP": 2}})
