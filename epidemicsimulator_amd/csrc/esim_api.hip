@@ -88,6 +88,9 @@ struct esim_ctx_impl {
     uint32_t small_max = 128;          // infected-slice length up to which the persistent single-workgroup kernel runs a step
     hipEvent_t sev[2] = { nullptr, nullptr };   // k_small timing
     double small_ms = 0; uint64_t small_steps = 0;
+    // esim_area_census: the count table on the device and its pinned mirror, [n_areas * 5]
+    uint32_t *area_cnt = nullptr;
+    uint32_t *pin_area = nullptr; size_t pin_area_n = 0;
 };
 
 #define CTX(c) (reinterpret_cast<esim_ctx_impl *>(c))
@@ -239,6 +242,7 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     for (auto &ev : c->kdev) (void)hipEventDestroy(ev);
     if (c->pin_ctrl) (void)hipHostFree(c->pin_ctrl);
     if (c->pin_rec) (void)hipHostFree(c->pin_rec);
+    if (c->pin_area) (void)hipHostFree(c->pin_area);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -384,6 +388,10 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if ((rc = dev_upload(c, &d.room_idx, room_idx.data(), room_idx.size()))) return rc;
     if ((rc = dev_upload(c, &d.room_bld, pop->room_building, R))) return rc;
     if ((rc = dev_upload(c, &d.bld_type, pop->building_type, B))) return rc;
+    // the per-area read-backs: 4 B per building, and the count table of esim_area_census
+    if ((rc = dev_upload(c, &d.bld_area, pop->building_area, B))) return rc;
+    d.n_areas = pop->n_areas;
+    if ((rc = dev_alloc(c, &c->area_cnt, (size_t)pop->n_areas * 5u))) return rc;
     uint32_t *cnt = nullptr;
     const size_t per_parity = (size_t)B + R + n_routes;
     if ((rc = dev_alloc(c, &cnt, MARK_SLOTS * per_parity))) return rc;
@@ -578,6 +586,12 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
         c->pin_rec = nullptr; c->pin_rec_n = 0;
         HIP_TRY(c, hipHostMalloc((void **)&c->pin_rec, sizeof(esim_step_result) * ((size_t)c->P.max_steps + 1), hipHostMallocDefault));
         c->pin_rec_n = (size_t)c->P.max_steps + 1;
+    }
+    if (c->pin_area_n < (size_t)pop->n_areas * 5u) {
+        if (c->pin_area) (void)hipHostFree(c->pin_area);
+        c->pin_area = nullptr; c->pin_area_n = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->pin_area, sizeof(uint32_t) * std::max<size_t>(1, (size_t)pop->n_areas * 5u), hipHostMallocDefault));
+        c->pin_area_n = (size_t)pop->n_areas * 5u;
     }
     c->grid_citizens = grid_for(N, TPB, 2048);
     c->grid_infected = 1024;
@@ -1793,6 +1807,97 @@ extern "C" int esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_download_exposure_log: ") + hipGetErrorString(e));
     for (uint32_t s = 1; s <= t_done; ++s)
         for (uint32_t i = off[s - 1u]; i < off[s] && i - first < n; ++i) step[i - first] = s;
+    return ESIM_OK;
+}
+
+// ---- per-Output-Area read-backs ----------------------------------------------------------------------------------------
+extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!counts || (where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME)) return fail(c, ESIM_EINVAL, "esim_area_census: null output or unknown `where`");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_census: no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    const size_t n_out = (size_t)d.n_areas * 5u;
+    // stretches of whole workgroup passes, about 8192 of them at most: short enough to stay inside the LDS window of areas
+    const uint32_t per_block = (uint32_t)std::max<uint64_t>(4096u, (((uint64_t)d.n + 8191u) / 8192u + TPB - 1u) / TPB * TPB);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1u, ((uint64_t)d.n + per_block - 1u) / per_block);
+    HIP_TRY(c, hipMemsetAsync(c->area_cnt, 0, sizeof(uint32_t) * std::max<size_t>(1, n_out), c->stream));
+    hipLaunchKernelGGL(k_area_census, dim3(grid), dim3(TPB), 0, c->stream, d, where == ESIM_AREA_HOME ? 1 : 0, per_block, c->area_cnt);
+    if (n_out) HIP_TRY(c, hipMemcpyAsync(c->pin_area, c->area_cnt, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, c->stream));
+    Ctrl h;
+    const int rc = read_ctrl(c, &h);                              // (the one wait: the table is in the mirror behind it)
+    if (rc) return rc;
+    std::memcpy(counts, c->pin_area, sizeof(uint32_t) * n_out);
+    return ctrl_error(c, h);
+}
+
+extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!out || (what != ESIM_SERIES_INFECTED && what != ESIM_SERIES_EXPOSURES) || stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_area_series: null output, unknown `what`, stride 0 or no rows");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_series: no population uploaded");
+    const uint32_t t_done = c->host_t - 1u;                       // steps run so far
+    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
+        return fail(c, ESIM_ERANGE, "esim_area_series: rows outside the steps run so far");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    Ctrl h;
+    int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
+    // the at-work bit of every step run, as the schedule (citizen.rs:176-206) produced it: the arm of step s runs iff no
+    // lockdown was in force, i.e. the record of step s - 1 has none
+    std::vector<esim_step_result> rec((size_t)t_done + 1u);
+    HIP_TRY(c, hipMemcpy(rec.data() + 1, d.records + 1, sizeof(esim_step_result) * t_done, hipMemcpyDeviceToHost));
+    std::vector<uint8_t> aw((size_t)t_done + 1u, 0);
+    std::vector<uint32_t> tog;
+    uint32_t trigger = 0, t_all = 0xFFFFFFFFu;
+    for (uint32_t s = 1; s <= t_done; ++s) {
+        uint8_t cur = aw[s - 1u];
+        if (s == 1u || !rec[s - 1u].lockdown) {
+            const uint32_t hr = s % 24u;
+            if (hr == c->P.start_hour) cur = 1; else if (hr == c->P.end_hour) cur = 0;
+        }
+        aw[s] = cur;
+        if (cur != aw[s - 1u]) tog.push_back(s);
+        if (!trigger && rec[s].vaccination_active) trigger = s;
+        if (trigger && t_all == 0xFFFFFFFFu && rec[s].eligible_count <= c->P.vaccination_rate) t_all = s;
+    }
+    const bool replay = what == ESIM_SERIES_INFECTED && trigger != 0u;
+    if (replay && d.n_global != d.n)
+        return fail(c, ESIM_ESTATE, "esim_area_series: the Infected rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
+    uint8_t *d_aw = nullptr; uint32_t *d_tog = nullptr, *d_vax = nullptr, *d_out = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_aw); (void)hipFree(d_tog); (void)hipFree(d_vax); (void)hipFree(d_out); };
+    const size_t out_words = ((size_t)n_rows + 1u) * d.n_areas;
+    if (hipMalloc(&d_aw, aw.size()) != hipSuccess || hipMalloc(&d_tog, sizeof(uint32_t) * std::max<size_t>(1, tog.size())) != hipSuccess ||
+        hipMalloc(&d_out, sizeof(uint32_t) * std::max<size_t>(1, out_words)) != hipSuccess ||
+        (replay && hipMalloc(&d_vax, sizeof(uint32_t) * std::max<size_t>(1, d.n)) != hipSuccess)) {
+        cleanup(); (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, "esim_area_series: no device memory for the rows (ask for fewer)");
+    }
+    hipError_t e = hipMemcpyAsync(d_aw, aw.data(), aw.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !tog.empty()) e = hipMemcpyAsync(d_tog, tog.data(), sizeof(uint32_t) * tog.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(uint32_t) * out_words, c->stream);
+    if (e == hipSuccess && replay) {
+        e = hipMemsetAsync(d_vax, 0xFF, sizeof(uint32_t) * (size_t)d.n, c->stream);
+        if (e == hipSuccess)
+            hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(t_done - trigger + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, d, trigger, t_done, d_vax);
+    }
+    if (e == hipSuccess) {
+        AreaSeries q;
+        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done;
+        q.n_tog = (uint32_t)tog.size(); q.t_all = t_all; q.at_work = d_aw; q.tog = d_tog; q.vax_of = d_vax; q.out = d_out;
+        hipLaunchKernelGGL(k_area_series, dim3(grid_for(h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, h.log_len);
+        if (what == ESIM_SERIES_INFECTED)
+            hipLaunchKernelGGL(k_area_prefix, dim3(grid_for(d.n_areas, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d_out, n_rows, d.n_areas);
+        e = hipStreamSynchronize(c->stream);                      // (the host vectors above are done with here, too)
+    } else (void)hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint32_t) * (size_t)n_rows * d.n_areas, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_area_series: ") + hipGetErrorString(e));
     return ESIM_OK;
 }
 

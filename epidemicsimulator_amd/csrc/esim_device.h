@@ -270,6 +270,9 @@ struct Dev {
 #endif
     uint32_t xf_n;                      // steps buffer F covers (min(FREE_MAX, exposed_time + 1)); word xf[xf_n]: shards whose
                                         // chunk does not fit the one-pass form
+    // per-Output-Area read-backs (esim_kernels_area.h); no stepping kernel reads these
+    const uint32_t *bld_area;           // [n_bld] Output Area of each building
+    uint32_t n_areas;
 };
 
 // exchange buffer A: [0..4] census, [5] riders, then shared building counts, then shared room counts

@@ -26,3 +26,4 @@
 #include "esim_kernels_chunk.h"
 #include "esim_kernels_tiny.h"
 #include "esim_kernels_state.h"
+#include "esim_kernels_area.h"

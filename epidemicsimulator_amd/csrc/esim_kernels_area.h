@@ -1,0 +1,226 @@
+// esim_kernels_area.h -- per-Output-Area read-backs: the census by area as it stands (esim_area_census) and, after the
+// fact, per-area rows over the steps already run (esim_area_series).  Nothing here writes simulation state.
+#pragma once
+
+#define AREA_WINDOW 256u           // areas whose counters a workgroup of k_area_census keeps in LDS
+
+// counts[area * 5 + status] after the last completed step.  A workgroup takes a contiguous stretch of `per_block` citizens.
+// Citizens are normally home-sorted and buildings grouped by area, so a stretch sees few areas and neighbouring lanes
+// share one: a run of lanes with the same area is counted by its first lane (one ballot per status), into an LDS window
+// of AREA_WINDOW areas that starts at the area of the stretch's first citizen; keys outside the window (commuters at work,
+// a population in any other order) go to the global table directly.  The window is added to the global table at the end.
+__global__ __launch_bounds__(TPB) void k_area_census(Dev d, int home_only, uint32_t per_block, uint32_t *counts)
+{
+    __shared__ uint32_t win[AREA_WINDOW * 5u];
+    __shared__ uint32_t s_base;
+    const Ctrl *ctrl = d.ctrl;
+    const uint32_t t = ctrl->t - 1u;             // last completed step
+    const bool at_work = !home_only && ctrl->at_work != 0u;
+    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
+    const uint64_t hi = lo + per_block < (uint64_t)d.n ? lo + per_block : (uint64_t)d.n;
+    for (uint32_t i = threadIdx.x; i < AREA_WINDOW * 5u; i += TPB) win[i] = 0u;
+    if (threadIdx.x == 0) s_base = lo < hi ? d.bld_area[d.home[lo]] : 0u;
+    __syncthreads();
+    const uint32_t base = s_base, lane = threadIdx.x & 63u;
+    for (uint64_t c0 = lo; c0 < hi; c0 += TPB) {                  // the same trip count for every lane of the workgroup
+        const uint64_t c = c0 + threadIdx.x;
+        const bool valid = c < hi;
+        uint32_t area = 0xFFFFFFFFu, st = 7u;
+        if (valid) {
+            const uint32_t w = d.cit[c];
+            st = status_of(CW_TE(w), t, d.exposed_time, d.infected_time);
+            area = d.bld_area[(at_work && (w & FL_HAS_WORK)) ? d.work[c] : d.home[c]];
+        }
+        const uint32_t prev = __shfl_up(area, 1, 64);
+        const bool head = valid && (lane == 0u || prev != area);
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+        const unsigned long long run = (above ? (above & (0ull - above)) - 1ull : ~0ull) & (~0ull << lane);   // this lane up to the next head
+#pragma unroll
+        for (uint32_t s = 0; s < 5u; ++s) {
+            const unsigned long long m = __ballot(st == s) & run;  // (lanes without a citizen have st = 7)
+            if (head && m) {
+                const uint32_t a = area - base;
+                if (a < AREA_WINDOW) atomicAdd(&win[a * 5u + s], (uint32_t)__popcll(m));
+                else atomicAdd(&counts[(size_t)area * 5u + s], (uint32_t)__popcll(m));
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < AREA_WINDOW * 5u; i += TPB) {
+        const uint32_t v = win[i];
+        if (v) atomicAdd(&counts[(size_t)(base + i / 5u) * 5u + i % 5u], v);   // (only areas that were seen have a count)
+    }
+}
+
+// ---- esim_area_series -------------------------------------------------------------------------------------------------
+// What the host derives from the records and hands to the kernels: where everybody with a work place stands after the
+// schedule arm of every step run so far, and the steps at which that changes.
+struct AreaSeries {
+    uint32_t what, first, n_rows, stride;
+    uint32_t t_done;                // steps run so far
+    uint32_t n_tog;
+    uint32_t t_all;                 // first step that vaccinated the whole eligible set (0xFFFFFFFF: none)
+    const uint8_t *at_work;         // [t_done + 1]
+    const uint32_t *tog;            // [n_tog] steps s with at_work[s] != at_work[s - 1], ascending
+    const uint32_t *vax_of;         // [n] step at whose end a citizen was set Vaccinated (k_area_vax_replay), or nullptr
+    uint32_t *out;                  // [n_rows + 1][n_areas]
+};
+
+// The exposure step (biased) of log entry i from its position: the entries of step k are [log_off[k], log_off[k + 1]).
+// (The citizen word no longer holds it once the citizen has been vaccinated.)
+__device__ __forceinline__ uint32_t log_te(const Dev &d, uint32_t i, uint32_t k_max)
+{
+    uint32_t lo = 0u, hi = k_max;                                 // the largest k <= k_max with log_off[k] <= i
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (d.log_off[mid] <= i) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+// A citizen stands in `area` during the steps [p, e], first <= p: +1 at the first row inside, -1 behind the last one.
+__device__ __forceinline__ void rows_add(const AreaSeries &q, uint32_t n_areas, uint32_t p, uint32_t e, uint32_t area)
+{
+    if (e < p) return;
+    const uint64_t i_lo = ((uint64_t)(p - q.first) + q.stride - 1u) / q.stride;
+    uint64_t i_hi = (uint64_t)(e - q.first) / q.stride;
+    if (i_lo >= q.n_rows) return;
+    if (i_hi >= q.n_rows) i_hi = q.n_rows - 1u;
+    if (i_lo > i_hi) return;
+    atomicAdd(&q.out[i_lo * n_areas + area], 1u);
+    atomicSub(&q.out[(i_hi + 1u) * n_areas + area], 1u);
+}
+
+// A lane per exposure-log entry (the seeds are in the log).  EXPOSURES: one add at (row of the exposure step, area at
+// that step).  INFECTED: the citizen is Infected in steps te + exposed_time + 1 .. te + exposed_time + 1 + infected_time
+// (status_of), or until the step before the one at whose end it was vaccinated; its area changes only where the at-work
+// bit does, and only if it works outside its home area: +-1 at the ends of every constant piece, summed by k_area_prefix.
+__global__ __launch_bounds__(TPB) void k_area_series(Dev d, AreaSeries q, uint32_t log_len)
+{
+    for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < log_len; i += gridDim.x * TPB) {
+        const uint32_t c = d.log[i], w = d.cit[c];
+        const int ts = (int)log_te(d, i, q.t_done + TE_BIAS) - (int)TE_BIAS;   // exposure step; seeds: -(exposed_time + 1)
+        const bool commuter = (w & FL_HAS_WORK) && !(w & FL_SAME_AREA);
+        const uint32_t a_home = d.bld_area[d.home[c]];
+        const uint32_t a_work = commuter ? d.bld_area[d.work[c]] : a_home;
+        if (q.what == ESIM_SERIES_EXPOSURES) {
+            if ((w & CW_BUS_EXPOSED) || ts < (int)q.first || ts > (int)q.t_done) continue;
+            const uint64_t row = (uint64_t)((uint32_t)ts - q.first) / q.stride;
+            if (row < q.n_rows) atomicAdd(&q.out[row * d.n_areas + (q.at_work[ts] ? a_work : a_home)], 1u);
+            continue;
+        }
+        int p = ts + (int)d.exposed_time + 1, e = p + (int)d.infected_time;
+        if (CW_TE(w) == TE_VACCINATED) {
+            uint32_t v = q.vax_of ? q.vax_of[c] : 0xFFFFFFFFu;
+            if (q.t_all < v) v = q.t_all;
+            if (v != 0xFFFFFFFFu && (int)v - 1 < e) e = (int)v - 1;
+        }
+        if (e > (int)q.t_done) e = (int)q.t_done;
+        if (p < (int)q.first) p = (int)q.first;
+        if (e < p) continue;
+        if (!commuter) { rows_add(q, d.n_areas, (uint32_t)p, (uint32_t)e, a_home); continue; }
+        uint32_t k = 0u, k_hi = q.n_tog;                          // the first change of the at-work bit behind step p
+        while (k < k_hi) { const uint32_t mid = (k + k_hi) >> 1; if (q.tog[mid] > (uint32_t)p) k_hi = mid; else k = mid + 1u; }
+        for (uint32_t s = (uint32_t)p;;) {
+            const uint32_t nxt = k < q.n_tog ? q.tog[k] : 0xFFFFFFFFu;
+            const uint32_t pe = nxt - 1u < (uint32_t)e ? nxt - 1u : (uint32_t)e;
+            rows_add(q, d.n_areas, s, pe, q.at_work[s] ? a_work : a_home);
+            if (pe >= (uint32_t)e) break;
+            s = nxt; ++k;
+        }
+    }
+}
+
+// Difference rows to counts: a lane per area walks down its column.
+__global__ __launch_bounds__(TPB) void k_area_prefix(uint32_t *out, uint32_t n_rows, uint32_t n_areas)
+{
+    const uint32_t a = blockIdx.x * TPB + threadIdx.x;
+    if (a >= n_areas) return;
+    uint32_t acc = 0u;
+    for (uint32_t r = 0; r < n_rows; ++r) { acc += out[(size_t)r * n_areas + a]; out[(size_t)r * n_areas + a] = acc; }
+}
+
+// Was the citizen a live vaccination candidate at the end of step t (eligible(), on the word as it stood THEN)?  A word
+// that is Vaccinated now belonged to the eligible set from the trigger step on: only members are vaccinated, nobody
+// Vaccinated is exposed, and the set never drops a vaccinated member (Q10).
+__device__ __forceinline__ bool was_eligible(uint32_t w, uint32_t t, uint32_t trigger)
+{
+    const uint32_t te = CW_TE(w);
+    if (te == TE_SUSCEPTIBLE || te == TE_VACCINATED) return true;
+    if (te >= TE_RECOVERED) return false;
+    if (te > t + TE_BIAS) return true;                            // exposed later: Susceptible at step t
+    return te > trigger + TE_BIAS && !(w & CW_BUS_EXPOSED);
+}
+
+// The citizen word does not keep the step of a vaccination, and somebody Exposed or Infected can be vaccinated
+// (simulator.rs:551).  The choice of simulator.rs:524-553 is a pure function of the step and of the eligible set, so it is
+// walked again, a workgroup per step, exactly as finish_phase walks it: the first `vaccination_rate` distinct live
+// candidates in candidate order.  vax_of[c] = the earliest step that chose c, for the citizens that are Vaccinated now.
+// Steps that vaccinated the whole set (eligible_count <= rate) are the caller's (AreaSeries::t_all).  One shard only.
+struct AreaVaxShared {
+    uint32_t tab_key[VACC_TABLE];
+    uint32_t tab_idx[VACC_TABLE];
+    uint32_t wsum[FIN_TPB / 64];
+    uint32_t s_total;
+};
+
+__global__ __launch_bounds__(FIN_TPB) void k_area_vax_replay(Dev d, uint32_t trigger, uint32_t t_done, uint32_t *vax_of)
+{
+    __shared__ AreaVaxShared sm;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t k = d.vaccination_rate;
+    for (uint32_t t = trigger + blockIdx.x; t <= t_done; t += gridDim.x) {
+        if (d.records[t].eligible_count <= k) continue;
+        for (uint32_t i = tid; i < VACC_TABLE; i += FIN_TPB) { sm.tab_key[i] = 0xFFFFFFFFu; sm.tab_idx[i] = 0xFFFFFFFFu; }
+        __syncthreads();
+        uint32_t already = 0;
+        for (uint32_t base = 0; already < k; base += VACC_BATCH) {
+            uint32_t j[4], slot[4]; bool live[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t i = base + tid * 4u + q;
+                j[q] = vacc_candidate(d, i, t);
+                live[q] = j[q] < d.n && was_eligible(d.cit[j[q]], t, trigger);
+                slot[q] = 0;
+                if (live[q]) {
+                    uint32_t sl = (j[q] * 2654435761u) >> 18;        // 14 bits
+                    for (;;) {
+                        const uint32_t old = atomicCAS(&sm.tab_key[sl], 0xFFFFFFFFu, j[q]);
+                        if (old == 0xFFFFFFFFu || old == j[q]) break;
+                        sl = (sl + 1u) & (VACC_TABLE - 1u);
+                    }
+                    atomicMin(&sm.tab_idx[sl], i);
+                    slot[q] = sl;
+                }
+            }
+            __syncthreads();
+            bool first[4]; uint32_t mine = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                first[q] = live[q] && sm.tab_idx[slot[q]] == base + tid * 4u + q;
+                mine += first[q];
+            }
+            uint32_t incl = mine;                                    // scan of `mine` in candidate order
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o, 64); if (lane >= (uint32_t)o) incl += v; }
+            if (lane == 63) sm.wsum[wv] = incl;
+            __syncthreads();
+            if (tid == 0) { uint32_t a = 0; for (uint32_t w = 0; w < FIN_TPB / 64; ++w) { const uint32_t v = sm.wsum[w]; sm.wsum[w] = a; a += v; } sm.s_total = a; }
+            __syncthreads();
+            uint32_t pos = already + sm.wsum[wv] + incl - mine;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (first[q]) {
+                    if (pos < k && CW_TE(d.cit[j[q]]) == TE_VACCINATED) atomicMin(&vax_of[j[q]], t);
+                    pos++;
+                }
+            }
+            const uint32_t got = sm.s_total;
+            __syncthreads();
+            already += got < k - already ? got : k - already;
+            if (base >= (1u << 26)) break;                           // (the run itself raised ESIM_ERANGE there)
+        }
+        __syncthreads();
+    }
+}

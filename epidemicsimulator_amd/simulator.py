@@ -317,6 +317,26 @@ class Simulator:
         area = self.population.building_area[st["current_building"]]
         return np.bincount(area[st["status"] == _lib.INFECTED], minlength=self.population.n_areas)
 
+    def area_census(self, where="current"):
+        """uint32 [n_areas, 5]: citizens per Output Area and DiseaseStatus after the last completed step, counted on the
+        device (esim_area_census).  where: "current" (the area of the building a citizen stands in) or "home"."""
+        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
+        out = np.zeros((self.population.n_areas, 5), np.uint32)
+        _lib.check(self.lib.esim_area_census(self._ctx, int(code), out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
+    def area_series(self, what, first_step=1, n_rows=None, stride=1):
+        """uint32 [n_rows, n_areas] over the steps already run (esim_area_series): row i is step first_step + i * stride.
+        what: "infected" (citizens Infected after that step, by the area they stand in) or "exposures" (building exposures
+        of the `stride` steps from that one on, by area).  n_rows=None: up to the last step run."""
+        code = {"infected": _lib.SERIES_INFECTED, "exposures": _lib.SERIES_EXPOSURES}.get(what, what)
+        if n_rows is None:
+            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
+        out = np.zeros((max(0, int(n_rows)), self.population.n_areas), np.uint32)
+        _lib.check(self.lib.esim_area_series(self._ctx, int(code), int(first_step), int(n_rows), int(stride),
+                                             out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

@@ -223,6 +223,34 @@ int  esim_download_state(esim_ctx *ctx, uint8_t *status, uint16_t *timer,
  * in at that step (simulator.rs:324 only exposes members whose current area is the building's).  Order inside a time
  * step is unspecified.  *n_out = number of exposures; ESIM_ERANGE (with *n_out set) when cap is too small. */
 int  esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint32_t *step, uint8_t *on_bus, uint32_t cap, uint32_t *n_out);
+/* The census by Output Area, counted on the device -- what visualisation draws from output_areas[..].citizens
+ * (run/src/main.rs:246-259, visualisation/src/citizen_connections.rs:40-62) without a per-citizen download.
+ * counts[area * 5 + status], status = ESIM_SUSCEPTIBLE .. ESIM_VACCINATED, after the last completed step (after
+ * esim_reset: everybody Susceptible, the seeds Infected at home).  ESIM_AREA_CURRENT: the Output Area of the building the
+ * citizen stands in (what esim_download_state reports as current_building, through building_area); ESIM_AREA_HOME: the
+ * area of its household.  Leaves the simulation state as it is.  A sharded context counts its own citizens in its own
+ * population's area indices and starts no collective. */
+enum { ESIM_AREA_CURRENT = 0, ESIM_AREA_HOME = 1 };
+int  esim_area_census(esim_ctx *ctx, int where, uint32_t *counts /* [n_areas * 5] */);
+/* The same picture for the steps already run, derived after the fact from what the device holds (exposure log, citizen
+ * words, the records' lockdown flags): a run that never asks pays nothing.  Row i describes step
+ * s_i = first_step + i * stride (1-based, s_i <= steps run so far), out[i * n_areas + area]:
+ *   ESIM_SERIES_INFECTED   citizens Infected after step s_i, by the area they stand in then -- column ESIM_INFECTED of
+ *                          what esim_area_census(ESIM_AREA_CURRENT) would have returned had it been called after step s_i
+ *                          (a citizen set Vaccinated at the end of a step is not Infected after it; the record's `infected`
+ *                          is the census before that, simulator.rs:178);
+ *   ESIM_SERIES_EXPOSURES  building exposures (not public transport) of steps [s_i, s_i + stride), clipped to the steps
+ *                          run, credited to the area the citizen stands in at that step (statistics.rs:186-190,
+ *                          simulator.rs:324) -- with stride 1, the dense form of exposures.json's "OutputArea" series
+ *                          (statistics.rs:119-136).
+ * ESIM_ERANGE: first_step == 0 or the last row's step beyond the steps run; ESIM_ENOMEM: no device memory for the rows
+ * (ask for fewer).  The step at which somebody was vaccinated is not kept per citizen: under a vaccination programme the
+ * Infected rows walk the choice of simulator.rs:524-553 again for the steps run (4 B per citizen of temporary device
+ * memory); a sharded context cannot (the choice depends on the other shards' citizens) and returns ESIM_ESTATE for the
+ * Infected rows once a programme has run.  Otherwise a sharded context describes its own citizens, as above. */
+enum { ESIM_SERIES_INFECTED = 0, ESIM_SERIES_EXPOSURES = 1 };
+int  esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                      uint32_t *out /* [n_rows * n_areas] */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
