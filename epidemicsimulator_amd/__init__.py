@@ -8,6 +8,7 @@ from . import _lib
 from ._lib import EsimError, default_params
 from .population import Population, PRESETS
 from .simulator import Simulator, StatisticsRecorder, RECORD_DTYPE
+from .ensemble import Ensemble, EnsembleResult
 
-__all__ = ["Simulator", "StatisticsRecorder", "Population", "PRESETS", "EsimError",
+__all__ = ["Simulator", "StatisticsRecorder", "Ensemble", "EnsembleResult", "Population", "PRESETS", "EsimError",
            "default_params", "RECORD_DTYPE", "_lib"]

@@ -91,6 +91,16 @@ struct esim_ctx_impl {
     // esim_area_census: the count table on the device and its pinned mirror, [n_areas * 5]
     uint32_t *area_cnt = nullptr;
     uint32_t *pin_area = nullptr; size_t pin_area_n = 0;
+    // esim_restart: the distinct seeds on the device, the capacity of the record log (max_steps at esim_create), and what the call
+    // copies to the device -- control block and threshold LUT -- in pinned memory, with an event behind those two copies
+    uint32_t *seeds_dev = nullptr;
+    uint32_t cap_steps = 0;
+    struct RestartStage { Ctrl h; uint64_t lut[512]; } *pin_restart = nullptr;
+    hipEvent_t restart_ev = nullptr; bool restart_ev_used = false;
+    // esim_ensemble_*: accumulators over the members of an ensemble, [n_areas] each (nullptr before the first esim_ensemble_begin)
+    uint32_t *ens_hit = nullptr, *ens_members = nullptr;
+    unsigned long long *ens_sum = nullptr, *ens_sumsq = nullptr;
+    int ens_where = ESIM_AREA_HOME; uint32_t ens_mask = 0, ens_min = 0;
 };
 
 #define CTX(c) (reinterpret_cast<esim_ctx_impl *>(c))
@@ -189,25 +199,49 @@ extern "C" int esim_threshold_lut(const esim_params *p, uint64_t out[512])
     return ESIM_OK;
 }
 
-extern "C" int esim_create(const esim_params *p, esim_ctx **out)
+namespace {
+// What esim_create and esim_restart accept as parameters (the device ordinal and the record log's capacity apart).
+int check_params(esim_ctx_impl *c, const esim_params *p, const std::string &who)
 {
-    if (!p || !out) return fail(nullptr, ESIM_EINVAL, "esim_create: null argument");
     if (p->exposed_time + p->infected_time + 2u > TE_BIAS)
-        return fail(nullptr, ESIM_ERANGE, "esim_create: exposed_time + infected_time + 2 exceeds the state encoding (512)");
+        return fail(c, ESIM_ERANGE, who + ": exposed_time + infected_time + 2 exceeds the state encoding (512)");
     if (p->vaccination_rate > VACC_MAX_RATE)
-        return fail(nullptr, ESIM_ERANGE, "esim_create: vaccination_rate above 8192 is not supported");
+        return fail(c, ESIM_ERANGE, who + ": vaccination_rate above 8192 is not supported");
     if (p->bus_capacity == 0 || p->start_hour == 0 || p->end_hour == 0 || p->start_hour > 24 || p->end_hour > 24)
-        return fail(nullptr, ESIM_EINVAL, "esim_create: bad bus_capacity / working hours");
+        return fail(c, ESIM_EINVAL, who + ": bad bus_capacity / working hours");
     {
         // the schedule is evaluated once for everybody, which needs the four arms of citizen.rs:177-205 to
         // fall on four different hours
         const uint32_t h[4] = { (p->start_hour + 23u) % 24u, p->start_hour % 24u, (p->end_hour + 23u) % 24u, p->end_hour % 24u };
         for (int a = 0; a < 4; ++a) for (int b = a + 1; b < 4; ++b)
-            if (h[a] == h[b]) return fail(nullptr, ESIM_EINVAL, "esim_create: start_hour-1, start_hour, end_hour-1, end_hour must be distinct");
-        if (p->start_hour > 23 || p->end_hour > 23) return fail(nullptr, ESIM_EINVAL, "esim_create: working hours must be in 1..23");
+            if (h[a] == h[b]) return fail(c, ESIM_EINVAL, who + ": start_hour-1, start_hour, end_hour-1, end_hour must be distinct");
+        if (p->start_hour > 23 || p->end_hour > 23) return fail(c, ESIM_EINVAL, who + ": working hours must be in 1..23");
     }
     if (p->max_steps == 0 || p->max_steps > ESIM_MAX_STEP)
-        return fail(nullptr, ESIM_ERANGE, "esim_create: max_steps must be in 1..7600");
+        return fail(c, ESIM_ERANGE, who + ": max_steps must be in 1..7600");
+    return ESIM_OK;
+}
+
+// Everything in Dev that is derived from the parameters.
+void params_to_dev(esim_ctx_impl *c)
+{
+    Dev &d = c->d;
+    d.exposed_time = c->P.exposed_time; d.infected_time = c->P.infected_time;
+    d.vaccination_rate = c->P.vaccination_rate; d.bus_capacity = c->P.bus_capacity;
+    d.start_hour = c->P.start_hour; d.end_hour = c->P.end_hour;
+    d.seed_lo = (uint32_t)c->P.seed; d.seed_hi = (uint32_t)(c->P.seed >> 32);
+    d.thr_lockdown = c->P.lockdown_threshold; d.thr_vacc = c->P.vaccination_threshold;
+    d.thr_mask_pt = c->P.mask_pt_threshold; d.thr_mask_all = c->P.mask_everywhere_threshold;
+    d.max_steps = c->P.max_steps;
+    c->xf_n =std::min<uint32_t>(FREE_MAX, c->P.exposed_time + 1u);
+    d.xf_n = (uint32_t)c->xf_n;
+}
+}  // namespace
+
+extern "C" int esim_create(const esim_params *p, esim_ctx **out)
+{
+    if (!p || !out) return fail(nullptr, ESIM_EINVAL, "esim_create: null argument");
+    if (int rc = check_params(nullptr, p, "esim_create")) return rc;
     int n_dev = 0;
     hipError_t e = hipGetDeviceCount(&n_dev);
     if (e != hipSuccess || n_dev <= 0)
@@ -217,6 +251,7 @@ extern "C" int esim_create(const esim_params *p, esim_ctx **out)
     if (e != hipSuccess) return fail(nullptr, ESIM_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
     esim_ctx_impl *c = new esim_ctx_impl();
     c->P = *p;
+    c->cap_steps = p->max_steps;
     if (const char *e = std::getenv("ESIM_COMM_TIMEOUT_S")) { const double v = std::atof(e); if (v > 0.0) c->comm_timeout_s = v; }
     std::memset(&c->d, 0, sizeof c->d);
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -243,6 +278,8 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     if (c->pin_ctrl) (void)hipHostFree(c->pin_ctrl);
     if (c->pin_rec) (void)hipHostFree(c->pin_rec);
     if (c->pin_area) (void)hipHostFree(c->pin_area);
+    if (c->pin_restart) (void)hipHostFree(c->pin_restart);
+    if (c->restart_ev) (void)hipEventDestroy(c->restart_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -369,6 +406,8 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     c->comm_fn = nullptr; c->comm_user = nullptr; c->comm_rank = 0; c->comm_world = 1;
     c->xr = nullptr; c->xr_n = 0;
     free_device(c);
+    c->seeds_dev = nullptr;                                        // (freed with the rest; the ensemble accumulators go with the population)
+    c->ens_hit = c->ens_members = nullptr; c->ens_sum = c->ens_sumsq = nullptr;
     Dev &d = c->d;
     std::memset(&d, 0, sizeof d);
     d.n = N; d.n_global = n_global; d.id_base = pop->citizen_id_base; d.n_bld = B; d.n_room = R;
@@ -397,7 +436,7 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if ((rc = dev_alloc(c, &cnt, MARK_SLOTS * per_parity))) return rc;
     c->cnt_base = cnt;
     c->cnt_bytes = sizeof(uint32_t) * MARK_SLOTS * per_parity;
-    if ((rc = dev_alloc(c, &d.exp_step, 2 * ((size_t)c->P.max_steps + 2)))) return rc;
+    if ((rc = dev_alloc(c, &d.exp_step, 2 * ((size_t)c->cap_steps + 2)))) return rc;
     if ((rc = dev_alloc(c, &d.exp_part, (size_t)EXP_ROWS * 2u * FREE_MAX))) return rc;
     HIP_TRY(c, hipMemset(d.exp_part, 0, sizeof(uint32_t) * EXP_ROWS * 2u * FREE_MAX));
     if ((rc = dev_alloc(c, &d.dec, FREE_MAX + 1))) return rc;
@@ -520,11 +559,17 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if ((rc = dev_alloc(c, &d.hist, TE_SLOTS))) return rc;
     if ((rc = dev_alloc(c, &d.log, (size_t)N + 1))) return rc;
     if ((rc = dev_alloc(c, &d.log_off, TE_SLOTS + 1))) return rc;
+    {
+        // the distinct seeds, for esim_restart (which writes their words and the head of the log from this array)
+        const uint32_t *sd = nullptr;
+        if ((rc = dev_upload(c, &sd, c->init_log.data(), c->init_log.size()))) return rc;
+        c->seeds_dev = const_cast<uint32_t *>(sd);
+    }
     uint64_t lut[512];
     esim_threshold_lut(&c->P, lut);
     if ((rc = dev_upload(c, &d.thr, lut, 512))) return rc;
     if ((rc = dev_alloc(c, &d.ctrl, 1))) return rc;
-    if ((rc = dev_alloc(c, &d.records, (size_t)c->P.max_steps + 1))) return rc;
+    if ((rc = dev_alloc(c, &d.records, (size_t)c->cap_steps + 1))) return rc;
     if ((rc = dev_upload(c, &d.route_off, route_off.data(), route_off.size()))) return rc;
     if ((rc = dev_upload(c, &d.route_riders, riders.data(), riders.size()))) return rc;
     if ((rc = dev_upload(c, &d.route_of, route_of.data(), N))) return rc;
@@ -533,13 +578,7 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if ((rc = dev_alloc(c, &d.bus_idx, big_scratch))) return rc;
     if ((rc = dev_alloc(c, &d.bus_cnt, big_scratch))) return rc;
     if ((rc = dev_alloc(c, &d.bus_flag, big_scratch))) return rc;
-    d.exposed_time = c->P.exposed_time; d.infected_time = c->P.infected_time;
-    d.vaccination_rate = c->P.vaccination_rate; d.bus_capacity = c->P.bus_capacity;
-    d.start_hour = c->P.start_hour; d.end_hour = c->P.end_hour;
-    d.seed_lo = (uint32_t)c->P.seed; d.seed_hi = (uint32_t)(c->P.seed >> 32);
-    d.thr_lockdown = c->P.lockdown_threshold; d.thr_vacc = c->P.vaccination_threshold;
-    d.thr_mask_pt = c->P.mask_pt_threshold; d.thr_mask_all = c->P.mask_everywhere_threshold;
-    d.max_steps = c->P.max_steps;
+    params_to_dev(c);
     d.n_shards = sharded ? 2u : 1u;
     d.n_shared_bld = pop->n_shared_buildings; d.n_shared_room = pop->n_shared_rooms;
     if ((rc = dev_upload(c, &d.shared_bld, pop->shared_building_local, pop->n_shared_buildings))) return rc;
@@ -573,19 +612,19 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     c->xb_n = XB_HEADER + VACC_WINDOW / 32u;
     if ((rc = dev_alloc(c, &d.xa, c->xa_n))) return rc;
     if ((rc = dev_alloc(c, &d.xb, c->xb_n))) return rc;
-    c->xf_n = std::min<uint32_t>(FREE_MAX, c->P.exposed_time + 1u);
-    d.xf_n = (uint32_t)c->xf_n;
     if ((rc = dev_alloc(c, &d.xf, FREE_MAX + 1))) return rc;
     HIP_TRY(c, hipMemset(d.xf, 0, sizeof(uint32_t) * (FREE_MAX + 1)));
     HIP_TRY(c, hipMemset(d.xa, 0, sizeof(uint32_t) * c->xa_n));
     HIP_TRY(c, hipMemset(d.xb, 0, sizeof(uint32_t) * c->xb_n));
 
     if (!c->pin_ctrl) HIP_TRY(c, hipHostMalloc((void **)&c->pin_ctrl, sizeof(Ctrl), hipHostMallocDefault));
-    if (c->pin_rec_n < (size_t)c->P.max_steps + 1) {
+    if (!c->pin_restart) HIP_TRY(c, hipHostMalloc((void **)&c->pin_restart, sizeof(*c->pin_restart), hipHostMallocDefault));
+    if (!c->restart_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->restart_ev, hipEventDisableTiming));
+    if (c->pin_rec_n < (size_t)c->cap_steps + 1) {
         if (c->pin_rec) (void)hipHostFree(c->pin_rec);
         c->pin_rec = nullptr; c->pin_rec_n = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->pin_rec, sizeof(esim_step_result) * ((size_t)c->P.max_steps + 1), hipHostMallocDefault));
-        c->pin_rec_n = (size_t)c->P.max_steps + 1;
+        HIP_TRY(c, hipHostMalloc((void **)&c->pin_rec, sizeof(esim_step_result) * ((size_t)c->cap_steps + 1), hipHostMallocDefault));
+        c->pin_rec_n = (size_t)c->cap_steps + 1;
     }
     if (c->pin_area_n < (size_t)pop->n_areas * 5u) {
         if (c->pin_area) (void)hipHostFree(c->pin_area);
@@ -642,6 +681,60 @@ extern "C" int esim_reset(esim_ctx *ctx)
     c->stop_flag_dev = 0;
     c->pin_track = false;
     c->last_chunk_pairs = (uint32_t)c->init_log.size();
+    c->phase_s[0] = c->phase_s[1] = c->phase_s[2] = 0;
+    c->kev_used = 0;
+    c->small_ms = 0; c->small_steps = 0;
+    c->pkev_used = 0; c->pipe_steps = 0;
+    c->chunk_ms = 0; c->chunk_steps = 0; c->chunk_count = 0;
+    c->vax_chunk_steps = 0; c->vax_chunk_cuts = 0; c->elig_seen = false; c->repair_armed = false; c->quiet = false;
+    return ESIM_OK;
+}
+
+// esim_reset with new parameters and without the host: nothing here waits for the stream or copies anything proportional to
+// the population.  Host -> device go the control block and the threshold LUT (4.4 KB, from pinned memory); the citizen words,
+// the seeds' words, the census histogram and the log offsets are written by kernels, the rest is cleared or copied on the device.
+extern "C" int esim_restart(esim_ctx *ctx, const esim_params *p)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !p) return fail(c, ESIM_EINVAL, "esim_restart: null argument");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_restart: no population uploaded");
+    if (c->comm_world > 1) return fail(c, ESIM_ESTATE, "esim_restart: the context has a communicator of several ranks (the shards would have to agree on the parameters)");
+    if (int rc = check_params(c, p, "esim_restart")) return rc;
+    if (p->device != c->P.device) return fail(c, ESIM_EINVAL, "esim_restart: device must be the context's device");
+    if (p->max_steps > c->cap_steps) return fail(c, ESIM_ERANGE, "esim_restart: max_steps above the max_steps the context was created with (the record log's capacity)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    // the staging block is the source of the previous restart's two copies: they are long done unless restarts follow each
+    // other with nothing in between (then this waits for those copies, not for the stream)
+    if (c->restart_ev_used) HIP_TRY(c, hipEventSynchronize(c->restart_ev));
+    c->P = *p;
+    params_to_dev(c);
+    const Dev &d = c->d;
+    const uint32_t n_seeds = (uint32_t)c->init_log.size();
+    const uint32_t seed_te = TE_BIAS - (c->P.exposed_time + 1u);     // Infected(0) before step 1
+    for (uint32_t sc : c->init_log) c->init_state[sc] = CW_MAKE(seed_te, c->init_state[sc] & CW_FLAGS);   // (esim_reset's copy of the seeds' words)
+    Ctrl &h = c->pin_restart->h;
+    std::memset(&h, 0, sizeof h);
+    h.t = 1;
+    h.mask = ESIM_MASK_NONE;
+    h.n_susceptible = d.n - n_seeds;
+    h.log_len = n_seeds;
+    esim_threshold_lut(&c->P, c->pin_restart->lut);
+    HIP_TRY(c, hipMemcpyAsync(d.ctrl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(d.thr), c->pin_restart->lut, sizeof c->pin_restart->lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->restart_ev, c->stream));
+    c->restart_ev_used = true;
+    if (d.n) hipLaunchKernelGGL(k_restart_words, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, d.cit, d.n);
+    HIP_TRY(c, hipMemsetAsync(c->cnt_base, 0, c->cnt_bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.exp_step, 0, sizeof(uint32_t) * 2 * ((size_t)c->cap_steps + 2), c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.records, 0, sizeof(esim_step_result) * ((size_t)c->cap_steps + 1), c->stream));
+    hipLaunchKernelGGL(k_restart_books, dim3(grid_for(std::max<size_t>(TE_SLOTS + 1u, n_seeds), TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       d.cit, d.n, c->seeds_dev, n_seeds, seed_te, d.hist, d.log_off);
+    if (n_seeds) HIP_TRY(c, hipMemcpyAsync(d.log, c->seeds_dev, sizeof(uint32_t) * n_seeds, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->host_t = 1;
+    c->stop_flag_dev = 0;
+    c->pin_track = false; c->ctrl_fresh = false;
+    c->last_chunk_pairs = n_seeds;
     c->phase_s[0] = c->phase_s[1] = c->phase_s[2] = 0;
     c->kev_used = 0;
     c->small_ms = 0; c->small_steps = 0;
@@ -1811,13 +1904,10 @@ extern "C" int esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint
 }
 
 // ---- per-Output-Area read-backs ----------------------------------------------------------------------------------------
-extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
+namespace {
+// the count table of esim_area_census zeroed and counted on the context's stream (esim_ensemble_fold reads it where it is)
+int enqueue_area_census(esim_ctx_impl *c, int where)
 {
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c) return ESIM_EINVAL;
-    if (!counts || (where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME)) return fail(c, ESIM_EINVAL, "esim_area_census: null output or unknown `where`");
-    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_census: no population uploaded");
-    HIP_TRY(c, hipSetDevice(c->P.device));
     const Dev &d = c->d;
     const size_t n_out = (size_t)d.n_areas * 5u;
     // stretches of whole workgroup passes, about 8192 of them at most: short enough to stay inside the LDS window of areas
@@ -1825,11 +1915,81 @@ extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1u, ((uint64_t)d.n + per_block - 1u) / per_block);
     HIP_TRY(c, hipMemsetAsync(c->area_cnt, 0, sizeof(uint32_t) * std::max<size_t>(1, n_out), c->stream));
     hipLaunchKernelGGL(k_area_census, dim3(grid), dim3(TPB), 0, c->stream, d, where == ESIM_AREA_HOME ? 1 : 0, per_block, c->area_cnt);
+    return ESIM_OK;
+}
+}  // namespace
+
+extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!counts || (where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME)) return fail(c, ESIM_EINVAL, "esim_area_census: null output or unknown `where`");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_census: no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const size_t n_out = (size_t)c->d.n_areas * 5u;
+    if (int rc = enqueue_area_census(c, where)) return rc;
     if (n_out) HIP_TRY(c, hipMemcpyAsync(c->pin_area, c->area_cnt, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, c->stream));
     Ctrl h;
-    const int rc = read_ctrl(c, &h);                              // (the one wait: the table is in the mirror behind it)
-    if (rc) return rc;
+    if (int rc = read_ctrl(c, &h)) return rc;                     // (the one wait: the table is in the mirror behind it)
     std::memcpy(counts, c->pin_area, sizeof(uint32_t) * n_out);
+    return ctrl_error(c, h);
+}
+
+// ---- per-Output-Area accumulators over the members of an ensemble ------------------------------------------------------
+extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if ((where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME) || status_mask == 0u || (status_mask >> 5) != 0u)
+        return fail(c, ESIM_EINVAL, "esim_ensemble_begin: unknown `where`, or a status mask that is empty or names a status beyond ESIM_VACCINATED");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const size_t na = std::max<size_t>(1, c->d.n_areas);
+    if (!c->ens_hit) {
+        int rc;
+        uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
+        if ((rc = dev_alloc(c, &hit, na)) || (rc = dev_alloc(c, &sum, na)) || (rc = dev_alloc(c, &sq, na)) || (rc = dev_alloc(c, &mem, 1))) {
+            dev_free(c, hit); dev_free(c, sum); dev_free(c, sq); dev_free(c, mem);
+            return rc;
+        }
+        c->ens_hit = hit; c->ens_sum = sum; c->ens_sumsq = sq; c->ens_members = mem;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->ens_hit, 0, sizeof(uint32_t) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens_sum, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens_sumsq, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens_members, 0, sizeof(uint32_t), c->stream));
+    c->ens_where = where; c->ens_mask = status_mask; c->ens_min = min_cases;
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_fold(esim_ctx *ctx)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!c->uploaded || !c->ens_hit) return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    int rc;
+    if ((rc = enqueue_area_census(c, c->ens_where))) return rc;
+    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->d.n_areas, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       c->area_cnt, c->d.n_areas, c->ens_mask, c->ens_min, c->ens_hit, c->ens_sum, c->ens_sumsq, c->ens_members);
+    HIP_TRY(c, hipGetLastError());
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!c->uploaded || !c->ens_hit) return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h;
+    int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
+    const size_t na = c->d.n_areas;
+    if (members) HIP_TRY(c, hipMemcpy(members, c->ens_members, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hit && na) HIP_TRY(c, hipMemcpy(hit, c->ens_hit, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
+    if (sum && na) HIP_TRY(c, hipMemcpy(sum, c->ens_sum, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
+    if (sumsq && na) HIP_TRY(c, hipMemcpy(sumsq, c->ens_sumsq, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
     return ctrl_error(c, h);
 }
 

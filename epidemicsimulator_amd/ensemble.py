@@ -1,0 +1,119 @@
+"""Ensembles of one uploaded population: many Philox seeds of one world, or the same world under several parameter sets,
+one member after another on ONE context (esim_restart), summarised per step on the host and per Output Area on the device
+(esim_ensemble_*).  The population is validated, hashed and uploaded once."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+
+from . import _lib
+from .simulator import RECORD_DTYPE, Simulator
+
+QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)           # the rows of ensemble_stats.json
+STAT_FIELDS = ("susceptible", "exposed", "infected", "recovered", "vaccinated", "exposures_building", "exposures_bus", "vaccinated_now")
+_EVENT_FIELDS = ("exposures_building", "exposures_bus", "vaccinated_now", "n_riders")   # what happens IN a step: zero in a step that did not run
+
+
+def pad_records(rec, n_steps):
+    """`rec` (the records of a member that stopped early, time steps 1..len(rec)) as n_steps rows: the rows behind the last
+    record carry its census and flags forward with time_step counting on, zero exposures, zero vaccinated_now and
+    disease_exists = 0 -- summaries over members stay defined for every step.  A member without any record pads with zeros."""
+    out = np.zeros(n_steps, RECORD_DTYPE)
+    k = min(len(rec), n_steps)
+    out[:k] = rec[:k]
+    if k < n_steps:
+        if k:
+            out[k:] = rec[k - 1]
+            for f in _EVENT_FIELDS:
+                out[f][k:] = 0
+        out["disease_exists"][k:] = 0
+        out["time_step"][k:] = np.arange(k + 1, n_steps + 1, dtype=np.uint32)
+    return out
+
+
+def area_summary(members, hit, total, sumsq):
+    """members, hit, mean = sum / members, var = population variance from sum and sumsq."""
+    m = int(members)
+    total, sumsq = np.asarray(total, np.float64), np.asarray(sumsq, np.float64)
+    mean = total / m if m else np.zeros_like(total)
+    var = np.maximum(sumsq / m - mean * mean, 0.0) if m else np.zeros_like(total)
+    return {"members": m, "hit": np.asarray(hit, np.uint32), "mean": mean, "var": var}
+
+
+class EnsembleResult:
+    def __init__(self, records, n_done, members, area=None, area_codes=None):
+        self.records = records            # structured [members, n_steps]
+        self.n_done = np.asarray(n_done, np.uint32)
+        self.members = list(members)      # the overrides of every member
+        self.area = area                  # area_summary(...) or None
+        self.area_codes = area_codes
+
+    def quantiles(self, field, qs):
+        """[len(qs), n_steps]: the quantiles of `field` over the members, per step."""
+        if self.records.shape[0] == 0:
+            return np.zeros((len(qs), self.records.shape[1]))
+        return np.quantile(self.records[field].astype(np.float64), list(qs), axis=0)
+
+    def mean(self, field):
+        if self.records.shape[0] == 0:
+            return np.zeros(self.records.shape[1])
+        return self.records[field].astype(np.float64).mean(axis=0)
+
+    def dump(self, directory):
+        """ensemble_stats.json: per field the mean and the 5/25/50/75/95 % rows over the members; ensemble_areas.json: hit, mean
+        and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index."""
+        os.makedirs(directory, exist_ok=True)
+        stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
+        for f in STAT_FIELDS:
+            q = self.quantiles(f, QUANTILES)
+            stats["fields"][f] = dict({"mean": self.mean(f).tolist()}, **{"q%02d" % round(100 * p): q[i].tolist() for i, p in enumerate(QUANTILES)})
+        with open(os.path.join(directory, "ensemble_stats.json"), "w") as fh:
+            json.dump(stats, fh)
+        doc = None
+        if self.area is not None:
+            a = self.area
+            key = (lambda i: self.area_codes[i]) if self.area_codes is not None else (lambda i: str(i))
+            doc = {"members": a["members"],
+                   "areas": {key(i): {"hit": int(a["hit"][i]), "mean": float(a["mean"][i]), "var": float(a["var"][i])} for i in range(len(a["hit"]))}}
+        with open(os.path.join(directory, "ensemble_areas.json"), "w") as fh:
+            json.dump(doc, fh)
+
+
+class Ensemble:
+    """Owns one Simulator; every member is a restart of it under the base parameters changed by the member's overrides."""
+
+    def __init__(self, population, params=None, area_codes=None):
+        self.simulator = Simulator(population, params, area_codes=area_codes)
+        self.area_codes = area_codes
+        self.base = _lib.Params()
+        C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
+
+    @staticmethod
+    def seeds(k, first=1):
+        return [{"seed": int(first) + i} for i in range(int(k))]
+
+    def run(self, members, n_steps, stop_when_done=False, area=None):
+        """members: iterable of override dicts (Ensemble.seeds); area: None, or the arguments of esim_ensemble_begin as a dict
+        (where, status_mask, min_cases).  Returns an EnsembleResult."""
+        sim = self.simulator
+        members = [dict(m) for m in members]
+        if area is not None:
+            sim.ensemble_begin(**area)
+        rows, n_done = [], []
+        for m in members:
+            sim.restart(self.base, **m)
+            rec = sim.run(n_steps, stop_when_done=stop_when_done)
+            if area is not None:
+                sim.ensemble_fold()
+            n_done.append(len(rec))
+            rows.append(pad_records(rec, n_steps))
+        records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
+        summary = None
+        if area is not None:
+            r = sim.ensemble_read()
+            summary = area_summary(r["members"], r["hit"], r["sum"], r["sumsq"])
+        return EnsembleResult(records, n_done, members, summary, self.area_codes)
+
+    def close(self):
+        self.simulator.close()

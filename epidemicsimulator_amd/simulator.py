@@ -199,6 +199,38 @@ class Simulator:
         self.statistics_recorder = StatisticsRecorder()
         self._steps = 0
 
+    def restart(self, params=None, **overrides):
+        """Back to step 0 under other parameters without a new upload (esim_restart): `params`, or the current parameters
+        changed by `overrides` (e.g. seed=7).  The initial state is rebuilt on the device; the call does not wait for it."""
+        p = _lib.Params()
+        C.memmove(C.byref(p), C.byref(params if params is not None else self.params), C.sizeof(_lib.Params))
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise AttributeError("esim_params has no field %r" % k)
+            setattr(p, k, v)
+        _lib.check(self.lib.esim_restart(self._ctx, C.byref(p)), self._ctx)
+        self.params = p
+        self.statistics_recorder = StatisticsRecorder()
+        self._steps = 0
+
+    # -- per-Output-Area accumulators over the members of an ensemble (esim_ensemble_*) -------
+    def ensemble_begin(self, where="home", status_mask=(1 << _lib.EXPOSED) | (1 << _lib.INFECTED) | (1 << _lib.RECOVERED), min_cases=1):
+        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
+        _lib.check(self.lib.esim_ensemble_begin(self._ctx, int(code), int(status_mask), int(min_cases)), self._ctx)
+
+    def ensemble_fold(self):
+        """Adds the state as it stands to the accumulators, on the device; nothing is downloaded."""
+        _lib.check(self.lib.esim_ensemble_fold(self._ctx), self._ctx)
+
+    def ensemble_read(self):
+        """{"members": int, "hit": uint32 [n_areas], "sum": uint64 [n_areas], "sumsq": uint64 [n_areas]}"""
+        na = self.population.n_areas
+        members = C.c_uint32(0)
+        hit, tot, sq = np.zeros(na, np.uint32), np.zeros(na, np.uint64), np.zeros(na, np.uint64)
+        _lib.check(self.lib.esim_ensemble_read(self._ctx, C.byref(members), hit.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               tot.ctypes.data_as(C.POINTER(C.c_uint64)), sq.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
+        return {"members": int(members.value), "hit": hit, "sum": tot, "sumsq": sq}
+
     def download_state(self):
         n = self.population.n_citizens
         out = {"status": np.zeros(n, np.uint8), "timer": np.zeros(n, np.uint16),

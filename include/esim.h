@@ -122,6 +122,18 @@ int  esim_create(const esim_params *p, esim_ctx **out);
 int  esim_upload_population(esim_ctx *ctx, const esim_population *pop);
 /* Back to time step 0 with the uploaded population (all Susceptible, seeds Infected(0)). */
 int  esim_reset(esim_ctx *ctx);
+/* Back to time step 0 with the uploaded population, as esim_reset, but with the parameters *p in force from here on
+ * (seed, exposure_chance, mask_effectiveness, the four thresholds, exposed/infected_time, vaccination_rate, bus_capacity,
+ * the hours) and without any host->device traffic proportional to the population: the initial state is rebuilt by
+ * kernels on the context's stream.  p->device must be the context's device and p->max_steps at most the max_steps the
+ * context was created with (the record log's capacity); p is validated exactly as esim_create validates it, and a refused
+ * *p leaves the context as it was.  Nothing waits for the device: the call may return before the work is done, every later
+ * call of this context is ordered behind it.  The only host->device copies are the control block and the threshold LUT
+ * (4.4 KB).  A context with a communicator of more than one rank returns ESIM_ESTATE (the shards would have to agree on
+ * the parameters).  The initially infected citizens stay those of the uploaded population.  esim_reset afterwards goes
+ * back to step 0 under the parameters of the last restart.  Checkpoints: their header is written from the parameters in
+ * force, so one saved after a restart goes back only into a context created with, or restarted to, the same parameters. */
+int  esim_restart(esim_ctx *ctx, const esim_params *p);
 
 /* Replaces Simulator::step (simulator.rs:131-152).  out->disease_exists == 0 is the
  * reference's Ok(false). */
@@ -232,6 +244,21 @@ int  esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint32_t *step
  * population's area indices and starts no collective. */
 enum { ESIM_AREA_CURRENT = 0, ESIM_AREA_HOME = 1 };
 int  esim_area_census(esim_ctx *ctx, int where, uint32_t *counts /* [n_areas * 5] */);
+/* Per-Output-Area accumulators over the members of an ensemble (runs of one population that differ in seed or parameters,
+ * one after another on this context); they live on the device and survive esim_reset and esim_restart.  A new
+ * esim_upload_population drops them.  20 bytes per area, allocated at the first begin.
+ * begin: zero them and fix what a member contributes -- x[area] = number of citizens whose status after the member's last
+ *        completed step is in status_mask (bit s = ESIM_* code s), by ESIM_AREA_HOME or ESIM_AREA_CURRENT.
+ * fold:  count x for the state as it stands (as esim_area_census counts) and add, WITHOUT any download or host wait:
+ *        members += 1; hit[area] += (x >= min_cases); sum[area] += x; sumsq[area] += x * x.
+ * read:  copy out; any pointer may be NULL.
+ * The usual risk map ("reached by the epidemic") is the mask Exposed | Infected | Recovered by home area with min_cases 1.
+ * ESIM_ESTATE before a population is uploaded, and for fold or read before begin; ESIM_EINVAL for an empty mask, a bit beyond
+ * ESIM_VACCINATED or an unknown `where`. */
+int  esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases);
+int  esim_ensemble_fold(esim_ctx *ctx);
+int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_areas] */,
+                        uint64_t *sum /* [n_areas] */, uint64_t *sumsq /* [n_areas] */);
 /* The same picture for the steps already run, derived after the fact from what the device holds (exposure log, citizen
  * words, the records' lockdown flags): a run that never asks pays nothing.  Row i describes step
  * s_i = first_step + i * stride (1-based, s_i <= steps run so far), out[i * n_areas + area]:
