@@ -101,6 +101,12 @@ struct esim_ctx_impl {
     uint32_t *ens_hit = nullptr, *ens_members = nullptr;
     unsigned long long *ens_sum = nullptr, *ens_sumsq = nullptr;
     int ens_where = ESIM_AREA_HOME; uint32_t ens_mask = 0, ens_min = 0;
+    uint32_t ens_n = 0; bool ens_valid = false;   // entries in use (n_areas, or n_groups by group); false: the labels they were begun for are gone
+    // esim_set_groups: a label per citizen, the groups' sizes and the count table of esim_group_census [n_groups * 5] on the
+    // device (nullptr: no labels); the table's pinned mirror, [ESIM_MAX_GROUPS * 5]
+    uint16_t *grp = nullptr; uint32_t n_groups = 0;
+    uint32_t *grp_size = nullptr, *grp_cnt = nullptr;
+    uint32_t *pin_grp = nullptr;
 };
 
 #define CTX(c) (reinterpret_cast<esim_ctx_impl *>(c))
@@ -278,6 +284,7 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     if (c->pin_ctrl) (void)hipHostFree(c->pin_ctrl);
     if (c->pin_rec) (void)hipHostFree(c->pin_rec);
     if (c->pin_area) (void)hipHostFree(c->pin_area);
+    if (c->pin_grp) (void)hipHostFree(c->pin_grp);
     if (c->pin_restart) (void)hipHostFree(c->pin_restart);
     if (c->restart_ev) (void)hipEventDestroy(c->restart_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -408,6 +415,8 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     free_device(c);
     c->seeds_dev = nullptr;                                        // (freed with the rest; the ensemble accumulators go with the population)
     c->ens_hit = c->ens_members = nullptr; c->ens_sum = c->ens_sumsq = nullptr;
+    c->ens_valid = false;
+    c->grp = nullptr; c->grp_size = c->grp_cnt = nullptr; c->n_groups = 0;   // (the labels belong to the population they were set for)
     Dev &d = c->d;
     std::memset(&d, 0, sizeof d);
     d.n = N; d.n_global = n_global; d.id_base = pop->citizen_id_base; d.n_bld = B; d.n_room = R;
@@ -1917,6 +1926,51 @@ int enqueue_area_census(esim_ctx_impl *c, int where)
     hipLaunchKernelGGL(k_area_census, dim3(grid), dim3(TPB), 0, c->stream, d, where == ESIM_AREA_HOME ? 1 : 0, per_block, c->area_cnt);
     return ESIM_OK;
 }
+
+// the count table of esim_group_census, the same way: four citizens per lane and trip, at most 1024 workgroups (four per
+// compute unit: every one of them ends with up to 4 * n_groups adds to the global table)
+int enqueue_group_census(esim_ctx_impl *c)
+{
+    const Dev &d = c->d;
+    HIP_TRY(c, hipMemsetAsync(c->grp_cnt, 0, sizeof(uint32_t) * (size_t)c->n_groups * 5u, c->stream));
+    hipLaunchKernelGGL(k_group_census, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 1024)), dim3(TPB), 0, c->stream, d, c->grp, c->n_groups, c->grp_cnt);
+    hipLaunchKernelGGL(k_group_finish, dim3(grid_for(c->n_groups, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, c->grp_size, c->n_groups, c->grp_cnt);
+    return ESIM_OK;
+}
+
+// What the series derive from the records of the steps run (rec[1 .. t_done]): the at-work bit after the schedule arm of every
+// step (citizen.rs:176-206: the arm of step s runs iff no lockdown was in force, i.e. the record of step s - 1 has none) and
+// the steps at which it changes; the step that started the vaccination programme (0: none) and the first one that vaccinated
+// the whole eligible set (0xFFFFFFFF: none).
+struct RunShape { std::vector<uint8_t> aw; std::vector<uint32_t> tog; uint32_t trigger = 0, t_all = 0xFFFFFFFFu; };
+int run_shape(esim_ctx_impl *c, uint32_t t_done, RunShape *r)
+{
+    std::vector<esim_step_result> rec((size_t)t_done + 1u);
+    HIP_TRY(c, hipMemcpy(rec.data() + 1, c->d.records + 1, sizeof(esim_step_result) * t_done, hipMemcpyDeviceToHost));
+    r->aw.assign((size_t)t_done + 1u, 0);
+    for (uint32_t s = 1; s <= t_done; ++s) {
+        uint8_t cur = r->aw[s - 1u];
+        if (s == 1u || !rec[s - 1u].lockdown) {
+            const uint32_t hr = s % 24u;
+            if (hr == c->P.start_hour) cur = 1; else if (hr == c->P.end_hour) cur = 0;
+        }
+        r->aw[s] = cur;
+        if (cur != r->aw[s - 1u]) r->tog.push_back(s);
+        if (!r->trigger && rec[s].vaccination_active) r->trigger = s;
+        if (r->trigger && r->t_all == 0xFFFFFFFFu && rec[s].eligible_count <= c->P.vaccination_rate) r->t_all = s;
+    }
+    return ESIM_OK;
+}
+
+// vax_of[c] = the step at whose end citizen c was set Vaccinated, on the context's stream (steps that vaccinated the whole
+// eligible set apart: RunShape::t_all)
+hipError_t enqueue_vax_replay(esim_ctx_impl *c, uint32_t trigger, uint32_t t_done, uint32_t *d_vax)
+{
+    const hipError_t e = hipMemsetAsync(d_vax, 0xFF, sizeof(uint32_t) * (size_t)c->d.n, c->stream);
+    if (e == hipSuccess)
+        hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(t_done - trigger + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, c->d, trigger, t_done, d_vax);
+    return e;
+}
 }  // namespace
 
 extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
@@ -1940,11 +1994,13 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c) return ESIM_EINVAL;
-    if ((where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME) || status_mask == 0u || (status_mask >> 5) != 0u)
+    if ((where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME && where != ESIM_BY_GROUP) || status_mask == 0u || (status_mask >> 5) != 0u)
         return fail(c, ESIM_EINVAL, "esim_ensemble_begin: unknown `where`, or a status mask that is empty or names a status beyond ESIM_VACCINATED");
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: no population uploaded");
+    if (where == ESIM_BY_GROUP && (!c->grp || c->comm_world > 1)) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: by group without labels (esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    const size_t na = std::max<size_t>(1, c->d.n_areas);
+    // one allocation serves both kinds: the areas, or up to ESIM_MAX_GROUPS groups
+    const size_t na = std::max<size_t>(ESIM_MAX_GROUPS, c->d.n_areas);
     if (!c->ens_hit) {
         int rc;
         uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
@@ -1959,6 +2015,7 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
     HIP_TRY(c, hipMemsetAsync(c->ens_sumsq, 0, sizeof(unsigned long long) * na, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->ens_members, 0, sizeof(uint32_t), c->stream));
     c->ens_where = where; c->ens_mask = status_mask; c->ens_min = min_cases;
+    c->ens_n = where == ESIM_BY_GROUP ? c->n_groups : c->d.n_areas; c->ens_valid = true;
     return ESIM_OK;
 }
 
@@ -1966,12 +2023,14 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens_hit) return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload");
+    if (!c->uploaded || !c->ens_hit || !c->ens_valid)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;
-    if ((rc = enqueue_area_census(c, c->ens_where))) return rc;
-    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->d.n_areas, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
-                       c->area_cnt, c->d.n_areas, c->ens_mask, c->ens_min, c->ens_hit, c->ens_sum, c->ens_sumsq, c->ens_members);
+    const bool by_group = c->ens_where == ESIM_BY_GROUP;
+    if ((rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, c->ens_where))) return rc;
+    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->ens_n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       by_group ? c->grp_cnt : c->area_cnt, c->ens_n, c->ens_mask, c->ens_min, c->ens_hit, c->ens_sum, c->ens_sumsq, c->ens_members);
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
@@ -1980,12 +2039,13 @@ extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hi
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens_hit) return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload");
+    if (!c->uploaded || !c->ens_hit || !c->ens_valid)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
     Ctrl h;
     int rc;
     if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
-    const size_t na = c->d.n_areas;
+    const size_t na = c->ens_n;
     if (members) HIP_TRY(c, hipMemcpy(members, c->ens_members, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (hit && na) HIP_TRY(c, hipMemcpy(hit, c->ens_hit, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
     if (sum && na) HIP_TRY(c, hipMemcpy(sum, c->ens_sum, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
@@ -2008,24 +2068,11 @@ extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, ui
     Ctrl h;
     int rc;
     if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
-    // the at-work bit of every step run, as the schedule (citizen.rs:176-206) produced it: the arm of step s runs iff no
-    // lockdown was in force, i.e. the record of step s - 1 has none
-    std::vector<esim_step_result> rec((size_t)t_done + 1u);
-    HIP_TRY(c, hipMemcpy(rec.data() + 1, d.records + 1, sizeof(esim_step_result) * t_done, hipMemcpyDeviceToHost));
-    std::vector<uint8_t> aw((size_t)t_done + 1u, 0);
-    std::vector<uint32_t> tog;
-    uint32_t trigger = 0, t_all = 0xFFFFFFFFu;
-    for (uint32_t s = 1; s <= t_done; ++s) {
-        uint8_t cur = aw[s - 1u];
-        if (s == 1u || !rec[s - 1u].lockdown) {
-            const uint32_t hr = s % 24u;
-            if (hr == c->P.start_hour) cur = 1; else if (hr == c->P.end_hour) cur = 0;
-        }
-        aw[s] = cur;
-        if (cur != aw[s - 1u]) tog.push_back(s);
-        if (!trigger && rec[s].vaccination_active) trigger = s;
-        if (trigger && t_all == 0xFFFFFFFFu && rec[s].eligible_count <= c->P.vaccination_rate) t_all = s;
-    }
+    RunShape shape;
+    if ((rc = run_shape(c, t_done, &shape))) return rc;
+    const std::vector<uint8_t> &aw = shape.aw;
+    const std::vector<uint32_t> &tog = shape.tog;
+    const uint32_t trigger = shape.trigger, t_all = shape.t_all;
     const bool replay = what == ESIM_SERIES_INFECTED && trigger != 0u;
     if (replay && d.n_global != d.n)
         return fail(c, ESIM_ESTATE, "esim_area_series: the Infected rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
@@ -2041,11 +2088,7 @@ extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, ui
     hipError_t e = hipMemcpyAsync(d_aw, aw.data(), aw.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && !tog.empty()) e = hipMemcpyAsync(d_tog, tog.data(), sizeof(uint32_t) * tog.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(uint32_t) * out_words, c->stream);
-    if (e == hipSuccess && replay) {
-        e = hipMemsetAsync(d_vax, 0xFF, sizeof(uint32_t) * (size_t)d.n, c->stream);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(t_done - trigger + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, d, trigger, t_done, d_vax);
-    }
+    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, trigger, t_done, d_vax);
     if (e == hipSuccess) {
         AreaSeries q;
         q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done;
@@ -2058,6 +2101,112 @@ extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, ui
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint32_t) * (size_t)n_rows * d.n_areas, hipMemcpyDeviceToHost);
     cleanup();
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_area_series: ") + hipGetErrorString(e));
+    return ESIM_OK;
+}
+
+// ---- read-backs by citizen group ---------------------------------------------------------------------------------------
+extern "C" int esim_set_groups(esim_ctx *ctx, const uint16_t *group, uint32_t n_groups)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_set_groups: no population uploaded");
+    if (c->comm_world > 1) return fail(c, ESIM_ESTATE, "esim_set_groups: the context has a communicator of several ranks (sharded groups are not built)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const uint32_t N = c->d.n;
+    std::vector<uint32_t> size;
+    if (group) {
+        if (n_groups == 0 || n_groups > ESIM_MAX_GROUPS) return fail(c, ESIM_EINVAL, "esim_set_groups: n_groups must be in 1..ESIM_MAX_GROUPS (1024)");
+        size.assign(n_groups, 0u);
+        for (uint32_t i = 0; i < N; ++i) {
+            if (group[i] >= n_groups) return fail(c, ESIM_EINVAL, "esim_set_groups: a label is not below n_groups");
+            size[group[i]]++;
+        }
+    }
+    uint16_t *lab = nullptr; uint32_t *sz = nullptr, *cnt = nullptr;
+    if (group) {
+        int rc;
+        if (!c->pin_grp) HIP_TRY(c, hipHostMalloc((void **)&c->pin_grp, sizeof(uint32_t) * ESIM_MAX_GROUPS * 5u, hipHostMallocDefault));
+        if ((rc = dev_alloc(c, &lab, N)) || (rc = dev_alloc(c, &sz, n_groups)) || (rc = dev_alloc(c, &cnt, (size_t)n_groups * 5u))) {
+            dev_free(c, lab); dev_free(c, sz); dev_free(c, cnt);
+            return rc;
+        }
+        hipError_t e = N ? hipMemcpy(lab, group, sizeof(uint16_t) * (size_t)N, hipMemcpyHostToDevice) : hipSuccess;
+        if (e == hipSuccess) e = hipMemcpy(sz, size.data(), sizeof(uint32_t) * n_groups, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            dev_free(c, lab); dev_free(c, sz); dev_free(c, cnt);
+            return fail(c, ESIM_ENODEVICE, std::string("esim_set_groups: ") + hipGetErrorString(e));
+        }
+    }
+    // the tables being replaced may still be read by work on the stream (a fold)
+    if (c->grp) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dev_free(c, c->grp); dev_free(c, c->grp_size); dev_free(c, c->grp_cnt);
+    c->grp = lab; c->grp_size = sz; c->grp_cnt = cnt; c->n_groups = group ? n_groups : 0u;
+    if (c->ens_where == ESIM_BY_GROUP) c->ens_valid = false;
+    return ESIM_OK;
+}
+
+extern "C" int esim_group_census(esim_ctx *ctx, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!counts) return fail(c, ESIM_EINVAL, "esim_group_census: null output");
+    if (!c->uploaded || !c->grp || c->comm_world > 1) return fail(c, ESIM_ESTATE, "esim_group_census: no population uploaded, or no labels (esim_set_groups)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const size_t n_out = (size_t)c->n_groups * 5u;
+    if (int rc = enqueue_group_census(c)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->pin_grp, c->grp_cnt, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, c->stream));
+    Ctrl h;
+    if (int rc = read_ctrl(c, &h)) return rc;                     // (the one wait: the table is in the mirror behind it)
+    std::memcpy(counts, c->pin_grp, sizeof(uint32_t) * n_out);
+    return ctrl_error(c, h);
+}
+
+extern "C" int esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c) return ESIM_EINVAL;
+    if (!out || what < ESIM_SUSCEPTIBLE || what > ESIM_GROUP_SERIES_EXPOSURES || stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_group_series: null output, unknown `what`, stride 0 or no rows");
+    if (!c->uploaded || !c->grp || c->comm_world > 1) return fail(c, ESIM_ESTATE, "esim_group_series: no population uploaded, or no labels (esim_set_groups)");
+    const uint32_t t_done = c->host_t - 1u;                       // steps run so far
+    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
+        return fail(c, ESIM_ERANGE, "esim_group_series: rows outside the steps run so far");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    Ctrl h;
+    int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
+    RunShape shape;
+    if ((rc = run_shape(c, t_done, &shape))) return rc;
+    const bool status_rows = what != ESIM_GROUP_SERIES_EXPOSURES;
+    const bool replay = status_rows && shape.trigger != 0u;
+    if (replay && d.n_global != d.n)
+        return fail(c, ESIM_ESTATE, "esim_group_series: the status rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
+    const uint32_t ng = c->n_groups;
+    uint32_t *d_vax = nullptr, *d_out = nullptr;
+    const size_t out_words = ((size_t)n_rows + 1u) * ng;
+    if (hipMalloc(&d_out, sizeof(uint32_t) * out_words) != hipSuccess ||
+        (replay && hipMalloc(&d_vax, sizeof(uint32_t) * std::max<size_t>(1, d.n)) != hipSuccess)) {
+        (void)hipFree(d_vax); (void)hipFree(d_out); (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, "esim_group_series: no device memory for the rows (ask for fewer)");
+    }
+    hipError_t e = hipMemsetAsync(d_out, 0, sizeof(uint32_t) * out_words, c->stream);
+    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax);
+    if (e == hipSuccess) {
+        AreaSeries q;
+        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done;
+        q.n_tog = 0; q.t_all = shape.t_all; q.at_work = nullptr; q.tog = nullptr; q.vax_of = d_vax; q.out = d_out;
+        const bool citizens = what == ESIM_VACCINATED || what == ESIM_SUSCEPTIBLE;   // (the pass over everybody Vaccinated)
+        hipLaunchKernelGGL(k_group_series, dim3(grid_for(citizens ? std::max<size_t>(d.n, h.log_len) : h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream,
+                           d, q, c->grp, ng, h.log_len);
+        if (status_rows) hipLaunchKernelGGL(k_area_prefix, dim3(grid_for(ng, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d_out, n_rows, ng);
+        if (what == ESIM_SUSCEPTIBLE)
+            hipLaunchKernelGGL(k_group_s_rows, dim3(grid_for((size_t)n_rows * ng, TPB, 4096)), dim3(TPB), 0, c->stream, d_out, n_rows, ng, c->grp_size);
+        e = hipStreamSynchronize(c->stream);
+    } else (void)hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(uint32_t) * (size_t)n_rows * ng, hipMemcpyDeviceToHost);
+    (void)hipFree(d_vax); (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_group_series: ") + hipGetErrorString(e));
     return ESIM_OK;
 }
 

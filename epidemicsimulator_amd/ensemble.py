@@ -1,6 +1,6 @@
 """Ensembles of one uploaded population: many Philox seeds of one world, or the same world under several parameter sets,
-one member after another on ONE context (esim_restart), summarised per step on the host and per Output Area on the device
-(esim_ensemble_*).  The population is validated, hashed and uploaded once."""
+one member after another on ONE context (esim_restart), summarised per step on the host and per Output Area -- or per
+citizen group -- on the device (esim_ensemble_*).  The population is validated, hashed and uploaded once."""
 import ctypes as C
 import json
 import os
@@ -83,8 +83,11 @@ class EnsembleResult:
 class Ensemble:
     """Owns one Simulator; every member is a restart of it under the base parameters changed by the member's overrides."""
 
-    def __init__(self, population, params=None, area_codes=None):
+    def __init__(self, population, params=None, area_codes=None, group=None):
+        """group: None, or (labels, n_groups) for Simulator.set_groups -- what run(area=dict(where="group", ...)) counts by."""
         self.simulator = Simulator(population, params, area_codes=area_codes)
+        if group is not None:
+            self.simulator.set_groups(*group)
         self.area_codes = area_codes
         self.base = _lib.Params()
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
@@ -95,7 +98,8 @@ class Ensemble:
 
     def run(self, members, n_steps, stop_when_done=False, area=None):
         """members: iterable of override dicts (Ensemble.seeds); area: None, or the arguments of esim_ensemble_begin as a dict
-        (where, status_mask, min_cases).  Returns an EnsembleResult."""
+        (where, status_mask, min_cases); where="group" counts by the groups given to Ensemble(...), and the summary then has
+        one entry per group.  Returns an EnsembleResult."""
         sim = self.simulator
         members = [dict(m) for m in members]
         if area is not None:
@@ -113,7 +117,8 @@ class Ensemble:
         if area is not None:
             r = sim.ensemble_read()
             summary = area_summary(r["members"], r["hit"], r["sum"], r["sumsq"])
-        return EnsembleResult(records, n_done, members, summary, self.area_codes)
+        by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
 
     def close(self):
         self.simulator.close()

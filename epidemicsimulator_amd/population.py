@@ -130,6 +130,19 @@ class Population:
         _lib.check(lib.esim_shard_cuts(C.byref(whole), n_shards, 1, cuts.ctypes.data_as(C.POINTER(C.c_uint32))))
         return cuts
 
+    # -- citizen groups (Simulator.set_groups) ------------------------------------------------
+    def age_bands(self, edges):
+        """(labels uint16 [n_citizens], n_groups): band k holds the ages edges[k - 1] <= age < edges[k] (np.digitize), band 0
+        everybody younger than edges[0], the last band everybody from edges[-1] on: len(edges) + 1 groups."""
+        edges = np.asarray(edges)
+        if edges.ndim != 1 or edges.size == 0 or (np.diff(edges) <= 0).any():
+            raise ValueError("age_bands: edges must be a non-empty, strictly increasing sequence")
+        return np.digitize(self.age, edges).astype(np.uint16), int(edges.size) + 1
+
+    def occupation_groups(self):
+        """(labels uint16 [n_citizens], n_groups): the occupation byte as the label, n_groups = the largest one + 1."""
+        return self.occupation.astype(np.uint16), (int(self.occupation.max()) + 1 if self.n_citizens else 1)
+
     def even_cuts(self, n_shards):
         """Area boundaries giving each shard about the same number of citizens."""
         area_of_citizen = self.building_area[self.home_building]

@@ -215,7 +215,8 @@ class Simulator:
 
     # -- per-Output-Area accumulators over the members of an ensemble (esim_ensemble_*) -------
     def ensemble_begin(self, where="home", status_mask=(1 << _lib.EXPOSED) | (1 << _lib.INFECTED) | (1 << _lib.RECOVERED), min_cases=1):
-        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
+        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)
+        self._ens_n = self._n_groups if code == _lib.BY_GROUP else self.population.n_areas
         _lib.check(self.lib.esim_ensemble_begin(self._ctx, int(code), int(status_mask), int(min_cases)), self._ctx)
 
     def ensemble_fold(self):
@@ -223,8 +224,9 @@ class Simulator:
         _lib.check(self.lib.esim_ensemble_fold(self._ctx), self._ctx)
 
     def ensemble_read(self):
-        """{"members": int, "hit": uint32 [n_areas], "sum": uint64 [n_areas], "sumsq": uint64 [n_areas]}"""
-        na = self.population.n_areas
+        """{"members": int, "hit": uint32 [n], "sum": uint64 [n], "sumsq": uint64 [n]}, n = n_areas, or n_groups for
+        accumulators begun by group."""
+        na = getattr(self, "_ens_n", self.population.n_areas)
         members = C.c_uint32(0)
         hit, tot, sq = np.zeros(na, np.uint32), np.zeros(na, np.uint64), np.zeros(na, np.uint64)
         _lib.check(self.lib.esim_ensemble_read(self._ctx, C.byref(members), hit.ctypes.data_as(C.POINTER(C.c_uint32)),
@@ -367,6 +369,48 @@ class Simulator:
         out = np.zeros((max(0, int(n_rows)), self.population.n_areas), np.uint32)
         _lib.check(self.lib.esim_area_series(self._ctx, int(code), int(first_step), int(n_rows), int(stride),
                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
+    # -- the same by citizen group (esim_set_groups, esim_group_census, esim_group_series) -------
+    _n_groups = 0
+
+    def set_groups(self, labels, n_groups=None):
+        """One label per citizen (copied to the device as uint16); n_groups=None: the largest label + 1.  labels=None drops
+        them.  Population.age_bands() and Population.occupation_groups() make such labels."""
+        if labels is None:
+            _lib.check(self.lib.esim_set_groups(self._ctx, None, 0), self._ctx)
+            self._n_groups = 0
+            return
+        raw = np.asarray(labels)
+        if raw.shape != (self.population.n_citizens,):
+            raise ValueError("set_groups: one label per citizen, got shape %s" % (raw.shape,))
+        if raw.size and (int(raw.min()) < 0 or int(raw.max()) > 0xFFFF):
+            raise ValueError("set_groups: labels must fit uint16")
+        lab = np.ascontiguousarray(raw, np.uint16)
+        if n_groups is None:
+            n_groups = int(lab.max()) + 1 if lab.size else 1
+        _lib.check(self.lib.esim_set_groups(self._ctx, lab.ctypes.data_as(C.POINTER(C.c_uint16)), int(n_groups)), self._ctx)
+        self._n_groups = int(n_groups)
+
+    def group_census(self):
+        """uint32 [n_groups, 5]: citizens per group and DiseaseStatus after the last completed step, counted on the device
+        (esim_group_census)."""
+        out = np.zeros((max(1, self._n_groups), 5), np.uint32)
+        _lib.check(self.lib.esim_group_census(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
+    def group_series(self, what, first_step=1, n_rows=None, stride=1):
+        """uint32 [n_rows, n_groups] over the steps already run (esim_group_series): row i is step first_step + i * stride.
+        what: "susceptible", "exposed", "infected", "recovered", "vaccinated" (citizens of the group with that status after
+        the step) or "exposures" (building and public-transport exposures of the `stride` steps from that one on, by the
+        group of the exposed citizen).  n_rows=None: up to the last step run."""
+        code = {"susceptible": _lib.SUSCEPTIBLE, "exposed": _lib.EXPOSED, "infected": _lib.INFECTED, "recovered": _lib.RECOVERED,
+                "vaccinated": _lib.VACCINATED, "exposures": _lib.GROUP_SERIES_EXPOSURES}.get(what, what)
+        if n_rows is None:
+            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
+        out = np.zeros((max(0, int(n_rows)), max(1, self._n_groups)), np.uint32)
+        _lib.check(self.lib.esim_group_series(self._ctx, int(code), int(first_step), int(n_rows), int(stride),
+                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
     def enable_kernel_timing(self, stride):

@@ -254,7 +254,7 @@ int  esim_area_census(esim_ctx *ctx, int where, uint32_t *counts /* [n_areas * 5
  * read:  copy out; any pointer may be NULL.
  * The usual risk map ("reached by the epidemic") is the mask Exposed | Infected | Recovered by home area with min_cases 1.
  * ESIM_ESTATE before a population is uploaded, and for fold or read before begin; ESIM_EINVAL for an empty mask, a bit beyond
- * ESIM_VACCINATED or an unknown `where`. */
+ * ESIM_VACCINATED or an unknown `where`.  where = ESIM_BY_GROUP: by citizen group instead of by area (esim_set_groups, below). */
 int  esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases);
 int  esim_ensemble_fold(esim_ctx *ctx);
 int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_areas] */,
@@ -278,6 +278,37 @@ int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_ar
 enum { ESIM_SERIES_INFECTED = 0, ESIM_SERIES_EXPOSURES = 1 };
 int  esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
                       uint32_t *out /* [n_rows * n_areas] */);
+/* Stratified outputs: the same read-backs by citizen GROUP -- an age band, an occupation, any label of the caller's.
+ * esim_set_groups copies one label per local citizen to the device (2 B per citizen; no host pointer is kept) and counts the
+ * groups' sizes once.  1 <= n_groups <= ESIM_MAX_GROUPS; a label >= n_groups is ESIM_EINVAL (checked on the host during the
+ * copy) and leaves the context as it was; group == NULL drops the labels.  ESIM_ESTATE before a population is uploaded and on
+ * a context whose communicator has more than one rank (the rule of esim_restart: sharded groups are not built, and the other
+ * group calls answer the same there).  The labels survive esim_reset, esim_restart and esim_checkpoint_restore; a new
+ * esim_upload_population drops them.  They are no simulation state: no checkpoint holds them, the population hash does not
+ * cover them.  A later call replaces them and invalidates ensemble accumulators begun by group (fold and read then return
+ * ESIM_ESTATE until the next begin).
+ * esim_group_census: counts[g * 5 + status] after the last completed step, with the semantics of esim_area_census (after
+ * esim_reset: everybody Susceptible, the seeds Infected).  Leaves the simulation state as it is.  ESIM_ESTATE without labels.
+ * esim_group_series: row i describes step s_i = first_step + i * stride, addressed as esim_area_series addresses its rows
+ * and with its ESIM_ERANGE / ESIM_ENOMEM rules, out[i * n_groups + g]:
+ *   what = ESIM_SUSCEPTIBLE .. ESIM_VACCINATED   citizens of group g with that status after step s_i -- that column of what
+ *                          esim_group_census would have returned after s_i, i.e. the state after the step's vaccinations
+ *                          (the convention of the area tables);
+ *   ESIM_GROUP_SERIES_EXPOSURES   exposures of steps [s_i, s_i + stride), clipped to the steps run, by the group of the
+ *                          exposed citizen: buildings AND public transport (a group has no location); the initially
+ *                          infected citizens are not counted.
+ * Limits: a row buffer of (n_rows + 1) * n_groups * 4 B on the device, and, once a vaccination programme has run, 4 B per
+ * citizen of temporary device memory for the status rows (the choice of simulator.rs:524-553 is walked again, as for
+ * esim_area_series).
+ * Ensembles: esim_ensemble_begin with where = ESIM_BY_GROUP sizes the accumulators by n_groups, x[g] = the citizens of group
+ * g whose status is in status_mask; fold and read then run over n_groups entries.  ESIM_ESTATE without labels. */
+#define ESIM_MAX_GROUPS 1024
+enum { ESIM_BY_GROUP = 2 };                    /* `where` of esim_ensemble_begin, beside ESIM_AREA_CURRENT and ESIM_AREA_HOME */
+enum { ESIM_GROUP_SERIES_EXPOSURES = 5 };      /* `what` of esim_group_series, beside the five status codes */
+int  esim_set_groups(esim_ctx *ctx, const uint16_t *group /* [n_citizens] */, uint32_t n_groups);
+int  esim_group_census(esim_ctx *ctx, uint32_t *counts /* [n_groups * 5] */);
+int  esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                       uint32_t *out /* [n_rows * n_groups] */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
