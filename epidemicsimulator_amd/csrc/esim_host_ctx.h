@@ -1,0 +1,369 @@
+// esim_host_ctx.h -- the context behind an esim_ctx, by concern; the helpers every host part uses; esim_create / esim_destroy.
+namespace {
+
+thread_local std::string g_create_error;
+
+// Event timing, six mechanisms, and every event they use: clear() is what going back to step 0 forgets, destroy() frees the events.
+struct Timing {
+    bool phase = false, kernel = false;                 // esim_enable_phase_timing / esim_enable_kernel_timing
+    uint32_t stride = 16;                               // kernel timing looks at every stride-th step
+    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };   // phases of a sequential step
+    double phase_s[3] = { 0, 0, 0 };
+    std::vector<hipEvent_t> kev; size_t kev_used = 0;   // two per timed step: before k_infected, after k_finish
+    hipEvent_t cev[2] = { nullptr, nullptr }; double chunk_ms = 0; uint64_t chunk_steps = 0, chunk_count = 0;   // bursts of chunk passes
+    std::vector<hipEvent_t> pkev; size_t pkev_used = 0; uint64_t pipe_steps = 0;   // sampled k_pipe launches
+    hipEvent_t sev[2] = { nullptr, nullptr }; double small_ms = 0; uint64_t small_steps = 0;   // k_small
+    // per-kernel device time of the chunk pass (esim_enable_chunk_kernel_timing): an event in front of every kernel of a chunk
+    bool kdetail = false;
+    std::vector<hipEvent_t> kdev; std::vector<int> kd_kind; size_t kd_used = 0;
+    double kd_ms[ESIM_CK_N] = { 0 }; uint64_t kd_calls[ESIM_CK_N] = { 0 };
+    bool host_trace = false;                            // ESIM_TRACE_HOST: esim_run prints where its host time went (stderr)
+    std::vector<std::pair<const char *, double>> ht;
+
+    static void make_pair(hipEvent_t (&e)[2]) { if (!e[0]) { (void)hipEventCreate(&e[0]); (void)hipEventCreate(&e[1]); } }
+    void clear()
+    {
+        phase_s[0] = phase_s[1] = phase_s[2] = 0;
+        kev_used = 0; pkev_used = 0; pipe_steps = 0;
+        small_ms = 0; small_steps = 0; chunk_ms = 0; chunk_steps = 0; chunk_count = 0;
+    }
+    void destroy()
+    {
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : cev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : sev) if (e) (void)hipEventDestroy(e);
+        for (auto *v : { &kev, &pkev, &kdev }) { for (auto &e : *v) (void)hipEventDestroy(e); v->clear(); }
+    }
+};
+
+// The exchange between shards (esim_comm_*): RCCL owned by the library, or a caller's all-reduce.
+struct Comm {
+    int rank = 0, world = 1;
+    ncclComm_t nccl = nullptr;
+    esim_allreduce_fn fn = nullptr; void *user = nullptr;
+    std::vector<uint32_t> stage;
+    uint32_t *xr = nullptr; size_t xr_n = 0;      // records exchange (sharded chunks)
+    uint64_t chunk_steps = 0, step_steps = 0;     // steps run as sharded chunks / as coupled steps
+    uint64_t calls = 0;
+    double timeout_s = 60.0;                      // deadline of a host wait on a stream that holds collectives (esim_comm_set_timeout)
+};
+
+// Pinned host mirrors: control block and records come back with ONE stream wait (two blocking copies cost more than a small chunk).
+struct Pinned {
+    Ctrl *ctrl = nullptr;
+    esim_step_result *rec = nullptr; size_t rec_n = 0;
+    uint32_t first = 0, valid = 0;                // records [first, first + valid) of the call in flight are in rec
+    bool track = false;
+    bool ctrl_fresh = false;                      // ctrl holds the control block as it stands (nothing was enqueued since)
+    uint32_t *area = nullptr; size_t area_n = 0;  // esim_area_census: mirror of the count table, [n_areas * 5]
+    uint32_t *grp = nullptr;                      // esim_group_census: the same, [ESIM_MAX_GROUPS * 5]
+};
+
+// esim_restart: the distinct seeds on the device; control block and threshold LUT staged in pinned memory, an event behind their copies.
+struct RestartStaging {
+    uint32_t *seeds_dev = nullptr;
+    struct Block { Ctrl h; uint64_t lut[512]; } *stage = nullptr;
+    hipEvent_t ev = nullptr; bool ev_used = false;
+};
+
+// esim_ensemble_*: accumulators over the members of an ensemble, [n_areas] each (nullptr before the first esim_ensemble_begin).
+struct Ensemble {
+    uint32_t *hit = nullptr, *members = nullptr;
+    unsigned long long *sum = nullptr, *sumsq = nullptr;
+    int where = ESIM_AREA_HOME; uint32_t mask = 0, min = 0;
+    uint32_t n = 0; bool valid = false;           // entries in use (n_areas, or n_groups by group); false: the labels they were begun for are gone
+};
+
+// esim_set_groups: a label per citizen, the groups' sizes and the count table of esim_group_census [n * 5] (nullptr: no labels).
+struct Groups {
+    uint16_t *lab = nullptr; uint32_t n = 0;
+    uint32_t *size = nullptr, *cnt = nullptr;
+};
+
+// What picks the form and the grids of the kernels: esim_set_* and the tuning knobs of the environment (read at upload).
+struct Tuning {
+    uint32_t grid_citizens = 1, grid_infected = 1, grid_expose = 1;
+    uint32_t grid_chunk = 1024;
+    bool grid_chunk_env = false;                // ESIM_GRID_CHUNK is set: the grid it names holds for chunks with few Infected too
+    bool pipeline = true;                       // run chunks of steps as one kernel per step while no vaccination programme runs
+    bool time_parallel = true;                  // draw all steps of a chunk in one pass when its marks fit the hash map
+    bool vax_chunks = true;                     // time-parallel chunks also under a vaccination programme (their vaccinations planned ahead, k_chunk_vax)
+    bool vax_repair = true;                     // planned chunks: repair the plan after bus exposures instead of cutting the chunk (ESIM_VAX_REPAIR=0: cut)
+    bool vax_repair_always = false;             // ESIM_VAX_REPAIR=2: from the start
+    uint32_t tiny_pairs = 2048;                 // chunks with at most this many (Infected, step) pairs at the last read-back run as ONE kernel (k_chunk_tiny; 0: off)
+    uint32_t small_grid = 64, small_mult = 4;   // chunks with few Infected: workgroups of the marks / fold kernels, multiplier of the draw kernels (0: off)
+    uint32_t draw_mult = 4, units_mult = 4;     // k_chunk_draw / k_chunk_units run this many times the marks grid: more, shorter wavefronts than the chip holds at once
+    uint32_t small_max = 128;                   // infected-slice length up to which the persistent single-workgroup kernel runs a step
+};
+
+struct esim_ctx_impl {
+    esim_params P;
+    Dev d;
+    bool uploaded = false;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // host copies needed for reset
+    std::vector<uint32_t> init_state;
+    std::vector<uint32_t> init_log;       // distinct seeds
+    size_t cnt_bytes = 0;
+    uint32_t *cnt_base = nullptr;
+    uint32_t n_routes = 0;
+    size_t xa_n = 0, xb_n = 0, xf_n = 0;
+    uint64_t pop_hash = 0;        // of the uploaded population arrays: a checkpoint only goes back into the population it came from
+    uint32_t cap_steps = 0;       // capacity of the record log (max_steps at esim_create)
+    uint32_t *area_cnt = nullptr; // esim_area_census: the count table on the device, [n_areas * 5]
+    std::vector<void *> allocs;   // device allocations
+    // where the run stands, as the host knows it (rewind_host takes it back to step 0)
+    uint32_t host_t = 1;                        // next time step to enqueue
+    uint32_t last_chunk_pairs = 0;              // Infected during the chunk last looked at (picks the form of the chunk's book-keeping)
+    uint32_t stop_flag_dev = 0;                 // what ctrl->stop_when_done holds (written only when it changes)
+    bool quiet = false;                         // Ctrl::quiet at the last read-back of a burst of chunk passes
+    bool repair_armed = false;                  // ... its two kernels are enqueued from the first cut of a run on (York never has one: 11 us a chunk saved)
+    bool elig_seen = false;                     // the last control block read back had an eligible set (a vaccination programme runs)
+    uint64_t vax_chunk_steps = 0, vax_chunk_cuts = 0, vax_chunk_repairs = 0;
+    Timing tm;
+    Comm comm;
+    Pinned pin;
+    RestartStaging rs;
+    Ensemble ens;
+    Groups grp;
+    Tuning tune;
+};
+
+#define CTX(c) (reinterpret_cast<esim_ctx_impl *>(c))
+
+void comm_release(esim_ctx_impl *c);     // (esim_host_shard.h)
+int wait_stream(esim_ctx_impl *c);
+
+int fail(esim_ctx_impl *c, int code, const std::string &msg)
+{
+    if (c) c->err = msg; else g_create_error = msg;
+    return code;
+}
+
+#define HIP_TRY(c, expr)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(c, ESIM_ENODEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+int alloc_failed(esim_ctx_impl *c, hipError_t e) { return fail(c, ESIM_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+
+template <class T> int dev_alloc(esim_ctx_impl *c, T **p, size_t n)
+{
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, sizeof(T) * (n ? n : 1));
+    if (e != hipSuccess) return alloc_failed(c, e);
+    c->allocs.push_back(q);
+    *p = (T *)q;
+    return ESIM_OK;
+}
+
+// an allocation with its initial content: every byte 0, or 0xFF where a table's empty value is all ones
+template <class T> int dev_alloc_fill(esim_ctx_impl *c, T **p, size_t n, int byte = 0)
+{
+    if (int rc = dev_alloc(c, p, n)) return rc;
+    if (n) HIP_TRY(c, hipMemset(*p, byte, sizeof(T) * n));
+    return ESIM_OK;
+}
+
+template <class T> int dev_upload(esim_ctx_impl *c, const T **p, const T *host, size_t n)
+{
+    T *q = nullptr;
+    int rc = dev_alloc(c, &q, n);
+    if (rc) return rc;
+    if (n) HIP_TRY(c, hipMemcpy(q, host, sizeof(T) * n, hipMemcpyHostToDevice));
+    *p = q;
+    return ESIM_OK;
+}
+
+void free_device(esim_ctx_impl *c)
+{
+    for (void *p : c->allocs) (void)hipFree(p);
+    c->allocs.clear();
+    c->uploaded = false;
+}
+
+// one allocation back (buffers that are re-sized: the commuter segments, the records exchange); every device pointer of a
+// context is one of its own allocations: any other pointer is left alone
+void dev_free(esim_ctx_impl *c, void *p)
+{
+    auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
+    if (it == c->allocs.end()) return;
+    c->allocs.erase(it);
+    (void)hipFree(p);
+}
+
+// A device buffer that lives as long as one call: freed when its scope ends, whichever way the call leaves.
+template <class T> struct DevTmp {
+    T *p = nullptr;
+    DevTmp() = default; DevTmp(const DevTmp &) = delete; DevTmp &operator=(const DevTmp &) = delete;
+    ~DevTmp() { (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, sizeof(T) * std::max<size_t>(1, n)); }
+};
+
+// the context's device made current and its stream drained
+int drain(esim_ctx_impl *c) { HIP_TRY(c, hipSetDevice(c->P.device)); HIP_TRY(c, hipStreamSynchronize(c->stream)); return ESIM_OK; }
+
+uint32_t grid_for(size_t items, uint32_t per_block, uint32_t cap)
+{
+    size_t g = (items + per_block - 1) / per_block;
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(g, cap));
+}
+
+static inline void ht_mark(esim_ctx_impl *c, const char *what)
+{
+    if (!c->tm.host_trace) return;
+    timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
+    c->tm.ht.emplace_back(what, ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3);
+}
+
+// The control block through the pinned mirror: an asynchronous copy and one wait.  Every read-back of it goes through the
+// mirror (burst_readback and sync_status fill it alongside other work), so that no copy is ever aimed at memory the call
+// does not own.
+int read_ctrl(esim_ctx_impl *c, Ctrl *h)
+{
+    HIP_TRY(c, hipMemcpyAsync(c->pin.ctrl, c->d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *h = *c->pin.ctrl;
+    return ESIM_OK;
+}
+
+// The sticky device-side error of a control block read back, as the call's return code.  A sharded run returns the lowest code
+// any shard raised (Ctrl::peer_error, summed by k_status_unpack), the same on every rank.
+int ctrl_error(esim_ctx_impl *c, const Ctrl &h)
+{
+    if (!h.error) return ESIM_OK;
+    const int code = -(int)(h.peer_error ? err_decode(h.peer_error) : h.error);
+    return fail(c, code, "device-side error " + std::to_string(code) + " (S underflow / vaccination window exhausted / a chunk table check; raised at check " +
+                         std::to_string(h.err_where) + ", esim_device.h ERR_AT_*)");
+}
+
+// The control block's error state as it stands.
+int device_error(esim_ctx_impl *c)
+{
+    Ctrl h;
+    const int rc = read_ctrl(c, &h);
+    return rc ? rc : ctrl_error(c, h);
+}
+
+}  // namespace
+
+extern "C" void esim_default_params(esim_params *p)
+{
+    if (!p) return;
+    p->exposure_chance = 0.00055; p->mask_effectiveness = 0.70;            // disease.rs:120,127
+    p->lockdown_threshold = 0.0034; p->vaccination_threshold = 0.005;      // interventions.rs:74-75
+    p->mask_pt_threshold = 0.001; p->mask_everywhere_threshold = 0.0022;   // interventions.rs:55-56
+    p->exposed_time = 4 * 24; p->infected_time = 14 * 24;                  // disease.rs:122-123
+    p->vaccination_rate = 85 * 18;                                         // disease.rs:125
+    p->bus_capacity = 20;                                                  // config.rs:37
+    p->start_hour = 9; p->end_hour = 17;                                   // citizen.rs:154-155
+    p->seed = 0x5EED2011ull;
+    p->device = 0;
+    p->max_steps = 5000;                                                   // disease.rs:124
+}
+
+// ceil(q * 2^32): `uniform < q` (citizen.rs:242) for uniform = w * 2^-32 (w a 32-bit word) is exactly
+// `w < ceil(q * 2^32)`, because scaling a double by 2^32 is exact.
+extern "C" int esim_threshold_lut(const esim_params *p, uint64_t out[512])
+{
+    if (!p || !out) return ESIM_EINVAL;
+    for (int row = 0; row < 2; ++row) {
+        // DiseaseModel::get_exposure_chance, disease.rs:131-154 (is_vaccinated = false: only
+        // Susceptible citizens are ever tested, simulator.rs:337,436)
+        double chance = p->exposure_chance - (row ? p->exposure_chance * p->mask_effectiveness : 0.0) - 0.0;
+        if (std::signbit(chance)) chance = 0.0;
+        for (int n = 0; n < 256; ++n) {
+            const double q = 1.0 - std::pow(1.0 - chance, (double)n);      // binomial, citizen.rs:47-49
+            const double scaled = std::ceil(std::ldexp(q, 32));
+            out[row * 256 + n] = scaled <= 0.0 ? 0ull : (uint64_t)scaled;
+        }
+    }
+    return ESIM_OK;
+}
+
+namespace {
+// What esim_create and esim_restart accept as parameters (the device ordinal and the record log's capacity apart).
+int check_params(esim_ctx_impl *c, const esim_params *p, const std::string &who)
+{
+    if (p->exposed_time + p->infected_time + 2u > TE_BIAS)
+        return fail(c, ESIM_ERANGE, who + ": exposed_time + infected_time + 2 exceeds the state encoding (512)");
+    if (p->vaccination_rate > VACC_MAX_RATE)
+        return fail(c, ESIM_ERANGE, who + ": vaccination_rate above 8192 is not supported");
+    if (p->bus_capacity == 0 || p->start_hour == 0 || p->end_hour == 0 || p->start_hour > 24 || p->end_hour > 24)
+        return fail(c, ESIM_EINVAL, who + ": bad bus_capacity / working hours");
+    {
+        // the schedule is evaluated once for everybody, which needs the four arms of citizen.rs:177-205 to
+        // fall on four different hours
+        const uint32_t h[4] = { (p->start_hour + 23u) % 24u, p->start_hour % 24u, (p->end_hour + 23u) % 24u, p->end_hour % 24u };
+        for (int a = 0; a < 4; ++a) for (int b = a + 1; b < 4; ++b)
+            if (h[a] == h[b]) return fail(c, ESIM_EINVAL, who + ": start_hour-1, start_hour, end_hour-1, end_hour must be distinct");
+        if (p->start_hour > 23 || p->end_hour > 23) return fail(c, ESIM_EINVAL, who + ": working hours must be in 1..23");
+    }
+    if (p->max_steps == 0 || p->max_steps > ESIM_MAX_STEP)
+        return fail(c, ESIM_ERANGE, who + ": max_steps must be in 1..7600");
+    return ESIM_OK;
+}
+
+// Everything in Dev that is derived from the parameters.
+void params_to_dev(esim_ctx_impl *c)
+{
+    Dev &d = c->d;
+    d.exposed_time = c->P.exposed_time; d.infected_time = c->P.infected_time;
+    d.vaccination_rate = c->P.vaccination_rate; d.bus_capacity = c->P.bus_capacity;
+    d.start_hour = c->P.start_hour; d.end_hour = c->P.end_hour;
+    d.seed_lo = (uint32_t)c->P.seed; d.seed_hi = (uint32_t)(c->P.seed >> 32);
+    d.thr_lockdown = c->P.lockdown_threshold; d.thr_vacc = c->P.vaccination_threshold;
+    d.thr_mask_pt = c->P.mask_pt_threshold; d.thr_mask_all = c->P.mask_everywhere_threshold;
+    d.max_steps = c->P.max_steps;
+    c->xf_n =std::min<uint32_t>(FREE_MAX, c->P.exposed_time + 1u);
+    d.xf_n = (uint32_t)c->xf_n;
+}
+}  // namespace
+
+extern "C" int esim_create(const esim_params *p, esim_ctx **out)
+{
+    if (!p || !out) return fail(nullptr, ESIM_EINVAL, "esim_create: null argument");
+    if (int rc = check_params(nullptr, p, "esim_create")) return rc;
+    int n_dev = 0;
+    hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e != hipSuccess || n_dev <= 0)
+        return fail(nullptr, ESIM_ENODEVICE, std::string("esim_create: no HIP device (") + hipGetErrorString(e) + ")");
+    if (p->device < 0 || p->device >= n_dev) return fail(nullptr, ESIM_EINVAL, "esim_create: device ordinal out of range");
+    e = hipSetDevice(p->device);
+    if (e != hipSuccess) return fail(nullptr, ESIM_ENODEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    esim_ctx_impl *c = new esim_ctx_impl();
+    c->P = *p;
+    c->cap_steps = p->max_steps;
+    if (const char *e = std::getenv("ESIM_COMM_TIMEOUT_S")) { const double v = std::atof(e); if (v > 0.0) c->comm.timeout_s = v; }
+    std::memset(&c->d, 0, sizeof c->d);
+    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { delete c; return fail(nullptr, ESIM_ENODEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    for (auto &ev : c->tm.ev) (void)hipEventCreate(&ev);
+    *out = reinterpret_cast<esim_ctx *>(c);
+    return ESIM_OK;
+}
+
+extern "C" void esim_destroy(esim_ctx *ctx)
+{
+    if (ctx) comm_release(CTX(ctx));
+    if (!ctx) return;
+    esim_ctx_impl *c = CTX(ctx);
+    (void)hipSetDevice(c->P.device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    free_device(c);
+    c->tm.destroy();
+    for (void *p : { (void *)c->pin.ctrl, (void *)c->pin.rec, (void *)c->pin.area, (void *)c->pin.grp, (void *)c->rs.stage })
+        if (p) (void)hipHostFree(p);
+    if (c->rs.ev) (void)hipEventDestroy(c->rs.ev);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+extern "C" const char *esim_last_error(const esim_ctx *ctx)
+{
+    if (!ctx) return g_create_error.c_str();
+    return reinterpret_cast<const esim_ctx_impl *>(ctx)->err.c_str();
+}

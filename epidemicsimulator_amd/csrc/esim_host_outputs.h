@@ -1,0 +1,328 @@
+// esim_host_outputs.h -- read-backs: records, state, exposure log; census and series by area and group; ensemble accumulators.
+extern "C" int esim_read_records(esim_ctx *ctx, uint32_t first_step, uint32_t n, esim_step_result *out)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
+    if (!out || first_step == 0 || (uint64_t)first_step + n > (uint64_t)c->P.max_steps + 1) return fail(c, ESIM_EINVAL, "esim_read_records: bad range");
+    if (int rc = drain(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, &c->d.records[first_step], sizeof(esim_step_result) * n, hipMemcpyDeviceToHost));
+    return device_error(c);
+}
+
+extern "C" int esim_synchronize(esim_ctx *ctx)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (int rc = drain(c)) return rc;
+    return ESIM_OK;
+}
+
+extern "C" int esim_download_state(esim_ctx *ctx, uint8_t *status, uint16_t *timer, uint32_t *current_building,
+                                   uint8_t *on_bus, uint8_t *eligible)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !c->uploaded) return fail(c, ESIM_ESTATE, "no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const uint32_t N = c->d.n;
+    DevTmp<uint8_t> d_status, d_bus, d_elig; DevTmp<uint16_t> d_timer; DevTmp<uint32_t> d_cur;
+    if ((status && d_status.alloc(N) != hipSuccess) || (on_bus && d_bus.alloc(N) != hipSuccess) || (eligible && d_elig.alloc(N) != hipSuccess) ||
+        (timer && d_timer.alloc(N) != hipSuccess) || (current_building && d_cur.alloc(N) != hipSuccess)) return fail(c, ESIM_ENOMEM, "esim_download_state: hipMalloc");
+    hipLaunchKernelGGL(k_decode_state, dim3(c->tune.grid_citizens), dim3(TPB), 0, c->stream, c->d, d_status.p, d_timer.p, d_cur.p, d_bus.p, d_elig.p);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && status) e = hipMemcpy(status, d_status.p, N, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && on_bus) e = hipMemcpy(on_bus, d_bus.p, N, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && eligible) e = hipMemcpy(eligible, d_elig.p, N, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && timer) e = hipMemcpy(timer, d_timer.p, 2 * (size_t)N, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && current_building) e = hipMemcpy(current_building, d_cur.p, 4 * (size_t)N, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_download_state: ") + hipGetErrorString(e));
+    return ESIM_OK;
+}
+
+extern "C" int esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint32_t *step, uint8_t *on_bus, uint32_t cap, uint32_t *n_out)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !c->uploaded || !n_out) return fail(c, ESIM_ESTATE, "no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h;
+    const int rc = read_ctrl(c, &h);
+    if (rc) return rc;
+    const uint32_t t_done = c->host_t - 1u;                       // steps run so far
+    // log_off[TE_BIAS + s] = first entry of step s; the entries before step 1 are the seeds (simulator_builder.rs:1268-1287)
+    std::vector<uint32_t> off((size_t)t_done + 2u);
+    HIP_TRY(c, hipMemcpy(off.data(), c->d.log_off + TE_BIAS + 1u, sizeof(uint32_t) * (t_done + 1u), hipMemcpyDeviceToHost));
+    off[t_done + 1u] = h.log_len;
+    const uint32_t first = t_done ? off[0] : h.log_len, n = h.log_len - first;
+    *n_out = n;
+    if (n > cap || (n && (!citizen || !step || !on_bus))) return fail(c, ESIM_ERANGE, "esim_download_exposure_log: buffers too small (n_out holds the size needed)");
+    if (n == 0) return ESIM_OK;
+    DevTmp<uint32_t> d_c; DevTmp<uint8_t> d_b;
+    if (d_c.alloc(n) != hipSuccess || d_b.alloc(n) != hipSuccess) return fail(c, ESIM_ENOMEM, "esim_download_exposure_log: hipMalloc");
+    hipLaunchKernelGGL(k_export_log, dim3(grid_for(n, TPB, 2048)), dim3(TPB), 0, c->stream, c->d, first, n, d_c.p, d_b.p);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(citizen, d_c.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(on_bus, d_b.p, n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_download_exposure_log: ") + hipGetErrorString(e));
+    for (uint32_t s = 1; s <= t_done; ++s)
+        for (uint32_t i = off[s - 1u]; i < off[s] && i - first < n; ++i) step[i - first] = s;
+    return ESIM_OK;
+}
+
+// ---- per-Output-Area read-backs ----------------------------------------------------------------------------------------
+namespace {
+// the count table of esim_area_census zeroed and counted on the context's stream (esim_ensemble_fold reads it where it is)
+int enqueue_area_census(esim_ctx_impl *c, int where)
+{
+    const Dev &d = c->d;
+    const size_t n_out = (size_t)d.n_areas * 5u;
+    // stretches of whole workgroup passes, about 8192 of them at most: short enough to stay inside the LDS window of areas
+    const uint32_t per_block = (uint32_t)std::max<uint64_t>(4096u, (((uint64_t)d.n + 8191u) / 8192u + TPB - 1u) / TPB * TPB);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1u, ((uint64_t)d.n + per_block - 1u) / per_block);
+    HIP_TRY(c, hipMemsetAsync(c->area_cnt, 0, sizeof(uint32_t) * std::max<size_t>(1, n_out), c->stream));
+    hipLaunchKernelGGL(k_area_census, dim3(grid), dim3(TPB), 0, c->stream, d, where == ESIM_AREA_HOME ? 1 : 0, per_block, c->area_cnt);
+    return ESIM_OK;
+}
+
+// the count table of esim_group_census, the same way: four citizens per lane and trip, at most 1024 workgroups (four per
+// compute unit: every one of them ends with up to 4 * n_groups adds to the global table)
+int enqueue_group_census(esim_ctx_impl *c)
+{
+    const Dev &d = c->d;
+    HIP_TRY(c, hipMemsetAsync(c->grp.cnt, 0, sizeof(uint32_t) * (size_t)c->grp.n * 5u, c->stream));
+    hipLaunchKernelGGL(k_group_census, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 1024)), dim3(TPB), 0, c->stream, d, c->grp.lab, c->grp.n, c->grp.cnt);
+    hipLaunchKernelGGL(k_group_finish, dim3(grid_for(c->grp.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, c->grp.size, c->grp.n, c->grp.cnt);
+    return ESIM_OK;
+}
+
+// What the series derive from the records of the steps run (rec[1 .. t_done]): the at-work bit after the schedule arm of every
+// step (citizen.rs:176-206: the arm of step s runs iff no lockdown was in force, i.e. the record of step s - 1 has none) and
+// the steps at which it changes; the step that started the vaccination programme (0: none) and the first one that vaccinated
+// the whole eligible set (0xFFFFFFFF: none).
+struct RunShape { std::vector<uint8_t> aw; std::vector<uint32_t> tog; uint32_t trigger = 0, t_all = 0xFFFFFFFFu; };
+int run_shape(esim_ctx_impl *c, uint32_t t_done, RunShape *r)
+{
+    std::vector<esim_step_result> rec((size_t)t_done + 1u);
+    HIP_TRY(c, hipMemcpy(rec.data() + 1, c->d.records + 1, sizeof(esim_step_result) * t_done, hipMemcpyDeviceToHost));
+    r->aw.assign((size_t)t_done + 1u, 0);
+    for (uint32_t s = 1; s <= t_done; ++s) {
+        uint8_t cur = r->aw[s - 1u];
+        if (s == 1u || !rec[s - 1u].lockdown) {
+            const uint32_t hr = s % 24u;
+            if (hr == c->P.start_hour) cur = 1; else if (hr == c->P.end_hour) cur = 0;
+        }
+        r->aw[s] = cur;
+        if (cur != r->aw[s - 1u]) r->tog.push_back(s);
+        if (!r->trigger && rec[s].vaccination_active) r->trigger = s;
+        if (r->trigger && r->t_all == 0xFFFFFFFFu && rec[s].eligible_count <= c->P.vaccination_rate) r->t_all = s;
+    }
+    return ESIM_OK;
+}
+
+// vax_of[c] = the step at whose end citizen c was set Vaccinated, on the context's stream (steps that vaccinated the whole
+// eligible set apart: RunShape::t_all)
+hipError_t enqueue_vax_replay(esim_ctx_impl *c, uint32_t trigger, uint32_t t_done, uint32_t *d_vax)
+{
+    const hipError_t e = hipMemsetAsync(d_vax, 0xFF, sizeof(uint32_t) * (size_t)c->d.n, c->stream);
+    if (e == hipSuccess)
+        hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(t_done - trigger + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, c->d, trigger, t_done, d_vax);
+    return e;
+}
+
+// The tail of both census calls: the count table to its pinned mirror, one wait (the control block's read-back: the table is in
+// the mirror behind it), the mirror to the caller.
+int census_readback(esim_ctx_impl *c, const uint32_t *table, uint32_t *mirror, size_t n_out, uint32_t *counts)
+{
+    if (n_out) HIP_TRY(c, hipMemcpyAsync(mirror, table, sizeof(uint32_t) * n_out, hipMemcpyDeviceToHost, c->stream));
+    Ctrl h;
+    if (int rc = read_ctrl(c, &h)) return rc;
+    std::memcpy(counts, mirror, sizeof(uint32_t) * n_out);
+    return ctrl_error(c, h);
+}
+
+// esim_area_series and esim_group_series behind their own argument checks: n_rows rows of one column per area / group,
+// out[row * columns + column], counted from the exposure log on the device.  Rows that are a census over time (the areas'
+// Infected, a group's status) are summed up over the steps, and derived by replaying the vaccinations once a programme has run.
+int series_rows(esim_ctx_impl *c, bool by_group, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    const std::string who = by_group ? "esim_group_series" : "esim_area_series";
+    const bool status_rows = by_group ? what != ESIM_GROUP_SERIES_EXPOSURES : what == ESIM_SERIES_INFECTED;
+    const uint32_t t_done = c->host_t - 1u;                   // steps run so far
+    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
+        return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
+    RunShape shape;
+    if ((rc = run_shape(c, t_done, &shape))) return rc;
+    const bool replay = status_rows && shape.trigger != 0u;
+    if (replay && d.n_global != d.n)
+        return fail(c, ESIM_ESTATE, who + ": the " + (by_group ? "status" : "Infected") + " rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
+    const uint32_t cols = by_group ? c->grp.n : d.n_areas;
+    const size_t out_words = ((size_t)n_rows + 1u) * cols;
+    DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_tog, d_vax, d_out;          // (the areas' rows need the at-work bits, the groups' do not)
+    if ((!by_group && (d_aw.alloc(shape.aw.size()) != hipSuccess || d_tog.alloc(shape.tog.size()) != hipSuccess)) ||
+        d_out.alloc(out_words) != hipSuccess || (replay && d_vax.alloc(d.n) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, who + ": no device memory for the rows (ask for fewer)");
+    }
+    hipError_t e = hipSuccess;
+    if (!by_group) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && !by_group && !shape.tog.empty()) e = hipMemcpyAsync(d_tog.p, shape.tog.data(), sizeof(uint32_t) * shape.tog.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.p, 0, sizeof(uint32_t) * out_words, c->stream);
+    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax.p);
+    if (e == hipSuccess) {
+        AreaSeries q;
+        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done;
+        q.n_tog = by_group ? 0u : (uint32_t)shape.tog.size(); q.t_all = shape.t_all; q.at_work = d_aw.p; q.tog = d_tog.p; q.vax_of = d_vax.p; q.out = d_out.p;
+        if (by_group) {
+            const bool citizens = what == ESIM_VACCINATED || what == ESIM_SUSCEPTIBLE;   // (the pass over everybody Vaccinated)
+            hipLaunchKernelGGL(k_group_series, dim3(grid_for(citizens ? std::max<size_t>(d.n, h.log_len) : h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream,
+                               d, q, c->grp.lab, cols, h.log_len);
+        } else hipLaunchKernelGGL(k_area_series, dim3(grid_for(h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, h.log_len);
+        if (status_rows) hipLaunchKernelGGL(k_area_prefix, dim3(grid_for(cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d_out.p, n_rows, cols);
+        if (by_group && what == ESIM_SUSCEPTIBLE)
+            hipLaunchKernelGGL(k_group_s_rows, dim3(grid_for((size_t)n_rows * cols, TPB, 4096)), dim3(TPB), 0, c->stream, d_out.p, n_rows, cols, c->grp.size);
+        e = hipStreamSynchronize(c->stream);                      // (the host vectors above are done with here, too)
+    } else (void)hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, sizeof(uint32_t) * (size_t)n_rows * cols, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
+    return ESIM_OK;
+}
+}  // namespace
+
+extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!counts || (where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME)) return fail(c, ESIM_EINVAL, "esim_area_census: null output or unknown `where`");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_census: no population uploaded");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = enqueue_area_census(c, where)) return rc;
+    return census_readback(c, c->area_cnt, c->pin.area, (size_t)c->d.n_areas * 5u, counts);
+}
+
+// ---- per-Output-Area accumulators over the members of an ensemble ------------------------------------------------------
+extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if ((where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME && where != ESIM_BY_GROUP) || status_mask == 0u || (status_mask >> 5) != 0u)
+        return fail(c, ESIM_EINVAL, "esim_ensemble_begin: unknown `where`, or a status mask that is empty or names a status beyond ESIM_VACCINATED");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: no population uploaded");
+    if (where == ESIM_BY_GROUP && (!c->grp.lab || c->comm.world > 1)) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: by group without labels (esim_set_groups)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    // one allocation serves both kinds: the areas, or up to ESIM_MAX_GROUPS groups
+    const size_t na = std::max<size_t>(ESIM_MAX_GROUPS, c->d.n_areas);
+    if (!c->ens.hit) {
+        int rc;
+        uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
+        if ((rc = dev_alloc(c, &hit, na)) || (rc = dev_alloc(c, &sum, na)) || (rc = dev_alloc(c, &sq, na)) || (rc = dev_alloc(c, &mem, 1))) {
+            dev_free(c, hit); dev_free(c, sum); dev_free(c, sq); dev_free(c, mem);
+            return rc;
+        }
+        c->ens.hit = hit; c->ens.sum = sum; c->ens.sumsq = sq; c->ens.members = mem;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->ens.hit, 0, sizeof(uint32_t) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.sum, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.sumsq, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.members, 0, sizeof(uint32_t), c->stream));
+    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases;
+    c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_fold(esim_ctx *ctx)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!c->uploaded || !c->ens.hit || !c->ens.valid)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    int rc;
+    const bool by_group = c->ens.where == ESIM_BY_GROUP;
+    if ((rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, c->ens.where))) return rc;
+    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       by_group ? c->grp.cnt : c->area_cnt, c->ens.n, c->ens.mask, c->ens.min, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
+    HIP_TRY(c, hipGetLastError());
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!c->uploaded || !c->ens.hit || !c->ens.valid)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
+    const size_t na = c->ens.n;
+    if (members) HIP_TRY(c, hipMemcpy(members, c->ens.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hit && na) HIP_TRY(c, hipMemcpy(hit, c->ens.hit, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
+    if (sum && na) HIP_TRY(c, hipMemcpy(sum, c->ens.sum, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
+    if (sumsq && na) HIP_TRY(c, hipMemcpy(sumsq, c->ens.sumsq, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
+    return ctrl_error(c, h);
+}
+
+extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!out || (what != ESIM_SERIES_INFECTED && what != ESIM_SERIES_EXPOSURES) || stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_area_series: null output, unknown `what`, stride 0 or no rows");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_series: no population uploaded");
+    return series_rows(c, false, what, first_step, n_rows, stride, out);
+}
+
+// ---- read-backs by citizen group ---------------------------------------------------------------------------------------
+extern "C" int esim_set_groups(esim_ctx *ctx, const uint16_t *group, uint32_t n_groups)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_set_groups: no population uploaded");
+    if (c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_set_groups: the context has a communicator of several ranks (sharded groups are not built)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const uint32_t N = c->d.n;
+    std::vector<uint32_t> size;
+    if (group) {
+        if (n_groups == 0 || n_groups > ESIM_MAX_GROUPS) return fail(c, ESIM_EINVAL, "esim_set_groups: n_groups must be in 1..ESIM_MAX_GROUPS (1024)");
+        size.assign(n_groups, 0u);
+        for (uint32_t i = 0; i < N; ++i) {
+            if (group[i] >= n_groups) return fail(c, ESIM_EINVAL, "esim_set_groups: a label is not below n_groups");
+            size[group[i]]++;
+        }
+    }
+    uint16_t *lab = nullptr; uint32_t *sz = nullptr, *cnt = nullptr;
+    if (group) {
+        int rc;
+        if (!c->pin.grp) HIP_TRY(c, hipHostMalloc((void **)&c->pin.grp, sizeof(uint32_t) * ESIM_MAX_GROUPS * 5u, hipHostMallocDefault));
+        if ((rc = dev_alloc(c, &lab, N)) || (rc = dev_alloc(c, &sz, n_groups)) || (rc = dev_alloc(c, &cnt, (size_t)n_groups * 5u))) {
+            dev_free(c, lab); dev_free(c, sz); dev_free(c, cnt);
+            return rc;
+        }
+        hipError_t e = N ? hipMemcpy(lab, group, sizeof(uint16_t) * (size_t)N, hipMemcpyHostToDevice) : hipSuccess;
+        if (e == hipSuccess) e = hipMemcpy(sz, size.data(), sizeof(uint32_t) * n_groups, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            dev_free(c, lab); dev_free(c, sz); dev_free(c, cnt);
+            return fail(c, ESIM_ENODEVICE, std::string("esim_set_groups: ") + hipGetErrorString(e));
+        }
+    }
+    // the tables being replaced may still be read by work on the stream (a fold)
+    if (c->grp.lab) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dev_free(c, c->grp.lab); dev_free(c, c->grp.size); dev_free(c, c->grp.cnt);
+    c->grp.lab = lab; c->grp.size = sz; c->grp.cnt = cnt; c->grp.n = group ? n_groups : 0u;
+    if (c->ens.where == ESIM_BY_GROUP) c->ens.valid = false;
+    return ESIM_OK;
+}
+
+extern "C" int esim_group_census(esim_ctx *ctx, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!counts) return fail(c, ESIM_EINVAL, "esim_group_census: null output");
+    if (!c->uploaded || !c->grp.lab || c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_group_census: no population uploaded, or no labels (esim_set_groups)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = enqueue_group_census(c)) return rc;
+    return census_readback(c, c->grp.cnt, c->pin.grp, (size_t)c->grp.n * 5u, counts);
+}
+
+extern "C" int esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!out || what < ESIM_SUSCEPTIBLE || what > ESIM_GROUP_SERIES_EXPOSURES || stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_group_series: null output, unknown `what`, stride 0 or no rows");
+    if (!c->uploaded || !c->grp.lab || c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_group_series: no population uploaded, or no labels (esim_set_groups)");
+    return series_rows(c, true, what, first_step, n_rows, stride, out);
+}

@@ -9,7 +9,7 @@
 // It computes what k_chunk_marks -> k_chunk_fold -> k_chunk_draw -> k_chunk_units compute: an item's Infected per step are summed
 // from the interval records of the entries that name its key (iv_count), a room's school from those that name its building.
 // A chunk it cannot take (more than TINY_E Infected, a vaccination plan, shards) it turns into a no-op: the steps do not advance,
-// the host sees that in its read-back and enqueues the wide form (esim_api.hip run_steps).
+// the host sees that in its read-back and enqueues the wide form (esim_host_run.h run_steps).
 #pragma once
 
 #define TINY_E 64u                 // Infected (log entries) of a chunk the one-workgroup form takes
