@@ -60,9 +60,11 @@ struct Pinned {
 };
 
 // esim_restart: the distinct seeds on the device; control block and threshold LUT staged in pinned memory, an event behind their copies.
+// esim_restart_seeded: the list that replaces them goes through a pinned buffer of its own, behind the same event.
 struct RestartStaging {
-    uint32_t *seeds_dev = nullptr;
+    uint32_t *seeds_dev = nullptr; size_t seeds_cap = 0;      // room of the device list, in seeds
     struct Block { Ctrl h; uint64_t lut[512]; } *stage = nullptr;
+    uint32_t *seeds_stage = nullptr; size_t seeds_stage_n = 0;
     hipEvent_t ev = nullptr; bool ev_used = false;
 };
 
@@ -71,6 +73,7 @@ struct Ensemble {
     uint32_t *hit = nullptr, *members = nullptr;
     unsigned long long *sum = nullptr, *sumsq = nullptr;
     int where = ESIM_AREA_HOME; uint32_t mask = 0, min = 0;
+    bool arrival = false; uint32_t horizon = 0;   // esim_ensemble_begin_arrival: a member contributes its arrival step, reached = arrival <= horizon
     uint32_t n = 0; bool valid = false;           // entries in use (n_areas, or n_groups by group); false: the labels they were begun for are gone
 };
 
@@ -110,8 +113,10 @@ struct esim_ctx_impl {
     uint32_t n_routes = 0;
     size_t xa_n = 0, xb_n = 0, xf_n = 0;
     uint64_t pop_hash = 0;        // of the uploaded population arrays: a checkpoint only goes back into the population it came from
+    uint64_t pop_hash_head = 0;   // the same hash before it mixes the seeds (esim_restart_seeded finishes it with its own list)
     uint32_t cap_steps = 0;       // capacity of the record log (max_steps at esim_create)
     uint32_t *area_cnt = nullptr; // esim_area_census: the count table on the device, [n_areas * 5]
+    uint32_t *arrival = nullptr;  // esim_area_arrival: first exposure step per area or group, [max(n_areas, ESIM_MAX_GROUPS)] (nullptr before the first call)
     std::vector<void *> allocs;   // device allocations
     // where the run stands, as the host knows it (rewind_host takes it back to step 0)
     uint32_t host_t = 1;                        // next time step to enqueue
@@ -355,7 +360,7 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_device(c);
     c->tm.destroy();
-    for (void *p : { (void *)c->pin.ctrl, (void *)c->pin.rec, (void *)c->pin.area, (void *)c->pin.grp, (void *)c->rs.stage })
+    for (void *p : { (void *)c->pin.ctrl, (void *)c->pin.rec, (void *)c->pin.area, (void *)c->pin.grp, (void *)c->rs.stage, (void *)c->rs.seeds_stage })
         if (p) (void)hipHostFree(p);
     if (c->rs.ev) (void)hipEventDestroy(c->rs.ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -92,6 +92,52 @@ int enqueue_group_census(esim_ctx_impl *c)
     return ESIM_OK;
 }
 
+// the table of esim_area_arrival filled with ESIM_NEVER and lowered on the context's stream, for the steps run so far as the
+// host knows them (esim_ensemble_fold reads it where it is).  The log's length is the device's to know: the grid covers the
+// longest log there can be, a lane per citizen, capped at 1024 workgroups, and strides over what the control block says.
+int enqueue_arrival(esim_ctx_impl *c, int where)
+{
+    const Dev &d = c->d;
+    const size_t room = std::max<size_t>(ESIM_MAX_GROUPS, d.n_areas);
+    if (!c->arrival) { if (int rc = dev_alloc(c, &c->arrival, room)) return rc; }
+    const bool by_group = where == ESIM_BY_GROUP;
+    const uint32_t n_keys = by_group ? c->grp.n : d.n_areas;
+    HIP_TRY(c, hipMemsetAsync(c->arrival, 0xFF, sizeof(uint32_t) * std::max<size_t>(1, n_keys), c->stream));
+    hipLaunchKernelGGL(k_area_arrival, dim3(grid_for(d.n, TPB, 1024)), dim3(TPB), 0, c->stream, d, by_group ? c->grp.lab : nullptr, n_keys,
+                       c->host_t - 1u, c->arrival);
+    return ESIM_OK;
+}
+
+// `where` of the arrival calls: by household area or by group; the area a citizen stands in is not built.
+int arrival_check(esim_ctx_impl *c, int where, const std::string &who)
+{
+    if (where != ESIM_AREA_HOME && where != ESIM_BY_GROUP) return fail(c, ESIM_EINVAL, who + ": `where` must be ESIM_AREA_HOME or ESIM_BY_GROUP");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, who + ": no population uploaded");
+    if (where == ESIM_BY_GROUP && (!c->grp.lab || c->comm.world > 1)) return fail(c, ESIM_ESTATE, who + ": by group without labels (esim_set_groups)");
+    return ESIM_OK;
+}
+
+// The accumulators allocated at the first begin -- one allocation serves both kinds: the areas, or up to ESIM_MAX_GROUPS
+// groups -- and zeroed on the stream.
+int ensemble_zero(esim_ctx_impl *c)
+{
+    const size_t na = std::max<size_t>(ESIM_MAX_GROUPS, c->d.n_areas);
+    if (!c->ens.hit) {
+        int rc;
+        uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
+        if ((rc = dev_alloc(c, &hit, na)) || (rc = dev_alloc(c, &sum, na)) || (rc = dev_alloc(c, &sq, na)) || (rc = dev_alloc(c, &mem, 1))) {
+            dev_free(c, hit); dev_free(c, sum); dev_free(c, sq); dev_free(c, mem);
+            return rc;
+        }
+        c->ens.hit = hit; c->ens.sum = sum; c->ens.sumsq = sq; c->ens.members = mem;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->ens.hit, 0, sizeof(uint32_t) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.sum, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.sumsq, 0, sizeof(unsigned long long) * na, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->ens.members, 0, sizeof(uint32_t), c->stream));
+    return ESIM_OK;
+}
+
 // What the series derive from the records of the steps run (rec[1 .. t_done]): the at-work bit after the schedule arm of every
 // step (citizen.rs:176-206: the arm of step s runs iff no lockdown was in force, i.e. the record of step s - 1 has none) and
 // the steps at which it changes; the step that started the vaccination programme (0: none) and the first one that vaccinated
@@ -199,6 +245,19 @@ extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
     return census_readback(c, c->area_cnt, c->pin.area, (size_t)c->d.n_areas * 5u, counts);
 }
 
+// The step of the first exposure per Output Area (of the household) or per group, from the exposure log where it lies.
+extern "C" int esim_area_arrival(esim_ctx *ctx, int where, uint32_t *step_out)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!step_out) return fail(c, ESIM_EINVAL, "esim_area_arrival: null output");
+    if (int rc = arrival_check(c, where, "esim_area_arrival")) return rc;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = enqueue_arrival(c, where)) return rc;
+    const bool by_group = where == ESIM_BY_GROUP;
+    HIP_TRY(c, hipGetLastError());
+    return census_readback(c, c->arrival, by_group ? c->pin.grp : c->pin.area, by_group ? c->grp.n : c->d.n_areas, step_out);
+}
+
 // ---- per-Output-Area accumulators over the members of an ensemble ------------------------------------------------------
 extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases)
 {
@@ -208,22 +267,19 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: no population uploaded");
     if (where == ESIM_BY_GROUP && (!c->grp.lab || c->comm.world > 1)) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: by group without labels (esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    // one allocation serves both kinds: the areas, or up to ESIM_MAX_GROUPS groups
-    const size_t na = std::max<size_t>(ESIM_MAX_GROUPS, c->d.n_areas);
-    if (!c->ens.hit) {
-        int rc;
-        uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
-        if ((rc = dev_alloc(c, &hit, na)) || (rc = dev_alloc(c, &sum, na)) || (rc = dev_alloc(c, &sq, na)) || (rc = dev_alloc(c, &mem, 1))) {
-            dev_free(c, hit); dev_free(c, sum); dev_free(c, sq); dev_free(c, mem);
-            return rc;
-        }
-        c->ens.hit = hit; c->ens.sum = sum; c->ens.sumsq = sq; c->ens.members = mem;
-    }
-    HIP_TRY(c, hipMemsetAsync(c->ens.hit, 0, sizeof(uint32_t) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.sum, 0, sizeof(unsigned long long) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.sumsq, 0, sizeof(unsigned long long) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.members, 0, sizeof(uint32_t), c->stream));
-    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases;
+    if (int rc = ensemble_zero(c)) return rc;
+    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases; c->ens.arrival = false;
+    c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t horizon)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (int rc = arrival_check(c, where, "esim_ensemble_begin_arrival")) return rc;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = ensemble_zero(c)) return rc;
+    c->ens.where = where; c->ens.arrival = true; c->ens.horizon = horizon;
     c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
     return ESIM_OK;
 }
@@ -236,6 +292,13 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;
     const bool by_group = c->ens.where == ESIM_BY_GROUP;
+    if (c->ens.arrival) {
+        if ((rc = enqueue_arrival(c, c->ens.where))) return rc;
+        hipLaunchKernelGGL(k_ensemble_fold_arrival, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                           c->arrival, c->ens.n, c->ens.horizon, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
+        HIP_TRY(c, hipGetLastError());
+        return ESIM_OK;
+    }
     if ((rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, c->ens.where))) return rc;
     hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
                        by_group ? c->grp.cnt : c->area_cnt, c->ens.n, c->ens.mask, c->ens.min, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);

@@ -61,18 +61,30 @@ int upload_validate(esim_ctx_impl *c, UploadHost &u)
     return ESIM_OK;
 }
 
-// FNV-1a over what the path reads of the population (checkpoints carry it, esim_checkpoint_restore compares it)
-uint64_t population_hash(const esim_population *pop)
+// FNV-1a over what the path reads of the population (checkpoints carry it, esim_checkpoint_restore compares it).  The seeds
+// come last: *head receives the state before them, so that esim_restart_seeded can finish the hash with the list in force.
+void fnv_mix(uint64_t &h, const void *p, size_t nbytes)
+{
+    const uint8_t *q = (const uint8_t *)p;
+    for (size_t i = 0; i < nbytes; ++i) { h ^= q[i]; h *= 0x100000001b3ull; }
+}
+
+uint64_t hash_with_seeds(uint64_t head, const uint32_t *seeds, uint32_t n_seeds)
+{
+    if (n_seeds) fnv_mix(head, seeds, sizeof(uint32_t) * (size_t)n_seeds);
+    return head;
+}
+
+uint64_t population_hash(const esim_population *pop, uint64_t *head)
 {
     const size_t N = pop->n_citizens, B = pop->n_buildings, R = pop->n_rooms;
     uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](const void *p, size_t nbytes) { const uint8_t *q = (const uint8_t *)p; for (size_t i = 0; i < nbytes; ++i) { h ^= q[i]; h *= 0x100000001b3ull; } };
-    mix(pop->home_building, sizeof(uint32_t) * N); mix(pop->work_building, sizeof(uint32_t) * N);
-    mix(pop->room, sizeof(uint32_t) * N); mix(pop->flags, N);
-    mix(pop->building_area, sizeof(uint32_t) * B); mix(pop->building_type, B);
-    if (R) mix(pop->room_building, sizeof(uint32_t) * R);
-    if (pop->n_seeds) mix(pop->seeds, sizeof(uint32_t) * (size_t)pop->n_seeds);
-    return h;
+    fnv_mix(h, pop->home_building, sizeof(uint32_t) * N); fnv_mix(h, pop->work_building, sizeof(uint32_t) * N);
+    fnv_mix(h, pop->room, sizeof(uint32_t) * N); fnv_mix(h, pop->flags, N);
+    fnv_mix(h, pop->building_area, sizeof(uint32_t) * B); fnv_mix(h, pop->building_type, B);
+    if (R) fnv_mix(h, pop->room_building, sizeof(uint32_t) * R);
+    *head = h;
+    return hash_with_seeds(h, pop->seeds, pop->n_seeds);
 }
 
 // ---- public transport routes: riders sharing (home area, work area), simulator.rs:181-186.
@@ -133,7 +145,8 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     c->comm.fn = nullptr; c->comm.user = nullptr; c->comm.rank = 0; c->comm.world = 1;
     c->comm.xr = nullptr; c->comm.xr_n = 0;
     free_device(c);
-    c->rs.seeds_dev = nullptr;                                     // (freed with the rest; the ensemble accumulators go with the population)
+    c->rs.seeds_dev = nullptr; c->rs.seeds_cap = 0;                // (freed with the rest; the ensemble accumulators go with the population)
+    c->arrival = nullptr;
     c->ens.hit = c->ens.members = nullptr; c->ens.sum = c->ens.sumsq = nullptr;
     c->ens.valid = false;
     c->grp = Groups();                                             // (the labels belong to the population they were set for)
@@ -269,7 +282,7 @@ int upload_step_tables(esim_ctx_impl *c, const UploadHost &u)
         // the distinct seeds, for esim_restart (which writes their words and the head of the log from this array)
         const uint32_t *sd = nullptr;
         if ((rc = dev_upload(c, &sd, c->init_log.data(), c->init_log.size()))) return rc;
-        c->rs.seeds_dev = const_cast<uint32_t *>(sd);
+        c->rs.seeds_dev = const_cast<uint32_t *>(sd); c->rs.seeds_cap = c->init_log.size();
     }
     uint64_t lut[512];
     esim_threshold_lut(&c->P, lut);
@@ -366,7 +379,7 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     u.pop = pop; u.N = pop->n_citizens; u.B = pop->n_buildings; u.R = pop->n_rooms;
     int rc;
     if ((rc = upload_validate(c, u))) return rc;
-    c->pop_hash = population_hash(pop);
+    c->pop_hash = population_hash(pop, &c->pop_hash_head);
     upload_routes(u);
     upload_member_lists(u);
     // initial state: everyone Susceptible at home (citizen.rs:139-162), seeds Infected(0)
@@ -440,43 +453,110 @@ extern "C" int esim_reset(esim_ctx *ctx)
     return ESIM_OK;
 }
 
-// esim_reset with new parameters and without the host: nothing here waits for the stream or copies anything proportional to
-// the population.  Host -> device go the control block and the threshold LUT (4.4 KB, from pinned memory); the citizen words,
-// the seeds' words, the census histogram and the log offsets are written by kernels, the rest is cleared or copied on the device.
-extern "C" int esim_restart(esim_ctx *ctx, const esim_params *p)
+namespace {
+
+// What esim_restart and esim_restart_seeded refuse alike.
+int restart_check(esim_ctx_impl *c, const esim_params *p, const std::string &who)
 {
-    esim_ctx_impl *c = CTX(ctx);
-    if (!c || !p) return fail(c, ESIM_EINVAL, "esim_restart: null argument");
-    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_restart: no population uploaded");
-    if (c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_restart: the context has a communicator of several ranks (the shards would have to agree on the parameters)");
-    if (int rc = check_params(c, p, "esim_restart")) return rc;
-    if (p->device != c->P.device) return fail(c, ESIM_EINVAL, "esim_restart: device must be the context's device");
-    if (p->max_steps > c->cap_steps) return fail(c, ESIM_ERANGE, "esim_restart: max_steps above the max_steps the context was created with (the record log's capacity)");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, who + ": no population uploaded");
+    if (c->comm.world > 1) return fail(c, ESIM_ESTATE, who + ": the context has a communicator of several ranks (the shards would have to agree on the parameters)");
+    if (int rc = check_params(c, p, who)) return rc;
+    if (p->device != c->P.device) return fail(c, ESIM_EINVAL, who + ": device must be the context's device");
+    if (p->max_steps > c->cap_steps) return fail(c, ESIM_ERANGE, who + ": max_steps above the max_steps the context was created with (the record log's capacity)");
+    return ESIM_OK;
+}
+
+// esim_reset with new parameters and without the host: nothing here waits for the stream or copies anything proportional to
+// the population.  Host -> device go the control block and the threshold LUT (4.4 KB, from pinned memory) and, when the seeds
+// are replaced, the distinct ones among them (4 B each, from pinned memory); the citizen words, the seeds' words, the census
+// histogram and the log offsets are written by kernels, the rest is cleared or copied on the device.
+// seeds != nullptr or replace: the distinct citizens of seeds[0 .. n_seeds), in the order of their first occurrence, become the
+// seeds in force; every index has been checked by the caller.
+int restart_enqueue(esim_ctx_impl *c, const esim_params *p, bool replace, const uint32_t *seeds, uint32_t n_seeds)
+{
     HIP_TRY(c, hipSetDevice(c->P.device));
-    // the staging block is the source of the previous restart's two copies: they are long done unless restarts follow each
+    // the staging blocks are the source of the previous restart's copies: they are long done unless restarts follow each
     // other with nothing in between (then this waits for those copies, not for the stream)
     if (c->rs.ev_used) HIP_TRY(c, hipEventSynchronize(c->rs.ev));
+    if (replace) {
+        // whatever can fail comes before the first change of the context: room for the list in pinned memory and on the device
+        // (a longer device list takes the place of the old one: hipFree waits for the work that still reads that one)
+        if (int rc = pinned_grow(c, &c->rs.seeds_stage, &c->rs.seeds_stage_n, n_seeds)) return rc;
+        if (n_seeds > c->rs.seeds_cap) {
+            uint32_t *grown = nullptr;
+            if (int rc = dev_alloc(c, &grown, n_seeds)) return rc;
+            dev_free(c, c->rs.seeds_dev);
+            c->rs.seeds_dev = grown; c->rs.seeds_cap = n_seeds;
+        }
+    }
     c->P = *p;
     params_to_dev(c);
     const Dev &d = c->d;
-    const uint32_t n_seeds = (uint32_t)c->init_log.size();
     const uint32_t te = seed_te(c);
-    for (uint32_t sc : c->init_log) c->init_state[sc] = CW_MAKE(te, c->init_state[sc] & CW_FLAGS);   // (esim_reset's copy of the seeds' words)
+    if (replace) {
+        // the old seeds' words back to Susceptible, the new ones set: O(old + new); a word that is set already is a duplicate
+        // (esim_upload_population tells them the same way)
+        for (uint32_t sc : c->init_log) c->init_state[sc] = CW_MAKE(TE_SUSCEPTIBLE, c->init_state[sc] & CW_FLAGS);
+        c->init_log.clear();
+        for (uint32_t i = 0; i < n_seeds; ++i) {
+            const uint32_t sc = seeds[i];
+            if (CW_TE(c->init_state[sc]) != te) { c->init_state[sc] = CW_MAKE(te, c->init_state[sc] & CW_FLAGS); c->init_log.push_back(sc); }
+        }
+        c->pop_hash = hash_with_seeds(c->pop_hash_head, seeds, n_seeds);
+        if (!c->init_log.empty()) std::memcpy(c->rs.seeds_stage, c->init_log.data(), sizeof(uint32_t) * c->init_log.size());
+    } else
+        for (uint32_t sc : c->init_log) c->init_state[sc] = CW_MAKE(te, c->init_state[sc] & CW_FLAGS);   // (esim_reset's copy of the seeds' words)
+    const uint32_t n_seeds_now = (uint32_t)c->init_log.size();
     Ctrl &h = c->rs.stage->h;
     initial_ctrl(c, &h);
     esim_threshold_lut(&c->P, c->rs.stage->lut);
     HIP_TRY(c, hipMemcpyAsync(d.ctrl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(const_cast<uint64_t *>(d.thr), c->rs.stage->lut, sizeof c->rs.stage->lut, hipMemcpyHostToDevice, c->stream));
+    if (replace && n_seeds_now) HIP_TRY(c, hipMemcpyAsync(c->rs.seeds_dev, c->rs.seeds_stage, sizeof(uint32_t) * n_seeds_now, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->rs.ev, c->stream));
     c->rs.ev_used = true;
     if (d.n) hipLaunchKernelGGL(k_restart_words, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, d.cit, d.n);
     HIP_TRY(c, hipMemsetAsync(c->cnt_base, 0, c->cnt_bytes, c->stream));
     HIP_TRY(c, hipMemsetAsync(d.exp_step, 0, sizeof(uint32_t) * 2 * ((size_t)c->cap_steps + 2), c->stream));
     HIP_TRY(c, hipMemsetAsync(d.records, 0, sizeof(esim_step_result) * ((size_t)c->cap_steps + 1), c->stream));
-    hipLaunchKernelGGL(k_restart_books, dim3(grid_for(std::max<size_t>(TE_SLOTS + 1u, n_seeds), TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
-                       d.cit, d.n, c->rs.seeds_dev, n_seeds, te, d.hist, d.log_off);
-    if (n_seeds) HIP_TRY(c, hipMemcpyAsync(d.log, c->rs.seeds_dev, sizeof(uint32_t) * n_seeds, hipMemcpyDeviceToDevice, c->stream));
+    hipLaunchKernelGGL(k_restart_books, dim3(grid_for(std::max<size_t>(TE_SLOTS + 1u, n_seeds_now), TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       d.cit, d.n, c->rs.seeds_dev, n_seeds_now, te, d.hist, d.log_off);
+    if (n_seeds_now) HIP_TRY(c, hipMemcpyAsync(d.log, c->rs.seeds_dev, sizeof(uint32_t) * n_seeds_now, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipGetLastError());
     rewind_host(c);
+    return ESIM_OK;
+}
+
+}  // namespace
+
+extern "C" int esim_restart(esim_ctx *ctx, const esim_params *p)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !p) return fail(c, ESIM_EINVAL, "esim_restart: null argument");
+    if (int rc = restart_check(c, p, "esim_restart")) return rc;
+    return restart_enqueue(c, p, false, nullptr, 0);
+}
+
+extern "C" int esim_restart_seeded(esim_ctx *ctx, const esim_params *p, const uint32_t *seeds, uint32_t n_seeds)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !p) return fail(c, ESIM_EINVAL, "esim_restart_seeded: null argument");
+    if (int rc = restart_check(c, p, "esim_restart_seeded")) return rc;
+    if (n_seeds && !seeds) return fail(c, ESIM_EINVAL, "esim_restart_seeded: seeds is NULL");
+    if (n_seeds > c->d.n) return fail(c, ESIM_ERANGE, "esim_restart_seeded: more seeds than citizens");
+    for (uint32_t i = 0; i < n_seeds; ++i)
+        if (seeds[i] >= c->d.n) return fail(c, ESIM_EINVAL, "esim_restart_seeded: seed index out of range");
+    return restart_enqueue(c, p, true, seeds, n_seeds);
+}
+
+extern "C" int esim_get_seeds(esim_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n_out)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !n_out) return fail(c, ESIM_EINVAL, "esim_get_seeds: null argument");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_get_seeds: no population uploaded");
+    const uint32_t n = (uint32_t)c->init_log.size();
+    *n_out = n;
+    if (n > cap || (n && !out)) return fail(c, ESIM_ERANGE, "esim_get_seeds: buffer too small (n_out holds the size needed)");
+    if (n) std::memcpy(out, c->init_log.data(), sizeof(uint32_t) * n);
     return ESIM_OK;
 }

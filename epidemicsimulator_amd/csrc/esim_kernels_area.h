@@ -1,5 +1,6 @@
 // esim_kernels_area.h -- per-Output-Area read-backs: the census by area as it stands (esim_area_census) and, after the
-// fact, per-area rows over the steps already run (esim_area_series).  Nothing here writes simulation state.
+// fact, per-area rows over the steps already run (esim_area_series) and the step at which the epidemic first reached every
+// area or citizen group (esim_area_arrival).  Nothing here writes simulation state.
 #pragma once
 
 #define AREA_WINDOW 256u           // areas whose counters a workgroup of k_area_census keeps in LDS
@@ -77,6 +78,27 @@ __device__ __forceinline__ uint32_t log_te(const Dev &d, uint32_t i, uint32_t k_
         if (d.log_off[mid] <= i) lo = mid; else hi = mid - 1u;
     }
     return lo;
+}
+
+// ---- esim_area_arrival ------------------------------------------------------------------------------------------------
+// first[key] = the earliest exposure step among the log's entries with that key (the table is filled with ESIM_NEVER by the
+// caller), key = the Output Area of the citizen's household, or its label where grp is given.  A lane per exposure-log entry,
+// grid-stride; the length of the log is read from the control block, so nobody has to wait for it on the host.  The step
+// comes from the entry's position (log_te); the seeds, "exposed" before step 1, count as step 0.  The log is in time order:
+// once a key has its first entry, almost every later one loses the comparison against a plain load of the table and issues
+// nothing -- a stale value read there is never smaller than the true one, so it costs an atomic at most, never a result.
+// The atomics stay near the number of keys reached instead of the number of entries.
+__global__ __launch_bounds__(TPB) void k_area_arrival(Dev d, const uint16_t *grp, uint32_t n_keys, uint32_t t_done, uint32_t *first)
+{
+    const uint32_t log_len = d.ctrl->log_len < d.n ? d.ctrl->log_len : d.n;
+    for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < log_len; i += gridDim.x * TPB) {
+        const uint32_t c = d.log[i];
+        if (c >= d.n) continue;
+        const uint32_t te = log_te(d, i, t_done + TE_BIAS);
+        const uint32_t s = te > TE_BIAS ? te - TE_BIAS : 0u;
+        const uint32_t key = grp ? (uint32_t)grp[c] : d.bld_area[d.home[c]];
+        if (key < n_keys && s < first[key]) atomicMin(&first[key], s);
+    }
 }
 
 // A citizen stands in `area` during the steps [p, e], first <= p: +1 at the first row inside, -1 behind the last one.

@@ -1,5 +1,6 @@
 // esim_kernels_restart.h -- ensembles on one uploaded population: the initial state rebuilt on the device (esim_restart)
-// and the per-Output-Area accumulators over the members of an ensemble (esim_ensemble_fold).  No stepping kernel is here.
+// and the per-Output-Area accumulators over the members of an ensemble (esim_ensemble_fold), by census or by arrival step.
+// No stepping kernel is here.
 #pragma once
 
 // Every citizen back to Susceptible: the static flags are all of the word that survives.  A pure stream over 4 B per
@@ -46,6 +47,21 @@ __global__ __launch_bounds__(TPB) void k_ensemble_fold(const uint32_t *counts, u
 #pragma unroll
     for (uint32_t s = 0; s < 5u; ++s) if ((mask >> s) & 1u) x += counts[(size_t)a * 5u + s];
     if (x >= min_cases) hit[a] += 1u;
+    sum[a] += x;
+    sumsq[a] += (unsigned long long)x * x;
+}
+
+// The same for accumulators begun with esim_ensemble_begin_arrival: x = the step at which the member's epidemic first
+// reached the entry (k_area_arrival has just filled `first`), counted only where it did so by the horizon.
+__global__ __launch_bounds__(TPB) void k_ensemble_fold_arrival(const uint32_t *first, uint32_t n, uint32_t horizon,
+                                                               uint32_t *hit, unsigned long long *sum, unsigned long long *sumsq, uint32_t *members)
+{
+    const uint32_t a = blockIdx.x * TPB + threadIdx.x;
+    if (a == 0u) *members += 1u;
+    if (a >= n) return;
+    const uint32_t x = first[a];
+    if (x == ESIM_NEVER || x > horizon) return;
+    hit[a] += 1u;
     sum[a] += x;
     sumsq[a] += (unsigned long long)x * x;
 }

@@ -1,6 +1,7 @@
 """Ensembles of one uploaded population: many Philox seeds of one world, or the same world under several parameter sets,
-one member after another on ONE context (esim_restart), summarised per step on the host and per Output Area -- or per
-citizen group -- on the device (esim_ensemble_*).  The population is validated, hashed and uploaded once."""
+or under other index cases (where the outbreak starts), one member after another on ONE context (esim_restart,
+esim_restart_seeded), summarised per step on the host and per Output Area -- or per citizen group -- on the device
+(esim_ensemble_*).  The population is validated, hashed and uploaded once."""
 import ctypes as C
 import json
 import os
@@ -41,6 +42,22 @@ def area_summary(members, hit, total, sumsq):
     return {"members": m, "hit": np.asarray(hit, np.uint32), "mean": mean, "var": var}
 
 
+def arrival_summary(members, hit, total, sumsq):
+    """members, hit (members whose epidemic reached the entry by the horizon), and over those members the mean = sum / hit and
+    the population variance of the arrival step; both NaN where hit == 0."""
+    hit = np.asarray(hit, np.uint32)
+    total, sumsq, h = np.asarray(total, np.float64), np.asarray(sumsq, np.float64), hit.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(hit > 0, total / h, np.nan)
+        var = np.where(hit > 0, np.maximum(sumsq / h - mean * mean, 0.0), np.nan)
+    return {"members": int(members), "hit": hit, "mean": mean, "var": var}
+
+
+def _json_number(x):
+    x = float(x)
+    return None if x != x else x          # NaN (an arrival mean nobody contributed to) is written as null
+
+
 class EnsembleResult:
     def __init__(self, records, n_done, members, area=None, area_codes=None):
         self.records = records            # structured [members, n_steps]
@@ -62,7 +79,8 @@ class EnsembleResult:
 
     def dump(self, directory):
         """ensemble_stats.json: per field the mean and the 5/25/50/75/95 % rows over the members; ensemble_areas.json: hit, mean
-        and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index."""
+        and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index (an arrival
+        summary's mean and var are null where hit is 0)."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -75,7 +93,7 @@ class EnsembleResult:
             a = self.area
             key = (lambda i: self.area_codes[i]) if self.area_codes is not None else (lambda i: str(i))
             doc = {"members": a["members"],
-                   "areas": {key(i): {"hit": int(a["hit"][i]), "mean": float(a["mean"][i]), "var": float(a["var"][i])} for i in range(len(a["hit"]))}}
+                   "areas": {key(i): {"hit": int(a["hit"][i]), "mean": _json_number(a["mean"][i]), "var": _json_number(a["var"][i])} for i in range(len(a["hit"]))}}
         with open(os.path.join(directory, "ensemble_areas.json"), "w") as fh:
             json.dump(doc, fh)
 
@@ -91,22 +109,46 @@ class Ensemble:
         self.area_codes = area_codes
         self.base = _lib.Params()
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
+        self._own_seeds = True            # the seeds in force are the uploaded population's
 
     @staticmethod
     def seeds(k, first=1):
         return [{"seed": int(first) + i} for i in range(int(k))]
 
+    def index_cases(self, k, n=10, first=1):
+        """k members that differ in where the outbreak starts AND in the Philox seed: member i runs under seed first + i from
+        the index cases Population.draw_index_cases(n, first + i) draws (n = 10: STARTING_INFECTED_COUNT, config.rs:27)."""
+        pop = self.simulator.population
+        return [{"seed": int(first) + i, "index_cases": pop.draw_index_cases(n, int(first) + i).tolist()} for i in range(int(k))]
+
     def run(self, members, n_steps, stop_when_done=False, area=None):
-        """members: iterable of override dicts (Ensemble.seeds); area: None, or the arguments of esim_ensemble_begin as a dict
-        (where, status_mask, min_cases); where="group" counts by the groups given to Ensemble(...), and the summary then has
-        one entry per group.  Returns an EnsembleResult."""
+        """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may
+        carry "index_cases": the citizens that start Infected in that member (one without starts from the population's own).
+        area: None, or the arguments of esim_ensemble_begin as a dict (where, status_mask, min_cases); where="group" counts by
+        the groups given to Ensemble(...), and the summary then has one entry per group; or dict(kind="arrival", where=...,
+        horizon=...) for the arrival step instead (esim_ensemble_begin_arrival; the summary's mean and var are then over the
+        members that reached the entry, NaN where none did).  Returns an EnsembleResult."""
         sim = self.simulator
         members = [dict(m) for m in members]
+        for m in members:
+            if "index_cases" in m:
+                m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
+        arrival = False
         if area is not None:
-            sim.ensemble_begin(**area)
+            area = dict(area)
+            kind = area.pop("kind", "census")
+            if kind not in ("census", "arrival"):
+                raise ValueError("Ensemble.run: area kind must be 'census' or 'arrival', got %r" % (kind,))
+            arrival = kind == "arrival"
+            (sim.ensemble_begin_arrival if arrival else sim.ensemble_begin)(**area)
         rows, n_done = [], []
         for m in members:
-            sim.restart(self.base, **m)
+            over = {k: v for k, v in m.items() if k != "index_cases"}
+            seeds = m.get("index_cases")
+            if seeds is None and not self._own_seeds:
+                seeds = sim.population.seeds
+            sim.restart(self.base, seeds=seeds, **over)
+            self._own_seeds = "index_cases" not in m
             rec = sim.run(n_steps, stop_when_done=stop_when_done)
             if area is not None:
                 sim.ensemble_fold()
@@ -116,7 +158,7 @@ class Ensemble:
         summary = None
         if area is not None:
             r = sim.ensemble_read()
-            summary = area_summary(r["members"], r["hit"], r["sum"], r["sumsq"])
+            summary = (arrival_summary if arrival else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
         return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
 

@@ -143,6 +143,33 @@ class Population:
         """(labels uint16 [n_citizens], n_groups): the occupation byte as the label, n_groups = the largest one + 1."""
         return self.occupation.astype(np.uint16), (int(self.occupation.max()) + 1 if self.n_citizens else 1)
 
+    # -- index cases (Simulator.restart(seeds=...)) -------------------------------------------
+    def residents_by_area(self):
+        """(order, offsets): order[offsets[a]:offsets[a + 1]] are the citizens whose household lies in Output Area a, in
+        ascending index.  Built once and kept."""
+        if getattr(self, "_residents", None) is None:
+            area = self.building_area[self.home_building] if self.n_citizens else np.zeros(0, np.uint32)
+            order = np.argsort(area, kind="stable").astype(np.uint32)
+            offsets = np.concatenate([[0], np.cumsum(np.bincount(area, minlength=self.n_areas))]).astype(np.int64)
+            self._residents = (order, offsets)
+        return self._residents
+
+    def draw_index_cases(self, n, seed):
+        """Index cases the way SimulatorBuilder::apply_initial_infections draws them (simulator_builder.rs:1111-1142): n times,
+        an Output Area uniformly over ALL areas, then one of its residents uniformly.  An area without residents yields
+        nobody for that draw (the reference's `continue`), so fewer than n may come back; the same citizen may come back
+        twice (the library counts it once).  numpy.random.default_rng(seed): the same seed, the same list."""
+        rng = np.random.default_rng(seed)
+        n = int(n)
+        if n <= 0 or self.n_areas == 0:
+            return np.zeros(0, np.uint32)
+        order, offsets = self.residents_by_area()
+        area = rng.integers(0, self.n_areas, size=n)
+        count = offsets[area + 1] - offsets[area]
+        pick = rng.integers(0, np.maximum(count, 1))
+        keep = count > 0
+        return order[offsets[area[keep]] + pick[keep]].astype(np.uint32)
+
     def even_cuts(self, n_shards):
         """Area boundaries giving each shard about the same number of citizens."""
         area_of_citizen = self.building_area[self.home_building]

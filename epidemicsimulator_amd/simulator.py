@@ -199,25 +199,52 @@ class Simulator:
         self.statistics_recorder = StatisticsRecorder()
         self._steps = 0
 
-    def restart(self, params=None, **overrides):
+    def restart(self, params=None, seeds=None, **overrides):
         """Back to step 0 under other parameters without a new upload (esim_restart): `params`, or the current parameters
-        changed by `overrides` (e.g. seed=7).  The initial state is rebuilt on the device; the call does not wait for it."""
+        changed by `overrides` (e.g. seed=7).  The initial state is rebuilt on the device; the call does not wait for it.
+        seeds: None keeps the initially infected citizens in force; an array of citizen indices replaces them
+        (esim_restart_seeded; Population.draw_index_cases draws such a list the way the reference's builder does)."""
         p = _lib.Params()
         C.memmove(C.byref(p), C.byref(params if params is not None else self.params), C.sizeof(_lib.Params))
         for k, v in overrides.items():
             if not hasattr(p, k):
                 raise AttributeError("esim_params has no field %r" % k)
             setattr(p, k, v)
-        _lib.check(self.lib.esim_restart(self._ctx, C.byref(p)), self._ctx)
+        if seeds is None:
+            _lib.check(self.lib.esim_restart(self._ctx, C.byref(p)), self._ctx)
+        else:
+            raw = np.asarray(seeds)
+            if raw.ndim != 1 or (raw.size and (raw.dtype.kind not in "iu" or int(raw.min()) < 0 or int(raw.max()) > 0xFFFFFFFF)):
+                raise ValueError("restart: seeds must be a one-dimensional array of citizen indices")
+            arr = np.ascontiguousarray(raw, np.uint32)
+            _lib.check(self.lib.esim_restart_seeded(self._ctx, C.byref(p), arr.ctypes.data_as(C.POINTER(C.c_uint32)), arr.size), self._ctx)
         self.params = p
         self.statistics_recorder = StatisticsRecorder()
         self._steps = 0
+
+    def seeds(self):
+        """The distinct initially infected citizens in force, in the order of the exposure log (esim_get_seeds)."""
+        n = C.c_uint32(0)
+        rc = self.lib.esim_get_seeds(self._ctx, None, 0, C.byref(n))
+        if rc not in (_lib.ESIM_OK, _lib.ESIM_ERANGE):
+            _lib.check(rc, self._ctx)
+        out = np.zeros(n.value, np.uint32)
+        if n.value:
+            _lib.check(self.lib.esim_get_seeds(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)), self._ctx)
+        return out
 
     # -- per-Output-Area accumulators over the members of an ensemble (esim_ensemble_*) -------
     def ensemble_begin(self, where="home", status_mask=(1 << _lib.EXPOSED) | (1 << _lib.INFECTED) | (1 << _lib.RECOVERED), min_cases=1):
         code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)
         self._ens_n = self._n_groups if code == _lib.BY_GROUP else self.population.n_areas
         _lib.check(self.lib.esim_ensemble_begin(self._ctx, int(code), int(status_mask), int(min_cases)), self._ctx)
+
+    def ensemble_begin_arrival(self, where="home", horizon=None):
+        """Accumulators of the arrival step instead (esim_ensemble_begin_arrival): a member counts as a hit where the epidemic
+        reached the area (where="home") or group (where="group") by step `horizon`; None: within whatever steps it ran."""
+        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)   # ("current": refused by the library)
+        self._ens_n = self._n_groups if code == _lib.BY_GROUP else self.population.n_areas
+        _lib.check(self.lib.esim_ensemble_begin_arrival(self._ctx, int(code), _lib.NEVER if horizon is None else int(horizon)), self._ctx)
 
     def ensemble_fold(self):
         """Adds the state as it stands to the accumulators, on the device; nothing is downloaded."""
@@ -357,6 +384,15 @@ class Simulator:
         code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
         out = np.zeros((self.population.n_areas, 5), np.uint32)
         _lib.check(self.lib.esim_area_census(self._ctx, int(code), out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
+    def area_arrival(self, where="home"):
+        """uint32 [n_areas] (where="home") or [n_groups] (where="group"): the step at which a citizen of the area (by
+        household) or group was first exposed, counted on the device from the exposure log (esim_area_arrival); 0 where an
+        initially infected citizen lives, _lib.NEVER where the epidemic has not arrived in the steps run so far."""
+        code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)   # ("current": refused by the library)
+        out = np.zeros(max(1, self._n_groups) if code == _lib.BY_GROUP else self.population.n_areas, np.uint32)
+        _lib.check(self.lib.esim_area_arrival(self._ctx, int(code), out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
     def area_series(self, what, first_step=1, n_rows=None, stride=1):

@@ -130,10 +130,25 @@ int  esim_reset(esim_ctx *ctx);
  * *p leaves the context as it was.  Nothing waits for the device: the call may return before the work is done, every later
  * call of this context is ordered behind it.  The only host->device copies are the control block and the threshold LUT
  * (4.4 KB).  A context with a communicator of more than one rank returns ESIM_ESTATE (the shards would have to agree on
- * the parameters).  The initially infected citizens stay those of the uploaded population.  esim_reset afterwards goes
- * back to step 0 under the parameters of the last restart.  Checkpoints: their header is written from the parameters in
+ * the parameters).  The initially infected citizens stay those in force (the uploaded population's, or the list of the last
+ * esim_restart_seeded).  esim_reset afterwards goes back to step 0 under the parameters of the last restart.  Checkpoints: their header is written from the parameters in
  * force, so one saved after a restart goes back only into a context created with, or restarted to, the same parameters. */
 int  esim_restart(esim_ctx *ctx, const esim_params *p);
+/* esim_restart with other index cases: the citizens seeds[0 .. n_seeds) (local indices, as esim_population.seeds) start
+ * Infected(0) instead of the ones in force -- what SimulatorBuilder::apply_initial_infections (simulator_builder.rs:1111-1142)
+ * draws anew for every run of the reference.  Duplicates count once, the first occurrence fixes the order in the exposure log
+ * (as esim_upload_population treats them); the list may be longer or shorter than the uploaded one, up to n_citizens, or empty.
+ * Host->device traffic: what esim_restart copies plus 4 B per distinct seed, from pinned memory; nothing waits for the stream
+ * (a list longer than any before makes room on the device first, which does wait for the work still reading the old one).
+ * The list stays in force for esim_reset and esim_restart until the next esim_restart_seeded or upload.  Checkpoints: the
+ * population hash is finished with the list as given, so a checkpoint saved afterwards goes back into every context whose
+ * seeds in force are that same list -- a fresh context uploaded with a population that carries it included -- and no other.
+ * Refused, leaving the context as it was: everything esim_restart refuses; seeds == NULL with n_seeds > 0 or an index
+ * >= n_citizens (ESIM_EINVAL); n_seeds > n_citizens (ESIM_ERANGE).
+ * esim_get_seeds: the distinct seeds in force, in log order; *n_out = their number, ESIM_ERANGE (with *n_out set) when cap is
+ * too small.  Pure host code. */
+int  esim_restart_seeded(esim_ctx *ctx, const esim_params *p, const uint32_t *seeds, uint32_t n_seeds);
+int  esim_get_seeds(esim_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n_out);
 
 /* Replaces Simulator::step (simulator.rs:131-152).  out->disease_exists == 0 is the
  * reference's Ok(false). */
@@ -244,6 +259,14 @@ int  esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint32_t *step
  * population's area indices and starts no collective. */
 enum { ESIM_AREA_CURRENT = 0, ESIM_AREA_HOME = 1 };
 int  esim_area_census(esim_ctx *ctx, int where, uint32_t *counts /* [n_areas * 5] */);
+/* When the epidemic reached every Output Area -- the arrival-time map -- from the exposure log where it lies on the device:
+ * step_out[a] = the first time step at which a citizen whose household lies in area a was exposed, in a building or on
+ * public transport; 0 for the area of an initially infected citizen; ESIM_NEVER for an area not reached in the steps run so
+ * far.  where = ESIM_AREA_HOME, or ESIM_BY_GROUP: the same by the citizen's label, [n_groups] (ESIM_ESTATE without labels).
+ * ESIM_AREA_CURRENT is not built: ESIM_EINVAL.  Leaves the simulation state as it is.  A sharded context describes its own
+ * citizens and starts no collective. */
+#define ESIM_NEVER 0xFFFFFFFFu
+int  esim_area_arrival(esim_ctx *ctx, int where, uint32_t *step_out /* [n_areas] or [n_groups] */);
 /* Per-Output-Area accumulators over the members of an ensemble (runs of one population that differ in seed or parameters,
  * one after another on this context); they live on the device and survive esim_reset and esim_restart.  A new
  * esim_upload_population drops them.  20 bytes per area, allocated at the first begin.
@@ -254,8 +277,14 @@ int  esim_area_census(esim_ctx *ctx, int where, uint32_t *counts /* [n_areas * 5
  * read:  copy out; any pointer may be NULL.
  * The usual risk map ("reached by the epidemic") is the mask Exposed | Infected | Recovered by home area with min_cases 1.
  * ESIM_ESTATE before a population is uploaded, and for fold or read before begin; ESIM_EINVAL for an empty mask, a bit beyond
- * ESIM_VACCINATED or an unknown `where`.  where = ESIM_BY_GROUP: by citizen group instead of by area (esim_set_groups, below). */
+ * ESIM_VACCINATED or an unknown `where`.  where = ESIM_BY_GROUP: by citizen group instead of by area (esim_set_groups, below).
+ * begin_arrival: zero them and fix instead that a member contributes its arrival step, x = what esim_area_arrival(where)
+ *        would return: fold then does members += 1 and, where x != ESIM_NEVER and x <= horizon, hit += 1; sum += x;
+ *        sumsq += x * x -- again without download or host wait.  hit / members is P(reached by the horizon), sum / hit the mean
+ *        arrival step among the members that reached the entry.  horizon = ESIM_NEVER: whatever steps ran.  `where` and the
+ *        errors are those of esim_area_arrival; read and the invalidation by esim_set_groups are the same for both kinds. */
 int  esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t min_cases);
+int  esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t horizon);
 int  esim_ensemble_fold(esim_ctx *ctx);
 int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_areas] */,
                         uint64_t *sum /* [n_areas] */, uint64_t *sumsq /* [n_areas] */);
