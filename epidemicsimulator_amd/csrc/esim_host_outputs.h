@@ -233,6 +233,57 @@ int series_rows(esim_ctx_impl *c, bool by_group, int what, uint32_t first_step, 
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
     return ESIM_OK;
 }
+// esim_area_status_series behind its argument checks: n_rows rows of one column per area, counted from the exposure log and
+// the citizen words into one plane (rows by household area, incidence) or two (rows by the area stood in) and summed up over
+// the steps by k_area_status_prefix, which leaves the result in plane 0 (esim_kernels_area_status.h).
+int area_status_rows(esim_ctx_impl *c, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    const std::string who = "esim_area_status_series";
+    const bool incidence = what == ESIM_AREA_SERIES_INCIDENCE, current = where == ESIM_AREA_CURRENT, sus = what == ESIM_SUSCEPTIBLE;
+    const uint32_t t_done = c->host_t - 1u;                   // steps run so far
+    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
+        return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
+    RunShape shape;
+    if ((rc = run_shape(c, t_done, &shape))) return rc;
+    const bool replay = !incidence && shape.trigger != 0u;
+    if (replay && d.n_global != d.n)
+        return fail(c, ESIM_ESTATE, who + ": the status rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
+    const size_t words = (size_t)n_rows * d.n_areas;
+    const size_t occ_words = (size_t)d.n_areas * (current ? 2u : 1u);    // (occupancy of plane 0, then of plane 1)
+    DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_vax, d_p0, d_p1, d_occ;
+    if (d_p0.alloc(words) != hipSuccess || (current && (d_p1.alloc(words) != hipSuccess || d_aw.alloc(shape.aw.size()) != hipSuccess)) ||
+        (sus && d_occ.alloc(occ_words) != hipSuccess) || (replay && d_vax.alloc(d.n) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, who + ": no device memory for the rows (ask for fewer)");
+    }
+    hipError_t e = hipMemsetAsync(d_p0.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
+    if (e == hipSuccess && current) e = hipMemsetAsync(d_p1.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
+    if (e == hipSuccess && current) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && sus) e = hipMemsetAsync(d_occ.p, 0, sizeof(uint32_t) * std::max<size_t>(1, occ_words), c->stream);
+    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax.p);
+    if (e == hipSuccess) {
+        AreaStatus q;
+        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done; q.t_all = shape.t_all;
+        q.vax_of = d_vax.p; q.at_work = d_aw.p; q.p0 = d_p0.p; q.p1 = d_p1.p;
+        const uint32_t log_len = std::min<uint32_t>(h.log_len, d.n);
+        uint32_t *occ0 = sus ? d_occ.p : nullptr, *occ1 = sus && current ? d_occ.p + d.n_areas : nullptr;
+        if (what != ESIM_VACCINATED)
+            hipLaunchKernelGGL(k_area_status_log, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, log_len);
+        if (replay && (what == ESIM_VACCINATED || sus))                // (nobody is Vaccinated before a programme has run)
+            hipLaunchKernelGGL(k_area_status_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
+        if (sus) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, occ0, occ1);
+        if (!incidence)
+            hipLaunchKernelGGL(k_area_status_prefix, dim3(grid_for(d.n_areas, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, d.n_areas, occ0, occ1);
+        e = hipStreamSynchronize(c->stream);                      // (the host vector above is done with here, too)
+    } else (void)hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && words) e = hipMemcpy(out, d_p0.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
+    return ESIM_OK;
+}
 }  // namespace
 
 extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
@@ -329,6 +380,17 @@ extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, ui
         return fail(c, ESIM_EINVAL, "esim_area_series: null output, unknown `what`, stride 0 or no rows");
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_series: no population uploaded");
     return series_rows(c, false, what, first_step, n_rows, stride, out);
+}
+
+extern "C" int esim_area_status_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const bool incidence = what == ESIM_AREA_SERIES_INCIDENCE;
+    if (!out || (where != ESIM_AREA_HOME && (where != ESIM_AREA_CURRENT || incidence)) || what < ESIM_SUSCEPTIBLE || what > ESIM_AREA_SERIES_INCIDENCE ||
+        stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_area_status_series: null output, unknown `where` or `what` (incidence rows: by ESIM_AREA_HOME only), stride 0 or no rows");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_status_series: no population uploaded");
+    return area_status_rows(c, where, what, first_step, n_rows, stride, out);
 }
 
 // ---- read-backs by citizen group ---------------------------------------------------------------------------------------

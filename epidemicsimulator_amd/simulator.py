@@ -407,6 +407,22 @@ class Simulator:
                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
+    def area_status_series(self, what, where="home", first_step=1, n_rows=None, stride=1):
+        """uint32 [n_rows, n_areas] over the steps already run (esim_area_status_series): row i is step first_step + i * stride.
+        what: "susceptible", "exposed", "infected", "recovered", "vaccinated" (citizens with that status after the step, by
+        the area of their household, where="home", or the area they stand in, where="current") or "incidence" (building and
+        public-transport exposures of the `stride` steps from that one on, by the household's area; where="home" only).
+        n_rows=None: up to the last step run."""
+        code = {"susceptible": _lib.SUSCEPTIBLE, "exposed": _lib.EXPOSED, "infected": _lib.INFECTED, "recovered": _lib.RECOVERED,
+                "vaccinated": _lib.VACCINATED, "incidence": _lib.AREA_SERIES_INCIDENCE}.get(what, what)
+        place = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
+        if n_rows is None:
+            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
+        out = np.zeros((max(0, int(n_rows)), self.population.n_areas), np.uint32)
+        _lib.check(self.lib.esim_area_status_series(self._ctx, int(place), int(code), int(first_step), int(n_rows), int(stride),
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     # -- the same by citizen group (esim_set_groups, esim_group_census, esim_group_series) -------
     _n_groups = 0
 

@@ -307,6 +307,31 @@ int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_ar
 enum { ESIM_SERIES_INFECTED = 0, ESIM_SERIES_EXPOSURES = 1 };
 int  esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
                       uint32_t *out /* [n_rows * n_areas] */);
+/* All five statuses per Output Area over the steps already run, and the new cases by area of residence -- the attack-rate map
+ * (Recovered by household area), the vaccination-coverage map and the surveillance view of incidence over time -- derived after
+ * the fact like the rows above and addressed like them: row i describes step s_i = first_step + i * stride,
+ * out[i * n_areas + area].
+ *   what = ESIM_SUSCEPTIBLE .. ESIM_VACCINATED, where = ESIM_AREA_CURRENT or ESIM_AREA_HOME
+ *                          column `what` of what esim_area_census(where) would have returned had it been called after step
+ *                          s_i, i.e. the state after the step's vaccinations (the convention of the area and group tables);
+ *   what = ESIM_AREA_SERIES_INCIDENCE, where = ESIM_AREA_HOME only
+ *                          exposures of steps [s_i, s_i + stride), clipped to the steps run, credited to the Output Area of
+ *                          the exposed citizen's household: buildings AND public transport; the initially infected citizens
+ *                          are not counted.  (By the area stood in it is ESIM_EINVAL: esim_area_series(ESIM_SERIES_EXPOSURES)
+ *                          is that table, and a bus has no area.)
+ * ESIM_EINVAL: a null context or output, an unknown `where` (ESIM_BY_GROUP included) or `what`, stride 0, no rows; ESIM_ESTATE
+ * before a population is uploaded; ESIM_ERANGE: first_step == 0 or the last row's step beyond the steps run; ESIM_ENOMEM: no
+ * device memory for the rows (ask for fewer).  A sharded context describes its own citizens and starts no collective; its
+ * status rows return ESIM_ESTATE once a vaccination programme has run (the rule of esim_area_series), its incidence rows stay
+ * available.  Leaves the simulation state, the records, the ensemble accumulators and the group labels as they are.
+ * Limits (temporary device memory): n_rows * n_areas * 4 B for rows by household area and for incidence, twice that for rows by
+ * the area stood in (one plane per value of the at-work bit) plus 1 B per step run; 4 B per area and plane of occupancy for
+ * the Susceptible rows; 4 B per citizen for the status rows once a vaccination programme has run (the choice of
+ * simulator.rs:524-553 is walked again).
+ * The work per exposure-log entry and per vaccinated citizen does not depend on the number of steps run. */
+enum { ESIM_AREA_SERIES_INCIDENCE = 5 };       /* `what` of esim_area_status_series, beside the five status codes */
+int  esim_area_status_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                             uint32_t *out /* [n_rows * n_areas] */);
 /* Stratified outputs: the same read-backs by citizen GROUP -- an age band, an occupation, any label of the caller's.
  * esim_set_groups copies one label per local citizen to the device (2 B per citizen; no host pointer is kept) and counts the
  * groups' sizes once.  1 <= n_groups <= ESIM_MAX_GROUPS; a label >= n_groups is ESIM_EINVAL (checked on the host during the
