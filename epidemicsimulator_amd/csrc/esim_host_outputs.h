@@ -183,13 +183,19 @@ int census_readback(esim_ctx_impl *c, const uint32_t *table, uint32_t *mirror, s
     return ctrl_error(c, h);
 }
 
-// esim_area_series and esim_group_series behind their own argument checks: n_rows rows of one column per area / group,
-// out[row * columns + column], counted from the exposure log on the device.  Rows that are a census over time (the areas'
-// Infected, a group's status) are summed up over the steps, and derived by replaying the vaccinations once a programme has run.
-int series_rows(esim_ctx_impl *c, bool by_group, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+// What one of the three series entry points asks of the engine (esim_kernels_series.h): its name, how its ESIM_ESTATE text
+// calls the status rows, the column key, the status or SERIES_EVENTS, and whether event rows leave out public transport.
+struct SeriesSpec { const char *who, *rows; uint32_t key, what; bool skip_bus, pieces; };
+
+// The series behind their own argument checks: n_rows rows of one column per area / group, out[row * columns + column], counted
+// from the exposure log and the citizen words into one plane, or two for the status rows by the area stood in, and summed up over
+// the steps by k_series_prefix, which leaves the result in plane 0.  Status rows are derived by replaying the vaccinations once a
+// programme has run.
+int series_rows(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
 {
-    const std::string who = by_group ? "esim_group_series" : "esim_area_series";
-    const bool status_rows = by_group ? what != ESIM_GROUP_SERIES_EXPOSURES : what == ESIM_SERIES_INFECTED;
+    const std::string who = s.who;
+    const bool events = s.what == SERIES_EVENTS, by_group = s.key == KEY_GROUP, stood = s.key == KEY_STOOD, sus = s.what == ESIM_SUSCEPTIBLE;
+    const bool two = stood && !events && !s.pieces;           // (an event is credited to one column of plane 0)
     const uint32_t t_done = c->host_t - 1u;                   // steps run so far
     if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
         return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
@@ -199,85 +205,40 @@ int series_rows(esim_ctx_impl *c, bool by_group, int what, uint32_t first_step, 
     if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
     RunShape shape;
     if ((rc = run_shape(c, t_done, &shape))) return rc;
-    const bool replay = status_rows && shape.trigger != 0u;
+    const bool replay = !events && shape.trigger != 0u;
     if (replay && d.n_global != d.n)
-        return fail(c, ESIM_ESTATE, who + ": the " + (by_group ? "status" : "Infected") + " rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
+        return fail(c, ESIM_ESTATE, who + ": the " + s.rows + " rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
     const uint32_t cols = by_group ? c->grp.n : d.n_areas;
-    const size_t out_words = ((size_t)n_rows + 1u) * cols;
-    DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_tog, d_vax, d_out;          // (the areas' rows need the at-work bits, the groups' do not)
-    if ((!by_group && (d_aw.alloc(shape.aw.size()) != hipSuccess || d_tog.alloc(shape.tog.size()) != hipSuccess)) ||
-        d_out.alloc(out_words) != hipSuccess || (replay && d_vax.alloc(d.n) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(c, ESIM_ENOMEM, who + ": no device memory for the rows (ask for fewer)");
-    }
-    hipError_t e = hipSuccess;
-    if (!by_group) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && !by_group && !shape.tog.empty()) e = hipMemcpyAsync(d_tog.p, shape.tog.data(), sizeof(uint32_t) * shape.tog.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out.p, 0, sizeof(uint32_t) * out_words, c->stream);
-    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax.p);
-    if (e == hipSuccess) {
-        AreaSeries q;
-        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done;
-        q.n_tog = by_group ? 0u : (uint32_t)shape.tog.size(); q.t_all = shape.t_all; q.at_work = d_aw.p; q.tog = d_tog.p; q.vax_of = d_vax.p; q.out = d_out.p;
-        if (by_group) {
-            const bool citizens = what == ESIM_VACCINATED || what == ESIM_SUSCEPTIBLE;   // (the pass over everybody Vaccinated)
-            hipLaunchKernelGGL(k_group_series, dim3(grid_for(citizens ? std::max<size_t>(d.n, h.log_len) : h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream,
-                               d, q, c->grp.lab, cols, h.log_len);
-        } else hipLaunchKernelGGL(k_area_series, dim3(grid_for(h.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, h.log_len);
-        if (status_rows) hipLaunchKernelGGL(k_area_prefix, dim3(grid_for(cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d_out.p, n_rows, cols);
-        if (by_group && what == ESIM_SUSCEPTIBLE)
-            hipLaunchKernelGGL(k_group_s_rows, dim3(grid_for((size_t)n_rows * cols, TPB, 4096)), dim3(TPB), 0, c->stream, d_out.p, n_rows, cols, c->grp.size);
-        e = hipStreamSynchronize(c->stream);                      // (the host vectors above are done with here, too)
-    } else (void)hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, sizeof(uint32_t) * (size_t)n_rows * cols, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
-    return ESIM_OK;
-}
-// esim_area_status_series behind its argument checks: n_rows rows of one column per area, counted from the exposure log and
-// the citizen words into one plane (rows by household area, incidence) or two (rows by the area stood in) and summed up over
-// the steps by k_area_status_prefix, which leaves the result in plane 0 (esim_kernels_area_status.h).
-int area_status_rows(esim_ctx_impl *c, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
-{
-    const std::string who = "esim_area_status_series";
-    const bool incidence = what == ESIM_AREA_SERIES_INCIDENCE, current = where == ESIM_AREA_CURRENT, sus = what == ESIM_SUSCEPTIBLE;
-    const uint32_t t_done = c->host_t - 1u;                   // steps run so far
-    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
-        return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    const Dev &d = c->d;
-    Ctrl h; int rc;
-    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
-    RunShape shape;
-    if ((rc = run_shape(c, t_done, &shape))) return rc;
-    const bool replay = !incidence && shape.trigger != 0u;
-    if (replay && d.n_global != d.n)
-        return fail(c, ESIM_ESTATE, who + ": the status rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
-    const size_t words = (size_t)n_rows * d.n_areas;
-    const size_t occ_words = (size_t)d.n_areas * (current ? 2u : 1u);    // (occupancy of plane 0, then of plane 1)
-    DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_vax, d_p0, d_p1, d_occ;
-    if (d_p0.alloc(words) != hipSuccess || (current && (d_p1.alloc(words) != hipSuccess || d_aw.alloc(shape.aw.size()) != hipSuccess)) ||
-        (sus && d_occ.alloc(occ_words) != hipSuccess) || (replay && d_vax.alloc(d.n) != hipSuccess)) {
+    const size_t words = (size_t)n_rows * cols;
+    const bool count_occ = sus && !by_group;                  // (a group's occupancy is its size)
+    const size_t occ_words = (size_t)cols * (two ? 2u : 1u);  // (occupancy of plane 0, then of plane 1)
+    DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_vax, d_p0, d_p1, d_occ, d_tog;
+    if (d_p0.alloc(words) != hipSuccess || (s.pieces && d_tog.alloc(shape.tog.size()) != hipSuccess) || (two && d_p1.alloc(words) != hipSuccess) || (stood && d_aw.alloc(shape.aw.size()) != hipSuccess) ||
+        (count_occ && d_occ.alloc(occ_words) != hipSuccess) || (replay && d_vax.alloc(d.n) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(c, ESIM_ENOMEM, who + ": no device memory for the rows (ask for fewer)");
     }
     hipError_t e = hipMemsetAsync(d_p0.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
-    if (e == hipSuccess && current) e = hipMemsetAsync(d_p1.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
-    if (e == hipSuccess && current) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && sus) e = hipMemsetAsync(d_occ.p, 0, sizeof(uint32_t) * std::max<size_t>(1, occ_words), c->stream);
+    if (e == hipSuccess && two) e = hipMemsetAsync(d_p1.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
+    if (e == hipSuccess && stood) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && s.pieces && !shape.tog.empty()) e = hipMemcpyAsync(d_tog.p, shape.tog.data(), sizeof(uint32_t) * shape.tog.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && count_occ) e = hipMemsetAsync(d_occ.p, 0, sizeof(uint32_t) * std::max<size_t>(1, occ_words), c->stream);
     if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax.p);
     if (e == hipSuccess) {
-        AreaStatus q;
-        q.what = (uint32_t)what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done; q.t_all = shape.t_all;
+        Series q;
+        q.what = s.what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done; q.t_all = shape.t_all;
         q.vax_of = d_vax.p; q.at_work = d_aw.p; q.p0 = d_p0.p; q.p1 = d_p1.p;
+        q.n_cols = cols; q.key = s.key; q.grp = by_group ? c->grp.lab : nullptr; q.skip_bus = s.skip_bus;
+        q.n_tog = s.pieces ? (uint32_t)shape.tog.size() : 0u; q.tog = d_tog.p;
         const uint32_t log_len = std::min<uint32_t>(h.log_len, d.n);
-        uint32_t *occ0 = sus ? d_occ.p : nullptr, *occ1 = sus && current ? d_occ.p + d.n_areas : nullptr;
-        if (what != ESIM_VACCINATED)
-            hipLaunchKernelGGL(k_area_status_log, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, log_len);
-        if (replay && (what == ESIM_VACCINATED || sus))                // (nobody is Vaccinated before a programme has run)
-            hipLaunchKernelGGL(k_area_status_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
-        if (sus) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, occ0, occ1);
-        if (!incidence)
-            hipLaunchKernelGGL(k_area_status_prefix, dim3(grid_for(d.n_areas, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, d.n_areas, occ0, occ1);
+        const uint32_t *occ0 = !sus ? nullptr : by_group ? c->grp.size : d_occ.p, *occ1 = sus && two ? d_occ.p + cols : nullptr;
+        if (s.what != ESIM_VACCINATED)
+            hipLaunchKernelGGL(k_series_log, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, log_len);
+        if (replay && (s.what == ESIM_VACCINATED || sus))            // (nobody is Vaccinated before a programme has run)
+            hipLaunchKernelGGL(k_series_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
+        if (count_occ) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, d_occ.p, two ? d_occ.p + cols : nullptr);
+        if (!events)
+            hipLaunchKernelGGL(k_series_prefix, dim3(grid_for(cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, occ0, occ1);
         e = hipStreamSynchronize(c->stream);                      // (the host vector above is done with here, too)
     } else (void)hipStreamSynchronize(c->stream);
     if (e == hipSuccess && words) e = hipMemcpy(out, d_p0.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost);
@@ -379,7 +340,9 @@ extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, ui
     if (!out || (what != ESIM_SERIES_INFECTED && what != ESIM_SERIES_EXPOSURES) || stride == 0 || n_rows == 0)
         return fail(c, ESIM_EINVAL, "esim_area_series: null output, unknown `what`, stride 0 or no rows");
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_series: no population uploaded");
-    return series_rows(c, false, what, first_step, n_rows, stride, out);
+    // the Infected by the area stood in; building exposures by the area stood in at the exposure
+    const SeriesSpec s = {"esim_area_series", "Infected", KEY_STOOD, what == ESIM_SERIES_INFECTED ? (uint32_t)ESIM_INFECTED : SERIES_EVENTS, true, what == ESIM_SERIES_INFECTED};
+    return series_rows(c, s, first_step, n_rows, stride, out);
 }
 
 extern "C" int esim_area_status_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
@@ -390,7 +353,8 @@ extern "C" int esim_area_status_series(esim_ctx *ctx, int where, int what, uint3
         stride == 0 || n_rows == 0)
         return fail(c, ESIM_EINVAL, "esim_area_status_series: null output, unknown `where` or `what` (incidence rows: by ESIM_AREA_HOME only), stride 0 or no rows");
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_area_status_series: no population uploaded");
-    return area_status_rows(c, where, what, first_step, n_rows, stride, out);
+    const SeriesSpec s = {"esim_area_status_series", "status", where == ESIM_AREA_CURRENT ? KEY_STOOD : KEY_HOME, (uint32_t)what, false, false};   // (INCIDENCE = SERIES_EVENTS)
+    return series_rows(c, s, first_step, n_rows, stride, out);
 }
 
 // ---- read-backs by citizen group ---------------------------------------------------------------------------------------
@@ -449,5 +413,6 @@ extern "C" int esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, u
     if (!out || what < ESIM_SUSCEPTIBLE || what > ESIM_GROUP_SERIES_EXPOSURES || stride == 0 || n_rows == 0)
         return fail(c, ESIM_EINVAL, "esim_group_series: null output, unknown `what`, stride 0 or no rows");
     if (!c->uploaded || !c->grp.lab || c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_group_series: no population uploaded, or no labels (esim_set_groups)");
-    return series_rows(c, true, what, first_step, n_rows, stride, out);
+    const SeriesSpec s = {"esim_group_series", "status", KEY_GROUP, (uint32_t)what, false, false};   // (EXPOSURES = SERIES_EVENTS)
+    return series_rows(c, s, first_step, n_rows, stride, out);
 }

@@ -27,6 +27,6 @@
 #include "esim_kernels_tiny.h"
 #include "esim_kernels_state.h"
 #include "esim_kernels_area.h"
-#include "esim_kernels_area_status.h"
 #include "esim_kernels_group.h"
+#include "esim_kernels_series.h"
 #include "esim_kernels_restart.h"

@@ -1,5 +1,5 @@
 // esim_kernels_area.h -- per-Output-Area read-backs: the census by area as it stands (esim_area_census) and, after the
-// fact, per-area rows over the steps already run (esim_area_series) and the step at which the epidemic first reached every
+// fact, the step at which the epidemic first reached every
 // area or citizen group (esim_area_arrival).  Nothing here writes simulation state.
 #pragma once
 
@@ -54,20 +54,6 @@ __global__ __launch_bounds__(TPB) void k_area_census(Dev d, int home_only, uint3
     }
 }
 
-// ---- esim_area_series -------------------------------------------------------------------------------------------------
-// What the host derives from the records and hands to the kernels: where everybody with a work place stands after the
-// schedule arm of every step run so far, and the steps at which that changes.
-struct AreaSeries {
-    uint32_t what, first, n_rows, stride;
-    uint32_t t_done;                // steps run so far
-    uint32_t n_tog;
-    uint32_t t_all;                 // first step that vaccinated the whole eligible set (0xFFFFFFFF: none)
-    const uint8_t *at_work;         // [t_done + 1]
-    const uint32_t *tog;            // [n_tog] steps s with at_work[s] != at_work[s - 1], ascending
-    const uint32_t *vax_of;         // [n] step at whose end a citizen was set Vaccinated (k_area_vax_replay), or nullptr
-    uint32_t *out;                  // [n_rows + 1][n_areas]
-};
-
 // The exposure step (biased) of log entry i from its position: the entries of step k are [log_off[k], log_off[k + 1]).
 // (The citizen word no longer holds it once the citizen has been vaccinated.)
 __device__ __forceinline__ uint32_t log_te(const Dev &d, uint32_t i, uint32_t k_max)
@@ -101,68 +87,6 @@ __global__ __launch_bounds__(TPB) void k_area_arrival(Dev d, const uint16_t *grp
     }
 }
 
-// A citizen stands in `area` during the steps [p, e], first <= p: +1 at the first row inside, -1 behind the last one.
-__device__ __forceinline__ void rows_add(const AreaSeries &q, uint32_t n_areas, uint32_t p, uint32_t e, uint32_t area)
-{
-    if (e < p) return;
-    const uint64_t i_lo = ((uint64_t)(p - q.first) + q.stride - 1u) / q.stride;
-    uint64_t i_hi = (uint64_t)(e - q.first) / q.stride;
-    if (i_lo >= q.n_rows) return;
-    if (i_hi >= q.n_rows) i_hi = q.n_rows - 1u;
-    if (i_lo > i_hi) return;
-    atomicAdd(&q.out[i_lo * n_areas + area], 1u);
-    atomicSub(&q.out[(i_hi + 1u) * n_areas + area], 1u);
-}
-
-// A lane per exposure-log entry (the seeds are in the log).  EXPOSURES: one add at (row of the exposure step, area at
-// that step).  INFECTED: the citizen is Infected in steps te + exposed_time + 1 .. te + exposed_time + 1 + infected_time
-// (status_of), or until the step before the one at whose end it was vaccinated; its area changes only where the at-work
-// bit does, and only if it works outside its home area: +-1 at the ends of every constant piece, summed by k_area_prefix.
-__global__ __launch_bounds__(TPB) void k_area_series(Dev d, AreaSeries q, uint32_t log_len)
-{
-    for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < log_len; i += gridDim.x * TPB) {
-        const uint32_t c = d.log[i], w = d.cit[c];
-        const int ts = (int)log_te(d, i, q.t_done + TE_BIAS) - (int)TE_BIAS;   // exposure step; seeds: -(exposed_time + 1)
-        const bool commuter = (w & FL_HAS_WORK) && !(w & FL_SAME_AREA);
-        const uint32_t a_home = d.bld_area[d.home[c]];
-        const uint32_t a_work = commuter ? d.bld_area[d.work[c]] : a_home;
-        if (q.what == ESIM_SERIES_EXPOSURES) {
-            if ((w & CW_BUS_EXPOSED) || ts < (int)q.first || ts > (int)q.t_done) continue;
-            const uint64_t row = (uint64_t)((uint32_t)ts - q.first) / q.stride;
-            if (row < q.n_rows) atomicAdd(&q.out[row * d.n_areas + (q.at_work[ts] ? a_work : a_home)], 1u);
-            continue;
-        }
-        int p = ts + (int)d.exposed_time + 1, e = p + (int)d.infected_time;
-        if (CW_TE(w) == TE_VACCINATED) {
-            uint32_t v = q.vax_of ? q.vax_of[c] : 0xFFFFFFFFu;
-            if (q.t_all < v) v = q.t_all;
-            if (v != 0xFFFFFFFFu && (int)v - 1 < e) e = (int)v - 1;
-        }
-        if (e > (int)q.t_done) e = (int)q.t_done;
-        if (p < (int)q.first) p = (int)q.first;
-        if (e < p) continue;
-        if (!commuter) { rows_add(q, d.n_areas, (uint32_t)p, (uint32_t)e, a_home); continue; }
-        uint32_t k = 0u, k_hi = q.n_tog;                          // the first change of the at-work bit behind step p
-        while (k < k_hi) { const uint32_t mid = (k + k_hi) >> 1; if (q.tog[mid] > (uint32_t)p) k_hi = mid; else k = mid + 1u; }
-        for (uint32_t s = (uint32_t)p;;) {
-            const uint32_t nxt = k < q.n_tog ? q.tog[k] : 0xFFFFFFFFu;
-            const uint32_t pe = nxt - 1u < (uint32_t)e ? nxt - 1u : (uint32_t)e;
-            rows_add(q, d.n_areas, s, pe, q.at_work[s] ? a_work : a_home);
-            if (pe >= (uint32_t)e) break;
-            s = nxt; ++k;
-        }
-    }
-}
-
-// Difference rows to counts: a lane per area walks down its column.
-__global__ __launch_bounds__(TPB) void k_area_prefix(uint32_t *out, uint32_t n_rows, uint32_t n_areas)
-{
-    const uint32_t a = blockIdx.x * TPB + threadIdx.x;
-    if (a >= n_areas) return;
-    uint32_t acc = 0u;
-    for (uint32_t r = 0; r < n_rows; ++r) { acc += out[(size_t)r * n_areas + a]; out[(size_t)r * n_areas + a] = acc; }
-}
-
 // Was the citizen a live vaccination candidate at the end of step t (eligible(), on the word as it stood THEN)?  A word
 // that is Vaccinated now belonged to the eligible set from the trigger step on: only members are vaccinated, nobody
 // Vaccinated is exposed, and the set never drops a vaccinated member (Q10).
@@ -179,7 +103,7 @@ __device__ __forceinline__ bool was_eligible(uint32_t w, uint32_t t, uint32_t tr
 // (simulator.rs:551).  The choice of simulator.rs:524-553 is a pure function of the step and of the eligible set, so it is
 // walked again, a workgroup per step, exactly as finish_phase walks it: the first `vaccination_rate` distinct live
 // candidates in candidate order.  vax_of[c] = the earliest step that chose c, for the citizens that are Vaccinated now.
-// Steps that vaccinated the whole set (eligible_count <= rate) are the caller's (AreaSeries::t_all).  One shard only.
+// Steps that vaccinated the whole set (eligible_count <= rate) are the caller's (Series::t_all).  One shard only.
 struct AreaVaxShared {
     uint32_t tab_key[VACC_TABLE];
     uint32_t tab_idx[VACC_TABLE];

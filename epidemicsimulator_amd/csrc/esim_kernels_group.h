@@ -54,60 +54,3 @@ __global__ __launch_bounds__(TPB) void k_group_finish(const uint32_t *size, uint
     uint32_t *row = counts + (size_t)g * 5u;
     row[0] = size[g] - row[1] - row[2] - row[3] - row[4];
 }
-
-// ---- esim_group_series ------------------------------------------------------------------------------------------------
-// The rows are addressed as those of esim_area_series (AreaSeries: what, first, n_rows, stride, t_done, t_all, vax_of, out;
-// the at-work fields are unused), out is [n_rows + 1][n_groups].
-// A lane per exposure-log entry (the seeds are in the log), its exposure step ts taken from the entry's position (log_te).
-// EXPOSURES: one add at (row of ts, group), buildings and public transport alike.  Status rows: the citizen is Exposed after
-// the steps ts .. ts + exposed_time, Infected after the infected_time + 1 steps that follow, Recovered from then on
-// (status_of); a citizen that was vaccinated stops being any of these with the step before the one at whose end it was
-// vaccinated.  SUSCEPTIBLE rows collect everybody who is NOT Susceptible -- the three intervals as one, and the Vaccinated --
-// and k_group_s_rows takes them from the group's size.  +-1 at the ends of an interval, summed by k_area_prefix.
-// Then a lane per citizen for the VACCINATED (and SUSCEPTIBLE) rows: +1 from the vaccinating step on.
-__global__ __launch_bounds__(TPB) void k_group_series(Dev d, AreaSeries q, const uint16_t *grp, uint32_t n_groups, uint32_t log_len)
-{
-    const uint32_t first = blockIdx.x * TPB + threadIdx.x, stride = gridDim.x * TPB;
-    if (q.what != ESIM_VACCINATED) {
-        for (uint32_t i = first; i < log_len; i += stride) {
-            const uint32_t c = d.log[i], w = d.cit[c], g = grp[c];
-            const int ts = (int)log_te(d, i, q.t_done + TE_BIAS) - (int)TE_BIAS;   // exposure step; seeds: -(exposed_time + 1)
-            if (q.what == ESIM_GROUP_SERIES_EXPOSURES) {
-                if (ts < (int)q.first || ts > (int)q.t_done) continue;
-                const uint64_t row = (uint64_t)((uint32_t)ts - q.first) / q.stride;
-                if (row < q.n_rows) atomicAdd(&q.out[row * n_groups + g], 1u);
-                continue;
-            }
-            const int inf = ts + (int)d.exposed_time + 1, rec = inf + (int)d.infected_time + 1;
-            int p, e = (int)q.t_done;
-            if (q.what == ESIM_EXPOSED) { p = ts; e = inf - 1; }
-            else if (q.what == ESIM_INFECTED) { p = inf; e = rec - 1; }
-            else if (q.what == ESIM_RECOVERED) p = rec;
-            else p = ts;                                              // SUSCEPTIBLE: not Susceptible from the exposure on
-            if (CW_TE(w) == TE_VACCINATED) {
-                uint32_t v = q.vax_of ? q.vax_of[c] : 0xFFFFFFFFu;
-                if (q.t_all < v) v = q.t_all;
-                if (v != 0xFFFFFFFFu && (int)v - 1 < e) e = (int)v - 1;
-            }
-            if (e > (int)q.t_done) e = (int)q.t_done;
-            if (p < (int)q.first) p = (int)q.first;
-            if (e < p) continue;
-            rows_add(q, n_groups, (uint32_t)p, (uint32_t)e, g);
-        }
-    }
-    if (q.what != ESIM_VACCINATED && q.what != ESIM_SUSCEPTIBLE) return;
-    for (uint32_t c = first; c < d.n; c += stride) {
-        if (CW_TE(d.cit[c]) != TE_VACCINATED) continue;
-        uint32_t v = q.vax_of ? q.vax_of[c] : 0xFFFFFFFFu;
-        if (q.t_all < v) v = q.t_all;
-        if (v == 0xFFFFFFFFu || v > q.t_done) continue;
-        rows_add(q, n_groups, v < q.first ? q.first : v, q.t_done, grp[c]);
-    }
-}
-
-// SUSCEPTIBLE rows: what k_area_prefix has summed is everybody who is not Susceptible.
-__global__ __launch_bounds__(TPB) void k_group_s_rows(uint32_t *out, uint32_t n_rows, uint32_t n_groups, const uint32_t *size)
-{
-    const size_t n = (size_t)n_rows * n_groups;
-    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * TPB) out[i] = size[i % n_groups] - out[i];
-}

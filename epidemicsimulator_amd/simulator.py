@@ -395,17 +395,21 @@ class Simulator:
         _lib.check(self.lib.esim_area_arrival(self._ctx, int(code), out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
+    def _series(self, call, codes, n_cols, first_step, n_rows, stride):
+        """One of the three series calls: uint32 [n_rows, n_cols]; n_rows=None: up to the last step run."""
+        if n_rows is None:
+            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
+        out = np.zeros((max(0, int(n_rows)), n_cols), np.uint32)
+        _lib.check(call(self._ctx, *(int(c) for c in codes), int(first_step), int(n_rows), int(stride),
+                        out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     def area_series(self, what, first_step=1, n_rows=None, stride=1):
         """uint32 [n_rows, n_areas] over the steps already run (esim_area_series): row i is step first_step + i * stride.
         what: "infected" (citizens Infected after that step, by the area they stand in) or "exposures" (building exposures
         of the `stride` steps from that one on, by area).  n_rows=None: up to the last step run."""
         code = {"infected": _lib.SERIES_INFECTED, "exposures": _lib.SERIES_EXPOSURES}.get(what, what)
-        if n_rows is None:
-            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
-        out = np.zeros((max(0, int(n_rows)), self.population.n_areas), np.uint32)
-        _lib.check(self.lib.esim_area_series(self._ctx, int(code), int(first_step), int(n_rows), int(stride),
-                                             out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
-        return out
+        return self._series(self.lib.esim_area_series, (code,), self.population.n_areas, first_step, n_rows, stride)
 
     def area_status_series(self, what, where="home", first_step=1, n_rows=None, stride=1):
         """uint32 [n_rows, n_areas] over the steps already run (esim_area_status_series): row i is step first_step + i * stride.
@@ -416,12 +420,7 @@ class Simulator:
         code = {"susceptible": _lib.SUSCEPTIBLE, "exposed": _lib.EXPOSED, "infected": _lib.INFECTED, "recovered": _lib.RECOVERED,
                 "vaccinated": _lib.VACCINATED, "incidence": _lib.AREA_SERIES_INCIDENCE}.get(what, what)
         place = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME}.get(where, where)
-        if n_rows is None:
-            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
-        out = np.zeros((max(0, int(n_rows)), self.population.n_areas), np.uint32)
-        _lib.check(self.lib.esim_area_status_series(self._ctx, int(place), int(code), int(first_step), int(n_rows), int(stride),
-                                                    out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
-        return out
+        return self._series(self.lib.esim_area_status_series, (place, code), self.population.n_areas, first_step, n_rows, stride)
 
     # -- the same by citizen group (esim_set_groups, esim_group_census, esim_group_series) -------
     _n_groups = 0
@@ -458,12 +457,7 @@ class Simulator:
         group of the exposed citizen).  n_rows=None: up to the last step run."""
         code = {"susceptible": _lib.SUSCEPTIBLE, "exposed": _lib.EXPOSED, "infected": _lib.INFECTED, "recovered": _lib.RECOVERED,
                 "vaccinated": _lib.VACCINATED, "exposures": _lib.GROUP_SERIES_EXPOSURES}.get(what, what)
-        if n_rows is None:
-            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= self._steps else 0
-        out = np.zeros((max(0, int(n_rows)), max(1, self._n_groups)), np.uint32)
-        _lib.check(self.lib.esim_group_series(self._ctx, int(code), int(first_step), int(n_rows), int(stride),
-                                              out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
-        return out
+        return self._series(self.lib.esim_group_series, (code,), max(1, self._n_groups), first_step, n_rows, stride)
 
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)

@@ -185,12 +185,44 @@ def commuting_world():
     return pop
 
 
+@pytest.fixture(scope="module")
+def small_worlds():
+    """(pop, ep, reference tables, building-exposure rows by the area stood in) of the two worlds, computed once."""
+    out = []
+    for pop, ep, n in (
+            # three areas, 500 citizens
+            (Population.synthetic("york", n_citizens=500, n_areas=3, citizens_per_school=500, n_seeds=5),
+             _lib.default_params(exposure_chance=0.003, vaccination_threshold=0.02, vaccination_rate=2, lockdown_threshold=0.05, seed=3), 400),
+            # two areas, most workers commuting across the boundary: the two planes differ for most citizens
+            (commuting_world(),
+             _lib.default_params(exposure_chance=0.01, vaccination_threshold=0.1, vaccination_rate=20, lockdown_threshold=0.2, seed=5), 500)):
+        out.append((pop, ep, ref_mod.reference_tables(pop, ep, n), _area_ref.reference_tables(pop, ep, n)["exposure_rows"]))
+    return out
+
+
+def check_other_entry_points(sim, pop, ref, exposure_rows, t_done, note):
+    """esim_area_series and, with the home area as the label, esim_group_series against the numpy reference itself: after the
+    fold all three entry points run one engine, so comparing them with each other would compare a code path with itself."""
+    same(sim.area_series("infected"), ref_mod.expected(ref, "current", "infected", t_done), "area_series infected, %s" % note)
+    assert exposure_rows[:t_done].any()
+    same(sim.area_series("exposures"), exposure_rows[:t_done], "area_series exposures, %s" % note)
+    sim.set_groups(ref_mod.home_area_labels(pop), pop.n_areas)
+    try:
+        # every step run; and the one row of the last step run: every interval that reaches it has nothing behind it
+        for window in (dict(first_step=1, stride=1), dict(first_step=t_done, n_rows=1)):
+            for name in STATUS:
+                want = ref_mod.expected(ref, "home", name, t_done, **window)
+                same(sim.group_series(name, **window), want, "group_series %s by home-area label, %s %s" % (name, window, note))
+            want = ref_mod.expected(ref, "home", "incidence", t_done, **window)
+            same(sim.group_series("exposures", **window), want, "group_series exposures by home-area label, %s %s" % (window, note))
+    finally:
+        sim.set_groups(None)
+
+
 @pytest.mark.parametrize("pipeline", [None, 0], ids=["default", "sequential"])
-def test_small_worlds(pipeline):
+def test_small_worlds(small_worlds, pipeline):
     # three areas, 500 citizens: asked while the exposure log is shorter than one wavefront, and again at the end
-    pop = Population.synthetic("york", n_citizens=500, n_areas=3, citizens_per_school=500, n_seeds=5)
-    ep = _lib.default_params(exposure_chance=0.003, vaccination_threshold=0.02, vaccination_rate=2, lockdown_threshold=0.05, seed=3)
-    ref = ref_mod.reference_tables(pop, ep, 400)
+    pop, ep, ref, exposure_rows = small_worlds[0]
     rec = ref["records"]
     entries = len(np.unique(pop.seeds)) + np.cumsum(rec["exposures_building"].astype(np.int64) + rec["exposures_bus"])
     early = int(np.flatnonzero(entries < 64)[-1]) + 1
@@ -200,16 +232,19 @@ def test_small_worlds(pipeline):
         sim.set_pipeline(pipeline)
     sim.run(early)
     check_all(sim, ref, early, "three areas, a log below 64 entries")
+    check_other_entry_points(sim, pop, ref, exposure_rows, early, "three areas, a log below 64 entries")
     sim.run(400 - early)
     check_records(sim, ref)
     check_all(sim, ref, 400, "three areas")
+    check_other_entry_points(sim, pop, ref, exposure_rows, 400, "three areas")
+    for name in STATUS:                                               # (the reference tables of this world are not empty)
+        assert ref["home"][:, :, STATUS.index(name)].any() and ref["current"][:, :, STATUS.index(name)].any()
     sim.close()
     # two areas, most workers commuting across the boundary: the two planes differ for most citizens
-    pop = commuting_world()
-    ep = _lib.default_params(exposure_chance=0.01, vaccination_threshold=0.1, vaccination_rate=20, lockdown_threshold=0.2, seed=5)
-    ref = ref_mod.reference_tables(pop, ep, 500)
+    pop, ep, ref, exposure_rows = small_worlds[1]
     assert ref["records"]["vaccination_active"].any() and ref["records"]["lockdown"].any() and ref["records"]["exposures_bus"].sum() > 0
     assert (ref["current"] != ref["home"]).any()
+    assert (exposure_rows != ref["incidence"]).any()                  # (by the area stood in and without the buses: another table)
     sim = Simulator(pop, ep)
     if pipeline is not None:
         sim.set_pipeline(pipeline)
@@ -217,6 +252,7 @@ def test_small_worlds(pipeline):
     check_records(sim, ref)
     check_all(sim, ref, 500, "two areas")
     check_all(sim, ref, 500, "two areas", first_step=2, stride=5)
+    check_other_entry_points(sim, pop, ref, exposure_rows, 500, "two areas")
     sim.close()
 
 

@@ -2,7 +2,7 @@
 peak and with stride 24 over the whole run; beside them, alternated in one loop, esim_area_series(ESIM_SERIES_INFECTED) on the
 same windows (the existing route to the one table both produce: it must give the same table, or the tool stops), and, for the
 last row only, the host route (download_state followed by np.bincount).  Then, in a child process of its own under
-`rocprofv3 --kernel-trace --stats`, the device time of the new kernels per table.  Prints one JSON line; --out also writes it
+`rocprofv3 --kernel-trace --stats`, the device time of the series kernels (esim_kernels_series.h), summed over all those calls.  Prints one JSON line; --out also writes it
 to a file (default profiles/area_status_series_<preset>.json).
 
     python tools/area_status_series.py [preset] [steps] [repeats] [--no-trace] [--out FILE]
@@ -28,7 +28,7 @@ from epidemicsimulator_amd import Population, Simulator, _lib  # noqa: E402
 
 STATUS = ("susceptible", "exposed", "infected", "recovered", "vaccinated")
 TABLES = [(where, what) for where in ("home", "current") for what in STATUS] + [("home", "incidence")]
-KERNELS = ("k_area_status_log", "k_area_status_vax", "k_area_occupancy", "k_area_status_prefix", "k_area_vax_replay", "k_area_series", "k_area_prefix")
+KERNELS = ("k_series_log", "k_series_vax", "k_area_occupancy", "k_series_prefix", "k_area_vax_replay")
 TRACE_CALLS = 3
 
 
