@@ -41,6 +41,10 @@ void ckpt_header(const esim_ctx_impl *c, const Ctrl &h, CkptHeader *o)
     std::memcpy(o->thresholds, th, sizeof th);
 }
 
+// A run that was rolled back to a snapshot under another seed or vaccination rate has a history drawn under two parameter sets;
+// the header names one, and the format does not change for it.
+std::string seam_refusal() { return "the run was branched from a snapshot under another seed or vaccination_rate (esim_rollback): a checkpoint's header can name one parameter set only"; }
+
 size_t ckpt_bytes(const CkptHeader &k)
 {
     return sizeof(CkptHeader) + k.ctrl_bytes + sizeof(uint32_t) * ((size_t)TE_SLOTS + TE_SLOTS + 1 + k.n + k.log_len + 2u * ((size_t)k.host_t + 1u)) +
@@ -52,6 +56,7 @@ extern "C" int esim_checkpoint_size(esim_ctx *ctx, size_t *bytes)
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !bytes) return fail(c, ESIM_ESTATE, "no population uploaded");
+    if (c->seam.step) return fail(c, ESIM_ESTATE, "esim_checkpoint_size: " + seam_refusal());
     HIP_TRY(c, hipSetDevice(c->P.device));
     Ctrl h;
     const int rc = read_ctrl(c, &h);
@@ -66,6 +71,7 @@ extern "C" int esim_checkpoint_save(esim_ctx *ctx, void *buf, size_t cap)
 {
     esim_ctx_impl *c = CTX(ctx);
     if (!c || !c->uploaded || !buf) return fail(c, ESIM_ESTATE, "no population uploaded");
+    if (c->seam.step) return fail(c, ESIM_ESTATE, "esim_checkpoint_save: " + seam_refusal());
     HIP_TRY(c, hipSetDevice(c->P.device));
     const Dev &d = c->d;
     Ctrl h; int rc;

@@ -83,6 +83,25 @@ struct Groups {
     uint32_t *size = nullptr, *cnt = nullptr;
 };
 
+// esim_snapshot: the state at rest after `step` completed steps, kept on the device, with the parameters then in force; the
+// control block stays on the host, normalised as esim_checkpoint_restore normalises it (esim_rollback stages it from there).
+// The buffers are allocated at the first snapshot and kept; step == 0: none is held (dropped, or never taken).
+struct Snapshot {
+    uint32_t step = 0;
+    esim_params P;
+    Ctrl h;
+    uint32_t *words = nullptr, *hist = nullptr, *log_off = nullptr, *exp_step = nullptr;   // [n], [TE_SLOTS], [TE_SLOTS + 1], [2 * (cap_steps + 2)]
+    esim_step_result *records = nullptr;                                                    // [cap_steps + 1]
+    uint32_t *log = nullptr; size_t log_cap = 0;                                            // the log's prefix: grown when a snapshot needs more
+    // what the host knew of the run then, beside the control block (esim_rollback sets the host's view to match)
+    uint32_t last_chunk_pairs = 0; bool quiet = false, repair_armed = false, elig_seen = false;
+    uint64_t vax_chunk_steps = 0, vax_chunk_cuts = 0, vax_chunk_repairs = 0;
+};
+
+// esim_rollback with another seed or vaccination_rate: the steps up to and including `step` drew their vaccinations under the
+// old values, the later ones under those in force (run_shape and the vaccination replay).  step == 0: no seam.
+struct Seam { uint32_t step = 0, rate = 0; uint64_t seed = 0; };
+
 // What picks the form and the grids of the kernels: esim_set_* and the tuning knobs of the environment (read at upload).
 struct Tuning {
     uint32_t grid_citizens = 1, grid_infected = 1, grid_expose = 1;
@@ -125,6 +144,7 @@ struct esim_ctx_impl {
     bool quiet = false;                         // Ctrl::quiet at the last read-back of a burst of chunk passes
     bool repair_armed = false;                  // ... its two kernels are enqueued from the first cut of a run on (York never has one: 11 us a chunk saved)
     bool elig_seen = false;                     // the last control block read back had an eligible set (a vaccination programme runs)
+    uint32_t rest_t = 0;                        // host_t for which pin.ctrl is known to hold the control block at rest (0: not known; esim_snapshot)
     uint64_t vax_chunk_steps = 0, vax_chunk_cuts = 0, vax_chunk_repairs = 0;
     Timing tm;
     Comm comm;
@@ -132,6 +152,8 @@ struct esim_ctx_impl {
     RestartStaging rs;
     Ensemble ens;
     Groups grp;
+    Snapshot snap;
+    Seam seam;
     Tuning tune;
 };
 

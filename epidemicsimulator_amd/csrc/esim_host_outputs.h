@@ -141,7 +141,8 @@ int ensemble_zero(esim_ctx_impl *c)
 // What the series derive from the records of the steps run (rec[1 .. t_done]): the at-work bit after the schedule arm of every
 // step (citizen.rs:176-206: the arm of step s runs iff no lockdown was in force, i.e. the record of step s - 1 has none) and
 // the steps at which it changes; the step that started the vaccination programme (0: none) and the first one that vaccinated
-// the whole eligible set (0xFFFFFFFF: none).
+// the whole eligible set (0xFFFFFFFF: none).  The rate that decides the latter is the one the step was drawn under: the old one up to
+// the seam of an esim_rollback, the one in force behind it.
 struct RunShape { std::vector<uint8_t> aw; std::vector<uint32_t> tog; uint32_t trigger = 0, t_all = 0xFFFFFFFFu; };
 int run_shape(esim_ctx_impl *c, uint32_t t_done, RunShape *r)
 {
@@ -157,18 +158,29 @@ int run_shape(esim_ctx_impl *c, uint32_t t_done, RunShape *r)
         r->aw[s] = cur;
         if (cur != r->aw[s - 1u]) r->tog.push_back(s);
         if (!r->trigger && rec[s].vaccination_active) r->trigger = s;
-        if (r->trigger && r->t_all == 0xFFFFFFFFu && rec[s].eligible_count <= c->P.vaccination_rate) r->t_all = s;
+        if (r->trigger && r->t_all == 0xFFFFFFFFu && rec[s].eligible_count <= (s <= c->seam.step ? c->seam.rate : c->P.vaccination_rate)) r->t_all = s;
     }
     return ESIM_OK;
 }
 
 // vax_of[c] = the step at whose end citizen c was set Vaccinated, on the context's stream (steps that vaccinated the whole
-// eligible set apart: RunShape::t_all)
+// eligible set apart: RunShape::t_all).  Across the seam of an esim_rollback the choice is walked in two launches: the steps up to
+// the seam under the seed and rate they were drawn with, the later ones under those in force.
 hipError_t enqueue_vax_replay(esim_ctx_impl *c, uint32_t trigger, uint32_t t_done, uint32_t *d_vax)
 {
     const hipError_t e = hipMemsetAsync(d_vax, 0xFF, sizeof(uint32_t) * (size_t)c->d.n, c->stream);
-    if (e == hipSuccess)
-        hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(t_done - trigger + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, c->d, trigger, t_done, d_vax);
+    if (e != hipSuccess) return e;
+    auto walk = [&](const Dev &d, uint32_t first, uint32_t last) {
+        if (first <= last)
+            hipLaunchKernelGGL(k_area_vax_replay, dim3(std::min<uint32_t>(last - first + 1u, 1024u)), dim3(FIN_TPB), 0, c->stream, d, trigger, first, last, d_vax);
+    };
+    const uint32_t seam = std::min(c->seam.step, t_done);
+    if (seam >= trigger) {
+        Dev old = c->d;
+        old.seed_lo = (uint32_t)c->seam.seed; old.seed_hi = (uint32_t)(c->seam.seed >> 32); old.vaccination_rate = c->seam.rate;
+        walk(old, trigger, seam);
+    }
+    walk(c->d, std::max(trigger, seam + 1u), t_done);
     return e;
 }
 

@@ -418,10 +418,13 @@ extern "C" int esim_step(esim_ctx *ctx, esim_step_result *out)
     if (rc) return rc;
     if (c->d.n_shards > 1) return fail(c, ESIM_ESTATE, "esim_step: a sharded population runs with esim_run_sharded");
     HIP_TRY(c, hipSetDevice(c->P.device));
+    c->rest_t = 0;
     if ((rc = run_steps(c, 1, false, nullptr))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (out) HIP_TRY(c, hipMemcpy(out, &c->d.records[c->host_t - 1], sizeof *out, hipMemcpyDeviceToHost));
-    return device_error(c);
+    if ((rc = device_error(c))) return rc;
+    c->rest_t = c->host_t;                           // (device_error has just read the control block at rest into the pinned mirror)
+    return ESIM_OK;
 }
 
 extern "C" int esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done, esim_step_result *out_array, uint32_t *n_done)
@@ -443,6 +446,7 @@ extern "C" int esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done, esi
     // bursts of chunk passes bring their records back together with the control block (burst_readback); whatever other forms
     // ran is fetched below
     pin.track = out_array != nullptr; pin.first = first; pin.valid = 0; pin.ctrl_fresh = false;
+    c->rest_t = 0;
     rc = run_steps(c, n_steps, stop_when_done != 0, nullptr);
     pin.track = false;
     if (rc) return rc;
@@ -455,6 +459,7 @@ extern "C" int esim_run(esim_ctx *ctx, uint32_t n_steps, int stop_when_done, esi
         std::fprintf(stderr, "[esim] esim_run(%u steps from %u): done %u, t=%u steps_done=%u finished=%u chunk_ok=%u parallel=%u, records mirrored %u, control block %s\n",
                      n_steps, first, done, h.t, h.steps_done, h.finished, h.chunk_ok, h.chunk_parallel, pin.valid, pin.ctrl_fresh ? "from the burst" : "read now");
     c->host_t = first + done;
+    c->rest_t = c->host_t;                           // (the pinned mirror holds the control block at rest, whichever way it came)
     if (out_array && done) {
         const uint32_t have = std::min(pin.valid, done);
         if (have < done) {

@@ -256,6 +256,7 @@ extern "C" int esim_debug_inject_error(esim_ctx *ctx, int code)
     if (int rc = drain(c)) return rc;
     const uint32_t v = (uint32_t)(-code);
     HIP_TRY(c, hipMemcpy(&c->d.ctrl->error, &v, sizeof v, hipMemcpyHostToDevice));
+    c->rest_t = 0;                                                 // (the pinned mirror no longer is the control block as it stands)
     return ESIM_OK;
 }
 
@@ -347,6 +348,7 @@ extern "C" int esim_run_sharded(esim_ctx *ctx, uint32_t n_steps, uint32_t *n_don
     HIP_TRY(c, hipSetDevice(c->P.device));
     Dev &d = c->d;
     const uint32_t first = c->host_t;
+    c->rest_t = 0;
     // no early stop here (a shard's local census says nothing about the disease elsewhere, and shards that stopped at
     // different steps would issue different collectives): a flag an earlier esim_run left on the device is cleared
     static const uint32_t zero = 0u;

@@ -150,6 +150,7 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     c->ens.hit = c->ens.members = nullptr; c->ens.sum = c->ens.sumsq = nullptr;
     c->ens.valid = false;
     c->grp = Groups();                                             // (the labels belong to the population they were set for)
+    c->snap = Snapshot();                                          // (so does a snapshot: its buffers went with the rest)
     Dev &d = c->d;
     std::memset(&d, 0, sizeof d);
     d.n = N; d.n_global = u.n_global; d.id_base = pop->citizen_id_base; d.n_bld = B; d.n_room = R;
@@ -421,6 +422,8 @@ void rewind_host(esim_ctx_impl *c)
     c->last_chunk_pairs = (uint32_t)c->init_log.size();
     c->vax_chunk_steps = 0; c->vax_chunk_cuts = 0; c->elig_seen = false; c->repair_armed = false; c->quiet = false;
     c->pin.track = false; c->pin.ctrl_fresh = false;
+    c->rest_t = 0;
+    c->seam = Seam();                                              // (the history that starts here is drawn under one parameter set)
     c->tm.clear();
 }
 
@@ -503,6 +506,7 @@ int restart_enqueue(esim_ctx_impl *c, const esim_params *p, bool replace, const 
             if (CW_TE(c->init_state[sc]) != te) { c->init_state[sc] = CW_MAKE(te, c->init_state[sc] & CW_FLAGS); c->init_log.push_back(sc); }
         }
         c->pop_hash = hash_with_seeds(c->pop_hash_head, seeds, n_seeds);
+        c->snap.step = 0;                                          // (a snapshot belongs to the seeds it grew from: dropped, its buffers kept)
         if (!c->init_log.empty()) std::memcpy(c->rs.seeds_stage, c->init_log.data(), sizeof(uint32_t) * c->init_log.size());
     } else
         for (uint32_t sc : c->init_log) c->init_state[sc] = CW_MAKE(te, c->init_state[sc] & CW_FLAGS);   // (esim_reset's copy of the seeds' words)

@@ -30,3 +30,4 @@
 #include "esim_kernels_group.h"
 #include "esim_kernels_series.h"
 #include "esim_kernels_restart.h"
+#include "esim_kernels_snapshot.h"

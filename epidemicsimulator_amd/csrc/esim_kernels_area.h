@@ -104,6 +104,9 @@ __device__ __forceinline__ bool was_eligible(uint32_t w, uint32_t t, uint32_t tr
 // walked again, a workgroup per step, exactly as finish_phase walks it: the first `vaccination_rate` distinct live
 // candidates in candidate order.  vax_of[c] = the earliest step that chose c, for the citizens that are Vaccinated now.
 // Steps that vaccinated the whole set (eligible_count <= rate) are the caller's (Series::t_all).  One shard only.
+// The steps walked are t_first .. t_done, t_first >= trigger, under the seed and the rate of `d`: after an esim_rollback that
+// changed either, the host launches the steps up to the seam with the old values in its copy of `d` and the later ones with
+// those in force (enqueue_vax_replay).
 struct AreaVaxShared {
     uint32_t tab_key[VACC_TABLE];
     uint32_t tab_idx[VACC_TABLE];
@@ -111,12 +114,12 @@ struct AreaVaxShared {
     uint32_t s_total;
 };
 
-__global__ __launch_bounds__(FIN_TPB) void k_area_vax_replay(Dev d, uint32_t trigger, uint32_t t_done, uint32_t *vax_of)
+__global__ __launch_bounds__(FIN_TPB) void k_area_vax_replay(Dev d, uint32_t trigger, uint32_t t_first, uint32_t t_done, uint32_t *vax_of)
 {
     __shared__ AreaVaxShared sm;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     const uint32_t k = d.vaccination_rate;
-    for (uint32_t t = trigger + blockIdx.x; t <= t_done; t += gridDim.x) {
+    for (uint32_t t = t_first + blockIdx.x; t <= t_done; t += gridDim.x) {
         if (d.records[t].eligible_count <= k) continue;
         for (uint32_t i = tid; i < VACC_TABLE; i += FIN_TPB) { sm.tab_key[i] = 0xFFFFFFFFu; sm.tab_idx[i] = 0xFFFFFFFFu; }
         __syncthreads();

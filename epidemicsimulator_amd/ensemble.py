@@ -1,7 +1,8 @@
 """Ensembles of one uploaded population: many Philox seeds of one world, or the same world under several parameter sets,
 or under other index cases (where the outbreak starts), one member after another on ONE context (esim_restart,
 esim_restart_seeded), summarised per step on the host and per Output Area -- or per citizen group -- on the device
-(esim_ensemble_*).  The population is validated, hashed and uploaded once."""
+(esim_ensemble_*); or, as a forecast, as branches from one snapshot of a shared history (esim_snapshot, esim_rollback).  The
+population is validated, hashed and uploaded once."""
 import ctypes as C
 import json
 import os
@@ -154,6 +155,48 @@ class Ensemble:
                 sim.ensemble_fold()
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
+        records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
+        summary = None
+        if area is not None:
+            r = sim.ensemble_read()
+            summary = (arrival_summary if arrival else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
+        by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
+
+    def forecast(self, history_steps, members, n_steps, area=None):
+        """Given the epidemic as it stands after `history_steps` steps under the base parameters, what happens next: the base
+        run is made once and kept on the device (Simulator.snapshot), and every member is a branch from it -- a rollback under
+        the base parameters changed by the member's overrides, then the remaining n_steps - history_steps steps.  members as
+        for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
+        library refuses them).  area: as for run(), folded once per member.  Returns an EnsembleResult whose records are
+        [members, n_steps], the shared history repeated in every row."""
+        sim = self.simulator
+        history_steps, n_steps = int(history_steps), int(n_steps)
+        if not 1 <= history_steps <= n_steps:
+            raise ValueError("Ensemble.forecast: history_steps must be in 1..n_steps")
+        members = [dict(m) for m in members]
+        if any("index_cases" in m for m in members):
+            raise ValueError("Ensemble.forecast: a branch cannot change the index cases of the shared history")
+        arrival = False
+        if area is not None:
+            area = dict(area)
+            kind = area.pop("kind", "census")
+            if kind not in ("census", "arrival"):
+                raise ValueError("Ensemble.forecast: area kind must be 'census' or 'arrival', got %r" % (kind,))
+            arrival = kind == "arrival"
+            (sim.ensemble_begin_arrival if arrival else sim.ensemble_begin)(**area)
+        sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
+        self._own_seeds = True
+        history = sim.run(history_steps)
+        sim.snapshot()
+        rows, n_done = [], []
+        for m in members:
+            sim.rollback(**m)
+            rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
+            if area is not None:
+                sim.ensemble_fold()
+            n_done.append(len(history) + len(rec))
+            rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = None
         if area is not None:

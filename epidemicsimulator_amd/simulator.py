@@ -222,6 +222,42 @@ class Simulator:
         self.statistics_recorder = StatisticsRecorder()
         self._steps = 0
 
+    # -- forecast ensembles: a snapshot on the device and branches from it (esim_snapshot, esim_rollback) -------
+    def snapshot(self):
+        """Keeps the state after the last completed step on the device, with the parameters in force (esim_snapshot): one
+        snapshot per context, a later call replaces it.  Nothing proportional to the population moves to the host."""
+        _lib.check(self.lib.esim_snapshot(self._ctx), self._ctx)
+
+    def snapshot_step(self):
+        """The step of the snapshot held (esim_snapshot_info); 0: none."""
+        step = C.c_uint32(0)
+        _lib.check(self.lib.esim_snapshot_info(self._ctx, C.byref(step), None), self._ctx)
+        return int(step.value)
+
+    def rollback(self, params=None, **overrides):
+        """Back to the snapshot's step with other parameters in force from the next step on (esim_rollback): `params`, or the
+        snapshot's own parameters changed by `overrides` (e.g. seed=7, lockdown_threshold=0.01), as restart applies them.  The
+        times and the working hours must be the snapshot's.  The statistics recorder keeps the entries of the shared history."""
+        step = C.c_uint32(0)
+        p = _lib.Params()
+        _lib.check(self.lib.esim_snapshot_info(self._ctx, C.byref(step), C.byref(p)), self._ctx)
+        if params is not None:
+            C.memmove(C.byref(p), C.byref(params), C.sizeof(_lib.Params))
+        for k, v in overrides.items():
+            if not hasattr(p, k):
+                raise AttributeError("esim_params has no field %r" % k)
+            setattr(p, k, v)
+        own = params is None and not overrides
+        _lib.check(self.lib.esim_rollback(self._ctx, None if own else C.byref(p)), self._ctx)
+        self.params = p
+        self._steps = int(step.value)
+        sr = self.statistics_recorder
+        if len(sr.global_stats) >= self._steps and len(sr.exposures_all) >= self._steps:
+            del sr.global_stats[self._steps:], sr.exposures_all[self._steps:], sr.memory_usage_entries[self._steps:], sr.timer_entries[self._steps:]
+        else:                                   # (a reset or restart in between emptied it: the history comes back from the records)
+            self.statistics_recorder = StatisticsRecorder()
+            self.statistics_recorder.push_block(self.records_so_far())
+
     def seeds(self):
         """The distinct initially infected citizens in force, in the order of the exposure log (esim_get_seeds)."""
         n = C.c_uint32(0)

@@ -370,6 +370,40 @@ int  esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_
 int  esim_checkpoint_size(esim_ctx *ctx, size_t *bytes);
 int  esim_checkpoint_save(esim_ctx *ctx, void *buf, size_t cap);
 int  esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t bytes);
+/* Forecast ensembles: given the epidemic as it stands at step T, what happens next under other policies or other random
+ * futures.  esim_snapshot keeps, ON THE DEVICE, the state at rest after the last completed step together with the parameters in
+ * force: what a checkpoint holds (the control block, the census histogram, the log offsets, the citizen words, the exposure log,
+ * the per-step exposure counts and the records so far).  One snapshot per context, a later call replaces it.  Memory: 4 B per
+ * citizen, the prefixes of the log, the exposure counts and the records, and the small tables; allocated at the first call and
+ * kept.  Nothing proportional to the population moves to the host and nothing waits for the stream (the control block is taken
+ * from the host's pinned mirror, where esim_run and esim_step leave it; after any other way to this step it is read once, 200
+ * bytes).  The snapshot is self-contained: it survives esim_reset, esim_restart and further running; esim_upload_population,
+ * esim_restart_seeded (the seeds in force belong to the state) and esim_snapshot_drop drop it.
+ * ESIM_ESTATE: before an upload; at step 0 (that state is esim_restart's to rebuild); with a sticky device-side error pending;
+ * on a context whose communicator has more than one rank (the rule of esim_restart); on a branch with a seam (below).
+ * ESIM_ENOMEM: no device memory (the context and an earlier snapshot are then as they were).
+ * esim_rollback goes back to the snapshot's step with *p in force from the next step on; p == NULL: the snapshot's own
+ * parameters.  May differ from the snapshot's: seed, exposure_chance, mask_effectiveness, the four thresholds, vaccination_rate,
+ * bus_capacity.  Must equal the snapshot's, else ESIM_EINVAL: exposed_time, infected_time, start_hour, end_hour (the state and
+ * everything derived from the history afterwards is a function of them) and device.  max_steps follows the rule of
+ * esim_restart and may not lie below the snapshot's step (ESIM_ERANGE).  *p is validated as esim_create validates it, and its
+ * exposure_chance must be a probability (ESIM_EINVAL); a refused
+ * call leaves the context and the snapshot as they were; ESIM_ESTATE without a snapshot.  Host->device traffic: the control
+ * block and the threshold LUT (4.4 KB, from pinned memory); everything else is restored on the device, and nothing waits.  The
+ * records and log entries of the steps up to the snapshot's stay readable, those behind it are the branch's.
+ * The seam: the vaccination choice of a step is drawn from the seed and vaccination_rate in force, and the series calls walk it
+ * again after the fact.  After a rollback that changed either, the steps up to and including the snapshot's were drawn under the
+ * old values and the later ones under the new: the context keeps that one seam (step, old seed, old rate) until esim_reset,
+ * esim_restart, an upload or a rollback to the snapshot's own seed and rate, and the series calls honour it.  One seam is all
+ * there is: every branch leaves from the one snapshot, esim_snapshot on a branch with a seam is ESIM_ESTATE (a history mixed
+ * twice is not built), and so are esim_checkpoint_size and esim_checkpoint_save while the seam is in force (their header names
+ * one parameter set).
+ * esim_snapshot_info: the snapshot's step (0: none) and parameters; either pointer may be NULL.  Pure host code.
+ * esim_snapshot_drop: frees the snapshot's device memory (esim_destroy and a new upload free it too). */
+int  esim_snapshot(esim_ctx *ctx);
+int  esim_rollback(esim_ctx *ctx, const esim_params *p);
+int  esim_snapshot_info(esim_ctx *ctx, uint32_t *step, esim_params *p);
+int  esim_snapshot_drop(esim_ctx *ctx);
 
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
