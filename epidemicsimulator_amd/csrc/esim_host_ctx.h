@@ -331,6 +331,9 @@ int check_params(esim_ctx_impl *c, const esim_params *p, const std::string &who)
     }
     if (p->max_steps == 0 || p->max_steps > ESIM_MAX_STEP)
         return fail(c, ESIM_ERANGE, who + ": max_steps must be in 1..7600");
+    // (NaN fails both comparisons; esim_threshold_lut would cast ceil(NaN) to uint64_t)
+    if (!(p->exposure_chance >= 0.0 && p->exposure_chance <= 1.0))
+        return fail(c, ESIM_EINVAL, who + ": exposure_chance must be a probability");
     return ESIM_OK;
 }
 

@@ -107,7 +107,6 @@ extern "C" int esim_rollback(esim_ctx *ctx, const esim_params *p)
     const esim_params q = p ? *p : s.P;
     if (int rc = check_params(c, &q, who)) return rc;
     if (q.device != c->P.device) return fail(c, ESIM_EINVAL, who + ": device must be the context's device");
-    if (!(q.exposure_chance >= 0.0 && q.exposure_chance <= 1.0)) return fail(c, ESIM_EINVAL, who + ": exposure_chance must be a probability");
     if (q.exposed_time != s.P.exposed_time || q.infected_time != s.P.infected_time || q.start_hour != s.P.start_hour || q.end_hour != s.P.end_hour)
         return fail(c, ESIM_EINVAL, who + ": exposed_time, infected_time and the working hours must be the snapshot's (the state is a function of them)");
     if (q.max_steps > c->cap_steps) return fail(c, ESIM_ERANGE, who + ": max_steps above the max_steps the context was created with (the record log's capacity)");

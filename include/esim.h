@@ -117,7 +117,10 @@ void esim_default_params(esim_params *p);
 
 /* Replaces Simulator::from(SimulatorBuilder) (simulator.rs:601-644): creates the device
  * context; esim_upload_population copies the population to HBM and builds the derived
- * tables (route lists, probability-threshold LUT). */
+ * tables (route lists, probability-threshold LUT).  The parameters are checked before the device is touched: ESIM_ERANGE for
+ * exposed_time + infected_time + 2 > 512, vaccination_rate > 8192, max_steps outside 1..7600; ESIM_EINVAL for bus_capacity 0,
+ * working hours outside 1..23 or with start_hour-1, start_hour, end_hour-1, end_hour not four different hours, and for an
+ * exposure_chance that is no probability (NaN, negative, above 1). */
 int  esim_create(const esim_params *p, esim_ctx **out);
 int  esim_upload_population(esim_ctx *ctx, const esim_population *pop);
 /* Back to time step 0 with the uploaded population (all Susceptible, seeds Infected(0)). */
@@ -386,8 +389,8 @@ int  esim_checkpoint_restore(esim_ctx *ctx, const void *buf, size_t bytes);
  * parameters.  May differ from the snapshot's: seed, exposure_chance, mask_effectiveness, the four thresholds, vaccination_rate,
  * bus_capacity.  Must equal the snapshot's, else ESIM_EINVAL: exposed_time, infected_time, start_hour, end_hour (the state and
  * everything derived from the history afterwards is a function of them) and device.  max_steps follows the rule of
- * esim_restart and may not lie below the snapshot's step (ESIM_ERANGE).  *p is validated as esim_create validates it, and its
- * exposure_chance must be a probability (ESIM_EINVAL); a refused
+ * esim_restart and may not lie below the snapshot's step (ESIM_ERANGE).  *p is validated as esim_create validates it (its
+ * exposure_chance must be a probability, ESIM_EINVAL); a refused
  * call leaves the context and the snapshot as they were; ESIM_ESTATE without a snapshot.  Host->device traffic: the control
  * block and the threshold LUT (4.4 KB, from pinned memory); everything else is restored on the device, and nothing waits.  The
  * records and log entries of the steps up to the snapshot's stay readable, those behind it are the branch's.

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import _oracle
+from _param_edges import random_population  # noqa: F401  (its home; other test modules import it from here)
 from epidemicsimulator_amd import Population, Simulator, _lib
 
 pytestmark = pytest.mark.gpu
@@ -482,34 +483,6 @@ def test_simulate_device_resident_blocks(tmp_path, capsys):
     gone = json.load(open(str(tmp_path) + "/gone/global_stats.json"))
     assert len(gone) == 337 + 1 and gone[336]["recovered"] == n
     sim1.close()
-
-
-def random_population(seed, n=700, n_areas=5, n_buildings=90, n_schools=3, rooms_per_school=4):
-    """Anything the ABI allows, not just what the reference's builder produces: workplaces in other areas,
-    people working in somebody's household, tiny and empty buildings, rooms with one member, citizens that
-    are not sorted by home (exercises res_idx), duplicate seeds."""
-    rng = np.random.default_rng(seed)
-    b_area = rng.integers(0, n_areas, n_buildings).astype(np.uint32)
-    b_type = rng.choice([_lib.HOUSEHOLD, _lib.WORKPLACE], n_buildings, p=[0.7, 0.3]).astype(np.uint8)
-    schools = rng.choice(n_buildings, n_schools, replace=False)
-    b_type[schools] = _lib.SCHOOL
-    room_bld = np.repeat(schools, rooms_per_school).astype(np.uint32)
-    not_school = np.nonzero(b_type != _lib.SCHOOL)[0]
-    home = rng.choice(not_school, n).astype(np.uint32)                 # unsorted on purpose
-    work = home.copy()
-    room = np.full(n, _lib.NO_ROOM, np.uint32)
-    kind = rng.random(n)
-    w = kind < 0.45                                                    # works in any non-school building, any area
-    work[w] = rng.choice(not_school, int(w.sum()))
-    sc = (kind >= 0.45) & (kind < 0.8)                                 # school member in a random room
-    r = rng.integers(0, len(room_bld), int(sc.sum()))
-    room[sc] = r
-    work[sc] = room_bld[r]
-    flags = (rng.random(n) < 0.5).astype(np.uint8) | ((rng.random(n) < 0.6).astype(np.uint8) << 1)
-    seeds = rng.integers(0, n, 9).astype(np.uint32)
-    seeds[-1] = seeds[0]
-    return Population(home_building=home, work_building=work, room=room, flags=flags, building_area=b_area,
-                      building_type=b_type, room_building=room_bld, seeds=seeds, n_areas=n_areas)
 
 
 def test_one_huge_workplace_overflows_a_unit_queue():

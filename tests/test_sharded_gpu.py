@@ -71,6 +71,30 @@ def test_three_uneven_shards_match_oracle():
     assert all("ok" in o for o in outs)
 
 
+# two parameter edges (tests/_param_edges.py has the unsharded cases); tests/test_param_edges.py checks on the CPU, over the oracle's
+# records of the whole world, that both are live: building and bus exposures, all three mask states, riders at the hours meant
+EDGE_SPEC = dict(n_citizens=12000, n_areas=40, citizens_per_school=2500, n_seeds=16)
+# exposed_time 2: a chunk is three steps, shorter than a Philox block of four, and buffer F covers three steps; the worker
+# checks that steps did run as sharded chunks
+CHUNK_OF_THREE = dict(backend="gloo", cuts="even", spec=EDGE_SPEC, params=dict(AGGRESSIVE, exposed_time=2), steps=240, chunk=120,
+                      expect=dict(vaccinated=1))
+# start_hour 22 > end_hour 6: the bus hours and the at-work stretch wrap midnight.  No programme starts in these 240 steps: the
+# sharded chunks without one, with building and bus exposures across the cut.  The last record has more Infected than the 16
+# seeds (citizens exposed in the run), citizens still Exposed, and masks everywhere
+NIGHT_SHIFT = dict(backend="gloo", cuts="even", spec=EDGE_SPEC, params=dict(AGGRESSIVE, start_hour=22, end_hour=6), steps=240, chunk=120,
+                   expect=dict(infected=17, exposed=1, mask_status=2))
+
+
+def test_two_shards_with_chunks_of_three_steps_match_oracle():
+    outs = launch(2, CHUNK_OF_THREE)
+    assert all("ok" in o for o in outs)
+
+
+def test_two_shards_on_a_night_shift_match_oracle():
+    outs = launch(2, NIGHT_SHIFT)
+    assert all("ok" in o for o in outs)
+
+
 def test_least_crossed_cuts_through_the_vaccination_programme_match_oracle():
     cfg = dict(backend="gloo", cuts="clean", spec=dict(n_citizens=12000, n_areas=40, citizens_per_school=2500, n_seeds=16),
                params=AGGRESSIVE, steps=600, chunk=150, expect=dict(vaccinated=1000))
