@@ -2,6 +2,7 @@
 // the one-pass form (k_chunk_marks, k_chunk_draw, k_chunk_units, k_chunk_books [+ k_chunk_count, k_chunk_scatter]) and the
 // books of a chunk that ran step by step (k_batch_finish).
 #pragma once
+#include "esim_rank.h"
 // ------------------------------------------------------------------------------- chunk set-up
 // A citizen exposed in step t is Infected no earlier than step t + exposed_time + 1 (disease.rs:47-71), so the
 // Infected census of the next <= exposed_time + 1 steps is already fixed -- as long as nobody is vaccinated.
@@ -1171,6 +1172,7 @@ struct RouteShared {
     uint16_t s_bus[CHUNK_ROUTE_MAX];
     uint8_t s_inf[CHUNK_ROUTE_MAX];
     uint32_t s_cnt[CHUNK_ROUTE_MAX + 1];
+    uint32_t s_seen[CHUNK_ROUTE_MAX / 32u];               // ranks handed out (rank_seen)
 };
 // Per wavefront: the item's / the school's Infected per step; 64 staged members; the item's slots of four time steps
 // (item_steps_regs).  A slot's descriptor is eight words: [0] first step of the slot + 3 (bits 0-6; a slot may begin up to three
@@ -1451,19 +1453,26 @@ __device__ __forceinline__ void route_pair_small(const Dev &d, Ctrl *ctrl, const
     // Nobody Infected aboard, or nobody who could still be exposed: no draw is made, whatever the buses (the order of the riders
     // is only needed to tell who shares a bus with whom).  A route that fills one bus at most needs no order either.
     if (!__any(inf) || !__any(can)) return;
+    const uint32_t cap = d.bus_capacity;
     uint32_t rank = 0;
-    if (sz > d.bus_capacity) {
+    if (sz > cap) {
         if (lane < sz) key = philox4x32_10(d.id_base + c, s, ESIM_SLOT_BUS_ORDER, 0u, d.seed_lo, d.seed_hi).w0;
-        for (uint32_t i = 0; i < sz; ++i) {
-            const uint32_t ki = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)i);   // i is uniform: a scalar broadcast
-            rank += ki < key || (ki == key && i < lane);                     // ids ascend with the lane
-        }
+        rank = rank_wave64(key, lane, sz);
     }
-    const uint32_t bus = rank / d.bus_capacity;
+    // The bus of a rank, and the buses of the route.  At most 64 riders in buses of 16 or more are four buses at most: the bus is
+    // the number of b >= 1 with rank >= b * cap, no division (the hardware has no scalar one: a uniform divisor costs the same
+    // 14 vector instructions as any).  Smaller buses divide.
+    uint32_t bus, n_bus;
+    if (cap >= 16u) {
+        bus = (rank >= cap ? 1u : 0u) + (rank >= 2u * cap ? 1u : 0u) + (rank >= 3u * cap ? 1u : 0u);
+        n_bus = 1u + (sz > cap ? 1u : 0u) + (sz > 2u * cap ? 1u : 0u) + (sz > 3u * cap ? 1u : 0u);
+    } else {
+        bus = rank / cap;
+        n_bus = (sz + cap - 1u) / cap;
+    }
     // Infected riders on my bus: one ballot per bus of the route
     const unsigned long long inf_m = __ballot(inf);
     uint32_t k = 0;
-    const uint32_t n_bus = (sz + d.bus_capacity - 1u) / d.bus_capacity;
     for (uint32_t b = 0; b < n_bus; ++b) {
         const unsigned long long on_b = __ballot(lane < sz && bus == b);
         if (bus == b) k = (uint32_t)__popcll(on_b & inf_m);
@@ -1474,7 +1483,6 @@ __device__ __forceinline__ void route_pair_small(const Dev &d, Ctrl *ctrl, const
         if (esim_u32(seed, d.id_base + c, s, ESIM_SLOT_BUS) < sm.thr[row * 256u + (k & 255u)]) { WORK_ADD(WK_HITS, 1); expose_min(d, ctrl, c, w, s, CW_BUS_EXPOSED); }
     }
 }
-
 // One (route of more than 64 riders, bus step) pair, by a whole workgroup of NT threads: ranks through LDS (simulator.rs:362-401).
 template <uint32_t NT>
 __device__ __forceinline__ void route_pair_big(const Dev &d, Ctrl *ctrl, const ChunkShared &sm, RouteShared &rs, uint32_t code, uint32_t t0, uint32_t n WORK_ARG)
@@ -1501,16 +1509,28 @@ __device__ __forceinline__ void route_pair_big(const Dev &d, Ctrl *ctrl, const C
     for (uint32_t i = threadIdx.x; i < sz; i += NT)
         rs.s_key[i] = philox4x32_10(d.id_base + d.route_riders[off + i], s, ESIM_SLOT_BUS_ORDER, 0u, d.seed_lo, d.seed_hi).w0;
     for (uint32_t i = threadIdx.x; i < sz / d.bus_capacity + 1u; i += NT) rs.s_cnt[i] = 0u;
+    for (uint32_t i = threadIdx.x; i < (sz + 31u) / 32u; i += NT) rs.s_seen[i] = 0u;
     __syncthreads();
+    // ranks by key alone, and a look whether two riders were given the same one (they shared a key: about once in 10^7 pairs)
+    int tie = 0;
     for (uint32_t i = threadIdx.x; i < sz; i += NT) {
-        const uint32_t ki = rs.s_key[i];
-        uint32_t rank = 0;
-        for (uint32_t qq = 0; qq < sz; ++qq) { const uint32_t kq = rs.s_key[qq]; rank += kq < ki || (kq == ki && qq < i); }
+        const uint32_t rank = rank_block(rs.s_key, rs.s_key[i], sz);
+        tie |= rank_seen(rs.s_seen, rank) ? 1 : 0;
         const uint32_t bus = rank / d.bus_capacity;
         rs.s_bus[i] = (uint16_t)bus;
         if (rs.s_inf[i]) atomicAdd(&rs.s_cnt[bus], 1u);
     }
-    __syncthreads();
+    if (__syncthreads_or(tie)) {
+        // ... then once more, by (key, index)
+        for (uint32_t i = threadIdx.x; i < sz / d.bus_capacity + 1u; i += NT) rs.s_cnt[i] = 0u;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < sz; i += NT) {
+            const uint32_t bus = rank_block_exact(rs.s_key, rs.s_key[i], i, sz) / d.bus_capacity;
+            rs.s_bus[i] = (uint16_t)bus;
+            if (rs.s_inf[i]) atomicAdd(&rs.s_cnt[bus], 1u);
+        }
+        __syncthreads();
+    }
     for (uint32_t i = threadIdx.x; i < sz; i += NT) {
         const uint32_t k = rs.s_cnt[rs.s_bus[i]];
         if (!k) continue;
