@@ -57,6 +57,7 @@ struct Pinned {
     bool ctrl_fresh = false;                      // ctrl holds the control block as it stands (nothing was enqueued since)
     uint32_t *area = nullptr; size_t area_n = 0;  // esim_area_census: mirror of the count table, [n_areas * 5]
     uint32_t *grp = nullptr;                      // esim_group_census: the same, [ESIM_MAX_GROUPS * 5]
+    uint8_t *aw = nullptr;                        // a series fold: the at-work bit per step as run_shape derived it, [cap_steps + 1], on its way to the device
 };
 
 // esim_restart: the distinct seeds on the device; control block and threshold LUT staged in pinned memory, an event behind their copies.
@@ -75,6 +76,18 @@ struct Ensemble {
     int where = ESIM_AREA_HOME; uint32_t mask = 0, min = 0;
     bool arrival = false; uint32_t horizon = 0;   // esim_ensemble_begin_arrival: a member contributes its arrival step, reached = arrival <= horizon
     uint32_t n = 0; bool valid = false;           // entries in use (n_areas, or n_groups by group); false: the labels they were begun for are gone
+    // esim_ensemble_begin_series: accumulators of their own, [n_rows][n_cols] each, beside the row plane(s) the series engine
+    // writes a member's rows into and the engine's small temporaries -- all kept from the begin on, so that a fold allocates
+    // nothing proportional to rows x columns (the 4 B per citizen of the vaccination replay: at the first fold that needs them).
+    // series == true: this kind is in force (where, n and valid as for the other two).
+    struct Rows {
+        uint32_t *hit = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
+        unsigned long long *sum = nullptr, *sumsq = nullptr;
+        uint8_t *aw = nullptr;
+        int what = 0; uint32_t first = 0, n_rows = 0, stride = 0, min = 0, n_cols = 0;
+        bool two = false;                         // p1 is allocated: status rows by the area stood in
+    } rows;
+    bool series = false;
 };
 
 // esim_set_groups: a label per citizen, the groups' sizes and the count table of esim_group_census [n * 5] (nullptr: no labels).
@@ -385,7 +398,7 @@ extern "C" void esim_destroy(esim_ctx *ctx)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_device(c);
     c->tm.destroy();
-    for (void *p : { (void *)c->pin.ctrl, (void *)c->pin.rec, (void *)c->pin.area, (void *)c->pin.grp, (void *)c->rs.stage, (void *)c->rs.seeds_stage })
+    for (void *p : { (void *)c->pin.ctrl, (void *)c->pin.rec, (void *)c->pin.area, (void *)c->pin.grp, (void *)c->pin.aw, (void *)c->rs.stage, (void *)c->rs.seeds_stage })
         if (p) (void)hipHostFree(p);
     if (c->rs.ev) (void)hipEventDestroy(c->rs.ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -199,62 +199,132 @@ int census_readback(esim_ctx_impl *c, const uint32_t *table, uint32_t *mirror, s
 // calls the status rows, the column key, the status or SERIES_EVENTS, and whether event rows leave out public transport.
 struct SeriesSpec { const char *who, *rows; uint32_t key, what; bool skip_bus, pieces; };
 
-// The series behind their own argument checks: n_rows rows of one column per area / group, out[row * columns + column], counted
-// from the exposure log and the citizen words into one plane, or two for the status rows by the area stood in, and summed up over
-// the steps by k_series_prefix, which leaves the result in plane 0.  Status rows are derived by replaying the vaccinations once a
-// programme has run.
-int series_rows(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+// What the engine works out before it enqueues anything: which of its passes the rows need and how much room they take.
+struct SeriesPlan {
+    bool events, by_group, stood, sus, two, replay, count_occ;
+    uint32_t t_done, cols, log_len;
+    size_t words, occ_words;                                  // (occupancy of plane 0, then of plane 1)
+    RunShape shape;
+};
+
+// Where the engine works: the row plane(s) and its temporaries on the device -- a call's own or the caller's -- and the host
+// memory the at-work bits are copied from, which has to stay as it is until the stream has run the copy.
+struct SeriesBufs { uint32_t *p0, *p1, *occ, *tog, *vax; uint8_t *aw; const uint8_t *h_aw; };
+
+// The first half of the engine: the window checked against the steps run, the one wait for the stream (the control block and the
+// records behind it), the run's shape derived from the records on the host.
+int series_plan(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_step, uint32_t n_rows, uint32_t stride, SeriesPlan *p)
 {
     const std::string who = s.who;
-    const bool events = s.what == SERIES_EVENTS, by_group = s.key == KEY_GROUP, stood = s.key == KEY_STOOD, sus = s.what == ESIM_SUSCEPTIBLE;
-    const bool two = stood && !events && !s.pieces;           // (an event is credited to one column of plane 0)
-    const uint32_t t_done = c->host_t - 1u;                   // steps run so far
-    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > t_done)
+    p->events = s.what == SERIES_EVENTS; p->by_group = s.key == KEY_GROUP; p->stood = s.key == KEY_STOOD; p->sus = s.what == ESIM_SUSCEPTIBLE;
+    p->two = p->stood && !p->events && !s.pieces;             // (an event is credited to one column of plane 0)
+    p->t_done = c->host_t - 1u;                               // steps run so far
+    if (first_step == 0 || (uint64_t)first_step + (uint64_t)(n_rows - 1u) * stride > p->t_done)
         return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
     HIP_TRY(c, hipSetDevice(c->P.device));
     const Dev &d = c->d;
     Ctrl h; int rc;
     if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
-    RunShape shape;
-    if ((rc = run_shape(c, t_done, &shape))) return rc;
-    const bool replay = !events && shape.trigger != 0u;
-    if (replay && d.n_global != d.n)
+    if ((rc = run_shape(c, p->t_done, &p->shape))) return rc;
+    p->replay = !p->events && p->shape.trigger != 0u;
+    if (p->replay && d.n_global != d.n)
         return fail(c, ESIM_ESTATE, who + ": the " + s.rows + " rows of a shard cannot be derived once a vaccination programme has run (the choice depends on the other shards' citizens)");
-    const uint32_t cols = by_group ? c->grp.n : d.n_areas;
-    const size_t words = (size_t)n_rows * cols;
-    const bool count_occ = sus && !by_group;                  // (a group's occupancy is its size)
-    const size_t occ_words = (size_t)cols * (two ? 2u : 1u);  // (occupancy of plane 0, then of plane 1)
+    p->cols = p->by_group ? c->grp.n : d.n_areas;
+    p->words = (size_t)n_rows * p->cols;
+    p->count_occ = p->sus && !p->by_group;                    // (a group's occupancy is its size)
+    p->occ_words = (size_t)p->cols * (p->two ? 2u : 1u);
+    p->log_len = std::min<uint32_t>(h.log_len, d.n);
+    return ESIM_OK;
+}
+
+// The second half: n_rows rows of one column per area / group, [row * columns + column], counted from the exposure log and the
+// citizen words into one plane, or two for the status rows by the area stood in, and summed up over the steps by k_series_prefix,
+// which leaves the result in plane 0 -- all on the context's stream, nothing waited for.  Status rows are derived by replaying
+// the vaccinations once a programme has run.
+hipError_t series_enqueue(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_step, uint32_t n_rows, uint32_t stride, const SeriesPlan &p, const SeriesBufs &b)
+{
+    const Dev &d = c->d;
+    const RunShape &shape = p.shape;
+    hipError_t e = hipMemsetAsync(b.p0, 0, sizeof(uint32_t) * std::max<size_t>(1, p.words), c->stream);
+    if (e == hipSuccess && p.two) e = hipMemsetAsync(b.p1, 0, sizeof(uint32_t) * std::max<size_t>(1, p.words), c->stream);
+    if (e == hipSuccess && p.stood) e = hipMemcpyAsync(b.aw, b.h_aw, shape.aw.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && s.pieces && !shape.tog.empty()) e = hipMemcpyAsync(b.tog, shape.tog.data(), sizeof(uint32_t) * shape.tog.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && p.count_occ) e = hipMemsetAsync(b.occ, 0, sizeof(uint32_t) * std::max<size_t>(1, p.occ_words), c->stream);
+    if (e == hipSuccess && p.replay) e = enqueue_vax_replay(c, shape.trigger, p.t_done, b.vax);
+    if (e != hipSuccess) return e;
+    Series q;
+    q.what = s.what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = p.t_done; q.t_all = shape.t_all;
+    q.vax_of = p.replay ? b.vax : nullptr; q.at_work = p.stood ? b.aw : nullptr; q.p0 = b.p0; q.p1 = p.two ? b.p1 : nullptr;
+    q.n_cols = p.cols; q.key = s.key; q.grp = p.by_group ? c->grp.lab : nullptr; q.skip_bus = s.skip_bus;
+    q.n_tog = s.pieces ? (uint32_t)shape.tog.size() : 0u; q.tog = s.pieces ? b.tog : nullptr;
+    const uint32_t *occ0 = !p.sus ? nullptr : p.by_group ? c->grp.size : b.occ, *occ1 = p.sus && p.two ? b.occ + p.cols : nullptr;
+    if (s.what != ESIM_VACCINATED)
+        hipLaunchKernelGGL(k_series_log, dim3(grid_for(p.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, p.log_len);
+    if (p.replay && (s.what == ESIM_VACCINATED || p.sus))         // (nobody is Vaccinated before a programme has run)
+        hipLaunchKernelGGL(k_series_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
+    if (p.count_occ) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, b.occ, p.two ? b.occ + p.cols : nullptr);
+    if (!p.events)
+        hipLaunchKernelGGL(k_series_prefix, dim3(grid_for(p.cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, occ0, occ1);
+    return hipSuccess;
+}
+
+// The series behind their own argument checks: the engine's two halves in buffers that live as long as the call, the wait for
+// the rows, and plane 0 copied out.
+int series_rows(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)
+{
+    const std::string who = s.who;
+    SeriesPlan p;
+    if (int rc = series_plan(c, s, first_step, n_rows, stride, &p)) return rc;
     DevTmp<uint8_t> d_aw; DevTmp<uint32_t> d_vax, d_p0, d_p1, d_occ, d_tog;
-    if (d_p0.alloc(words) != hipSuccess || (s.pieces && d_tog.alloc(shape.tog.size()) != hipSuccess) || (two && d_p1.alloc(words) != hipSuccess) || (stood && d_aw.alloc(shape.aw.size()) != hipSuccess) ||
-        (count_occ && d_occ.alloc(occ_words) != hipSuccess) || (replay && d_vax.alloc(d.n) != hipSuccess)) {
+    if (d_p0.alloc(p.words) != hipSuccess || (s.pieces && d_tog.alloc(p.shape.tog.size()) != hipSuccess) || (p.two && d_p1.alloc(p.words) != hipSuccess) || (p.stood && d_aw.alloc(p.shape.aw.size()) != hipSuccess) ||
+        (p.count_occ && d_occ.alloc(p.occ_words) != hipSuccess) || (p.replay && d_vax.alloc(c->d.n) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(c, ESIM_ENOMEM, who + ": no device memory for the rows (ask for fewer)");
     }
-    hipError_t e = hipMemsetAsync(d_p0.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
-    if (e == hipSuccess && two) e = hipMemsetAsync(d_p1.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream);
-    if (e == hipSuccess && stood) e = hipMemcpyAsync(d_aw.p, shape.aw.data(), shape.aw.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && s.pieces && !shape.tog.empty()) e = hipMemcpyAsync(d_tog.p, shape.tog.data(), sizeof(uint32_t) * shape.tog.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && count_occ) e = hipMemsetAsync(d_occ.p, 0, sizeof(uint32_t) * std::max<size_t>(1, occ_words), c->stream);
-    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, d_vax.p);
-    if (e == hipSuccess) {
-        Series q;
-        q.what = s.what; q.first = first_step; q.n_rows = n_rows; q.stride = stride; q.t_done = t_done; q.t_all = shape.t_all;
-        q.vax_of = d_vax.p; q.at_work = d_aw.p; q.p0 = d_p0.p; q.p1 = d_p1.p;
-        q.n_cols = cols; q.key = s.key; q.grp = by_group ? c->grp.lab : nullptr; q.skip_bus = s.skip_bus;
-        q.n_tog = s.pieces ? (uint32_t)shape.tog.size() : 0u; q.tog = d_tog.p;
-        const uint32_t log_len = std::min<uint32_t>(h.log_len, d.n);
-        const uint32_t *occ0 = !sus ? nullptr : by_group ? c->grp.size : d_occ.p, *occ1 = sus && two ? d_occ.p + cols : nullptr;
-        if (s.what != ESIM_VACCINATED)
-            hipLaunchKernelGGL(k_series_log, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, log_len);
-        if (replay && (s.what == ESIM_VACCINATED || sus))            // (nobody is Vaccinated before a programme has run)
-            hipLaunchKernelGGL(k_series_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
-        if (count_occ) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, d_occ.p, two ? d_occ.p + cols : nullptr);
-        if (!events)
-            hipLaunchKernelGGL(k_series_prefix, dim3(grid_for(cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, occ0, occ1);
-        e = hipStreamSynchronize(c->stream);                      // (the host vector above is done with here, too)
-    } else (void)hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && words) e = hipMemcpy(out, d_p0.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost);
+    const SeriesBufs b = { d_p0.p, d_p1.p, d_occ.p, d_tog.p, d_vax.p, d_aw.p, p.shape.aw.data() };
+    hipError_t e = series_enqueue(c, s, first_step, n_rows, stride, p, b);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // (the host vectors above are done with here, too)
+    else (void)hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && p.words) e = hipMemcpy(out, d_p0.p, sizeof(uint32_t) * p.words, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
+    return ESIM_OK;
+}
+
+// (where, what) of esim_ensemble_begin_series as the series entry point whose rows a member contributes.
+SeriesSpec fold_spec(int where, int what)
+{
+    const char *who = "esim_ensemble_fold";
+    if (where == ESIM_BY_GROUP) return {who, "status", KEY_GROUP, (uint32_t)what, false, false};                       // esim_group_series
+    if (where == ESIM_AREA_CURRENT && what == (int)SERIES_EVENTS) return {who, "status", KEY_STOOD, SERIES_EVENTS, true, false};   // esim_area_series(EXPOSURES)
+    return {who, "status", where == ESIM_AREA_CURRENT ? KEY_STOOD : KEY_HOME, (uint32_t)what, false, false};          // esim_area_status_series
+}
+
+// The accumulators and kept buffers of a series kind back to the device (nothing may still be using them).
+void rows_free(esim_ctx_impl *c, Ensemble::Rows *r)
+{
+    for (void *q : { (void *)r->hit, (void *)r->members, (void *)r->p0, (void *)r->p1, (void *)r->occ, (void *)r->vax, (void *)r->sum, (void *)r->sumsq, (void *)r->aw }) dev_free(c, q);
+    *r = Ensemble::Rows();
+}
+
+// One member's rows, as the engine leaves them in the kept planes, folded into the accumulators of a series kind.
+int fold_series(esim_ctx_impl *c)
+{
+    Ensemble::Rows &r = c->ens.rows;
+    const SeriesSpec s = fold_spec(c->ens.where, r.what);
+    SeriesPlan p;
+    if (int rc = series_plan(c, s, r.first, r.n_rows, r.stride, &p)) return rc;
+    if (p.cols != r.n_cols || p.two != r.two) return fail(c, ESIM_ESTATE, "esim_ensemble_fold: the accumulators were begun for other columns");
+    if (p.replay && !r.vax) {
+        if (int rc = dev_alloc(c, &r.vax, c->d.n)) { (void)hipGetLastError(); return rc; }
+    }
+    if (p.stood) std::memcpy(c->pin.aw, p.shape.aw.data(), p.shape.aw.size());   // (the stream is idle behind series_plan's wait)
+    const SeriesBufs b = { r.p0, r.p1, r.occ, nullptr, r.vax, r.aw, c->pin.aw };
+    const hipError_t e = series_enqueue(c, s, r.first, r.n_rows, r.stride, p, b);
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_ensemble_fold: ") + hipGetErrorString(e));
+    const uint64_t cells = (uint64_t)p.words;
+    hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(grid_for((size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream,
+                       r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
+    HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
 }  // namespace
@@ -292,7 +362,7 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
     if (where == ESIM_BY_GROUP && (!c->grp.lab || c->comm.world > 1)) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: by group without labels (esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
     if (int rc = ensemble_zero(c)) return rc;
-    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases; c->ens.arrival = false;
+    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases; c->ens.arrival = false; c->ens.series = false;
     c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
     return ESIM_OK;
 }
@@ -303,7 +373,7 @@ extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t ho
     if (int rc = arrival_check(c, where, "esim_ensemble_begin_arrival")) return rc;
     HIP_TRY(c, hipSetDevice(c->P.device));
     if (int rc = ensemble_zero(c)) return rc;
-    c->ens.where = where; c->ens.arrival = true; c->ens.horizon = horizon;
+    c->ens.where = where; c->ens.arrival = true; c->ens.series = false; c->ens.horizon = horizon;
     c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
     return ESIM_OK;
 }
@@ -311,8 +381,9 @@ extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t ho
 extern "C" int esim_ensemble_fold(esim_ctx *ctx)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens.hit || !c->ens.valid)
+    if (!c->uploaded || !c->ens.valid || !(c->ens.series ? c->ens.rows.hit : c->ens.hit))
         return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
+    if (c->ens.series) return fold_series(c);
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;
     const bool by_group = c->ens.where == ESIM_BY_GROUP;
@@ -333,6 +404,8 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
 extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (c->uploaded && c->ens.valid && c->ens.series)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read: the accumulators in force were begun by esim_ensemble_begin_series (read them with esim_ensemble_read_series)");
     if (!c->uploaded || !c->ens.hit || !c->ens.valid)
         return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
@@ -343,6 +416,67 @@ extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hi
     if (hit && na) HIP_TRY(c, hipMemcpy(hit, c->ens.hit, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
     if (sum && na) HIP_TRY(c, hipMemcpy(sum, c->ens.sum, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
     if (sumsq && na) HIP_TRY(c, hipMemcpy(sumsq, c->ens.sumsq, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
+    return ctrl_error(c, h);
+}
+
+// ---- the same over the rows of a series: [n_rows][n_cols] accumulators, a member's rows left on the device ---------------
+extern "C" int esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t min_cases)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if ((where != ESIM_AREA_CURRENT && where != ESIM_AREA_HOME && where != ESIM_BY_GROUP) || what < ESIM_SUSCEPTIBLE || what > (int)SERIES_EVENTS || stride == 0 || n_rows == 0)
+        return fail(c, ESIM_EINVAL, "esim_ensemble_begin_series: unknown `where` or `what`, stride 0 or no rows");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin_series: no population uploaded");
+    if (c->comm.world > 1) return fail(c, ESIM_ESTATE, "esim_ensemble_begin_series: the context has a communicator of several ranks (the rule of esim_restart)");
+    if (where == ESIM_BY_GROUP && !c->grp.lab) return fail(c, ESIM_ESTATE, "esim_ensemble_begin_series: by group without labels (esim_set_groups)");
+    if (first_step == 0) return fail(c, ESIM_ERANGE, "esim_ensemble_begin_series: first_step is 1-based");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const SeriesSpec s = fold_spec(where, what);
+    const uint32_t cols = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas;
+    const bool two = s.key == KEY_STOOD && s.what != SERIES_EVENTS;
+    const size_t cells = (size_t)n_rows * cols;
+    Ensemble::Rows &old = c->ens.rows;
+    if (!old.hit || old.n_rows != n_rows || old.n_cols != cols || old.two != two) {
+        // another shape: the new one is allocated before the old one goes, so that a refusal leaves everything as it was
+        Ensemble::Rows r;
+        int rc;
+        if (!c->pin.aw) HIP_TRY(c, hipHostMalloc((void **)&c->pin.aw, (size_t)c->cap_steps + 1u, hipHostMallocDefault));
+        if ((rc = dev_alloc(c, &r.hit, cells)) || (rc = dev_alloc(c, &r.sum, cells)) || (rc = dev_alloc(c, &r.sumsq, cells)) || (rc = dev_alloc(c, &r.members, 1)) ||
+            (rc = dev_alloc(c, &r.p0, cells)) || (two && (rc = dev_alloc(c, &r.p1, cells))) || (rc = dev_alloc(c, &r.occ, (size_t)cols * 2u)) ||
+            (rc = dev_alloc(c, &r.aw, (size_t)c->cap_steps + 1u))) {
+            (void)hipGetLastError();
+            rows_free(c, &r);
+            return fail(c, ESIM_ENOMEM, "esim_ensemble_begin_series: no device memory for the accumulators and the row planes (ask for fewer rows)");
+        }
+        if (old.hit) HIP_TRY(c, hipStreamSynchronize(c->stream));    // (a fold on the stream may still be using the old ones)
+        r.vax = old.vax; old.vax = nullptr;                          // (4 B per citizen whatever the shape)
+        rows_free(c, &old);
+        old = r;
+    }
+    Ensemble::Rows &r = c->ens.rows;
+    r.what = what; r.first = first_step; r.n_rows = n_rows; r.stride = stride; r.min = min_cases; r.n_cols = cols; r.two = two;
+    HIP_TRY(c, hipMemsetAsync(r.hit, 0, sizeof(uint32_t) * cells, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.sum, 0, sizeof(unsigned long long) * cells, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.sumsq, 0, sizeof(unsigned long long) * cells, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
+    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_read_series(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: no population uploaded, or no esim_ensemble_begin_series in force since the upload (or, by group, since esim_set_groups)");
+    const Ensemble::Rows &r = c->ens.rows;
+    if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, "esim_ensemble_read_series: rows outside the accumulators");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
+    const size_t at = (size_t)first_row * r.n_cols, cells = (size_t)n * r.n_cols;
+    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hit && cells) HIP_TRY(c, hipMemcpy(hit, r.hit + at, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    if (sum && cells) HIP_TRY(c, hipMemcpy(sum, r.sum + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
+    if (sumsq && cells) HIP_TRY(c, hipMemcpy(sumsq, r.sumsq + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
     return ctrl_error(c, h);
 }
 

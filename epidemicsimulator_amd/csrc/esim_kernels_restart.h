@@ -1,5 +1,6 @@
 // esim_kernels_restart.h -- ensembles on one uploaded population: the initial state rebuilt on the device (esim_restart)
-// and the per-Output-Area accumulators over the members of an ensemble (esim_ensemble_fold), by census or by arrival step.
+// and the per-Output-Area accumulators over the members of an ensemble (esim_ensemble_fold), by census, by arrival step or
+// over the rows of a series.
 // No stepping kernel is here.
 #pragma once
 
@@ -64,4 +65,46 @@ __global__ __launch_bounds__(TPB) void k_ensemble_fold_arrival(const uint32_t *f
     hit[a] += 1u;
     sum[a] += x;
     sumsq[a] += (unsigned long long)x * x;
+}
+
+// The same over the rows of a series (esim_ensemble_begin_series): x[cell] is what the series engine has just left in plane 0,
+// cells = n_rows * n_cols, and every cell has accumulators of its own.  A pure stream: four cells per lane and trip, 16-byte
+// loads of x and hit, 16-byte loads and stores of sum and sumsq, two cells each (the arrays come from hipMalloc, so every one
+// starts on a 16-byte boundary); a grid capped by the caller strides over the rest, and the up to three cells behind the last
+// whole four are taken by the first lanes of workgroup 0.  A cell with x == 0 adds nothing to sum and sumsq, and nothing to hit
+// unless min_cases == 0: what would not change is neither read nor written, so a window in which the epidemic has hardly
+// arrived costs the 4 B per cell of x and little else.  With min_cases == 0 every cell counts as hit, zero or not.
+__global__ __launch_bounds__(TPB) void k_ensemble_fold_rows(const uint32_t *x, uint64_t cells, uint32_t min_cases,
+                                                            uint32_t *hit, unsigned long long *sum, unsigned long long *sumsq, uint32_t *members)
+{
+    if (blockIdx.x == 0u && threadIdx.x == 0u) *members += 1u;
+    const uint4 *x4 = reinterpret_cast<const uint4 *>(x);
+    uint4 *h4 = reinterpret_cast<uint4 *>(hit);
+    ulonglong2 *s2 = reinterpret_cast<ulonglong2 *>(sum), *q2 = reinterpret_cast<ulonglong2 *>(sumsq);
+    const uint64_t n4 = cells >> 2, stride = (uint64_t)gridDim.x * TPB;
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += stride) {
+        const uint4 v = x4[i];
+        const uint32_t hx = v.x >= min_cases, hy = v.y >= min_cases, hz = v.z >= min_cases, hw = v.w >= min_cases;
+        if (hx | hy | hz | hw) {
+            uint4 h = h4[i];
+            h.x += hx; h.y += hy; h.z += hz; h.w += hw;
+            h4[i] = h;
+        }
+        if (v.x | v.y) {
+            ulonglong2 s = s2[2u * i], q = q2[2u * i];
+            s.x += v.x; s.y += v.y; q.x += (unsigned long long)v.x * v.x; q.y += (unsigned long long)v.y * v.y;
+            s2[2u * i] = s; q2[2u * i] = q;
+        }
+        if (v.z | v.w) {
+            ulonglong2 s = s2[2u * i + 1u], q = q2[2u * i + 1u];
+            s.x += v.z; s.y += v.w; q.x += (unsigned long long)v.z * v.z; q.y += (unsigned long long)v.w * v.w;
+            s2[2u * i + 1u] = s; q2[2u * i + 1u] = q;
+        }
+    }
+    const uint64_t tail = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0u && threadIdx.x < (uint32_t)(cells & 3u)) {
+        const uint32_t v = x[tail];
+        if (v >= min_cases) hit[tail] += 1u;
+        if (v) { sum[tail] += v; sumsq[tail] += (unsigned long long)v * v; }
+    }
 }

@@ -54,6 +54,13 @@ def arrival_summary(members, hit, total, sumsq):
     return {"members": int(members), "hit": hit, "mean": mean, "var": var}
 
 
+def series_summary(members, hit, total, sumsq, first_step=1, stride=1):
+    """area_summary over [n_rows, n_cols] accumulators, and steps: the step each row describes."""
+    out = area_summary(members, hit, total, sumsq)
+    out["steps"] = int(first_step) + int(stride) * np.arange(np.asarray(hit).shape[0], dtype=np.int64)
+    return out
+
+
 def _json_number(x):
     x = float(x)
     return None if x != x else x          # NaN (an arrival mean nobody contributed to) is written as null
@@ -81,7 +88,8 @@ class EnsembleResult:
     def dump(self, directory):
         """ensemble_stats.json: per field the mean and the 5/25/50/75/95 % rows over the members; ensemble_areas.json: hit, mean
         and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index (an arrival
-        summary's mean and var are null where hit is 0)."""
+        summary's mean and var are null where hit is 0).  A series summary goes to ensemble_area_series.npz instead -- steps,
+        hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -90,13 +98,22 @@ class EnsembleResult:
         with open(os.path.join(directory, "ensemble_stats.json"), "w") as fh:
             json.dump(stats, fh)
         doc = None
-        if self.area is not None:
+        if self.area is not None and "steps" in self.area:     # a series summary: arrays by (row, column), too many for JSON
+            a = self.area
+            arrays = {k: a[k] for k in ("steps", "hit", "mean", "var")}
+            if self.area_codes is not None:
+                arrays["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_series.npz"), **arrays)
+        elif self.area is not None:
             a = self.area
             key = (lambda i: self.area_codes[i]) if self.area_codes is not None else (lambda i: str(i))
             doc = {"members": a["members"],
                    "areas": {key(i): {"hit": int(a["hit"][i]), "mean": _json_number(a["mean"][i]), "var": _json_number(a["var"][i])} for i in range(len(a["hit"]))}}
         with open(os.path.join(directory, "ensemble_areas.json"), "w") as fh:
             json.dump(doc, fh)
+
+
+_KINDS = ("census", "arrival", "series")
 
 
 class Ensemble:
@@ -111,6 +128,35 @@ class Ensemble:
         self.base = _lib.Params()
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
         self._own_seeds = True            # the seeds in force are the uploaded population's
+
+    @staticmethod
+    def _area_kind(who, area, stop_when_done=False):
+        """area of run() / forecast() checked, before anything runs: (kind, the area dict without its kind), or (None, None)."""
+        if area is None:
+            return None, None
+        area = dict(area)
+        kind = area.pop("kind", "census")
+        if kind not in _KINDS:
+            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', got %r" % (who, kind))
+        if kind == "series" and stop_when_done:
+            raise ValueError("Ensemble.%s: area kind 'series' cannot go with stop_when_done=True (a member that stopped early has no "
+                             "rows behind its last step, and the library refuses the fold)" % who)
+        return kind, area
+
+    def _begin(self, kind, area):
+        sim = self.simulator
+        if kind is not None:
+            getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series"}[kind])(**area)
+
+    def _summary(self, kind, area):
+        sim = self.simulator
+        if kind is None:
+            return None
+        if kind == "series":
+            r = sim.ensemble_read_series()
+            return series_summary(r["members"], r["hit"], r["sum"], r["sumsq"], area.get("first_step", 1), area.get("stride", 1))
+        r = sim.ensemble_read()
+        return (arrival_summary if kind == "arrival" else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
 
     @staticmethod
     def seeds(k, first=1):
@@ -128,20 +174,16 @@ class Ensemble:
         area: None, or the arguments of esim_ensemble_begin as a dict (where, status_mask, min_cases); where="group" counts by
         the groups given to Ensemble(...), and the summary then has one entry per group; or dict(kind="arrival", where=...,
         horizon=...) for the arrival step instead (esim_ensemble_begin_arrival; the summary's mean and var are then over the
-        members that reached the entry, NaN where none did).  Returns an EnsembleResult."""
+        members that reached the entry, NaN where none did); or dict(kind="series", where=..., what=..., first_step=...,
+        n_rows=..., stride=..., min_cases=...) for the rows of a series (Simulator.ensemble_begin_series; the summary is a
+        series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError).  Returns an EnsembleResult."""
+        kind, area = self._area_kind("run", area, stop_when_done)
         sim = self.simulator
         members = [dict(m) for m in members]
         for m in members:
             if "index_cases" in m:
                 m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
-        arrival = False
-        if area is not None:
-            area = dict(area)
-            kind = area.pop("kind", "census")
-            if kind not in ("census", "arrival"):
-                raise ValueError("Ensemble.run: area kind must be 'census' or 'arrival', got %r" % (kind,))
-            arrival = kind == "arrival"
-            (sim.ensemble_begin_arrival if arrival else sim.ensemble_begin)(**area)
+        self._begin(kind, area)
         rows, n_done = [], []
         for m in members:
             over = {k: v for k, v in m.items() if k != "index_cases"}
@@ -156,10 +198,7 @@ class Ensemble:
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
-        summary = None
-        if area is not None:
-            r = sim.ensemble_read()
-            summary = (arrival_summary if arrival else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
+        summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
         return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
 
@@ -170,6 +209,7 @@ class Ensemble:
         for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
         library refuses them).  area: as for run(), folded once per member.  Returns an EnsembleResult whose records are
         [members, n_steps], the shared history repeated in every row."""
+        kind, area = self._area_kind("forecast", area)
         sim = self.simulator
         history_steps, n_steps = int(history_steps), int(n_steps)
         if not 1 <= history_steps <= n_steps:
@@ -177,14 +217,7 @@ class Ensemble:
         members = [dict(m) for m in members]
         if any("index_cases" in m for m in members):
             raise ValueError("Ensemble.forecast: a branch cannot change the index cases of the shared history")
-        arrival = False
-        if area is not None:
-            area = dict(area)
-            kind = area.pop("kind", "census")
-            if kind not in ("census", "arrival"):
-                raise ValueError("Ensemble.forecast: area kind must be 'census' or 'arrival', got %r" % (kind,))
-            arrival = kind == "arrival"
-            (sim.ensemble_begin_arrival if arrival else sim.ensemble_begin)(**area)
+        self._begin(kind, area)
         sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
         self._own_seeds = True
         history = sim.run(history_steps)
@@ -198,10 +231,7 @@ class Ensemble:
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
-        summary = None
-        if area is not None:
-            r = sim.ensemble_read()
-            summary = (arrival_summary if arrival else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
+        summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
         return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
 

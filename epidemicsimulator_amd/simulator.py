@@ -296,6 +296,36 @@ class Simulator:
                                                tot.ctypes.data_as(C.POINTER(C.c_uint64)), sq.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
         return {"members": int(members.value), "hit": hit, "sum": tot, "sumsq": sq}
 
+    def ensemble_begin_series(self, where, what, first_step=1, n_rows=None, stride=1, min_cases=1):
+        """Accumulators over the rows of a series instead (esim_ensemble_begin_series): a member contributes, cell for cell,
+        the rows area_status_series(what, where), area_series("exposures") or group_series(what) would return for it with the
+        same first_step, n_rows and stride.  where: "home", "current" or "group"; what: "susceptible", "exposed", "infected",
+        "recovered", "vaccinated", or "incidence" / "exposures" (two names of the event rows: exposures of the `stride` steps
+        from the row's on -- by "home" and "group" in buildings and on public transport, by "current" in buildings).
+        n_rows=None: up to the last step of the run (params.max_steps).  The rows stay on the device; ensemble_fold adds
+        hit += (x >= min_cases), sum += x, sumsq += x * x per cell there."""
+        place = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)
+        code = {"susceptible": _lib.SUSCEPTIBLE, "exposed": _lib.EXPOSED, "infected": _lib.INFECTED, "recovered": _lib.RECOVERED,
+                "vaccinated": _lib.VACCINATED, "incidence": _lib.ENSEMBLE_SERIES_EVENTS, "exposures": _lib.ENSEMBLE_SERIES_EVENTS}.get(what, what)
+        if n_rows is None:
+            last = int(self.params.max_steps)
+            n_rows = (last - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= last else 0
+        _lib.check(self.lib.esim_ensemble_begin_series(self._ctx, int(place), int(code), int(first_step), int(n_rows), int(stride), int(min_cases)), self._ctx)
+        self._ens_rows = int(n_rows)
+        self._ens_n = self._n_groups if place == _lib.BY_GROUP else self.population.n_areas
+
+    def ensemble_read_series(self, first_row=0, n_rows=None):
+        """{"members": int, "hit": uint32 [n, n_cols], "sum": uint64 [n, n_cols], "sumsq": uint64 [n, n_cols]}: rows
+        [first_row, first_row + n) of the accumulators begun by ensemble_begin_series; n_rows=None: all from first_row on."""
+        total = getattr(self, "_ens_rows", 0)
+        n = max(0, total - int(first_row)) if n_rows is None else int(n_rows)
+        cols = getattr(self, "_ens_n", self.population.n_areas)
+        members = C.c_uint32(0)
+        hit, tot, sq = np.zeros((n, cols), np.uint32), np.zeros((n, cols), np.uint64), np.zeros((n, cols), np.uint64)
+        _lib.check(self.lib.esim_ensemble_read_series(self._ctx, int(first_row), n, C.byref(members), hit.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      tot.ctypes.data_as(C.POINTER(C.c_uint64)), sq.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
+        return {"members": int(members.value), "hit": hit, "sum": tot, "sumsq": sq}
+
     def download_state(self):
         n = self.population.n_citizens
         out = {"status": np.zeros(n, np.uint8), "timer": np.zeros(n, np.uint16),

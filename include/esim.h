@@ -291,6 +291,45 @@ int  esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t horizon);
 int  esim_ensemble_fold(esim_ctx *ctx);
 int  esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit /* [n_areas] */,
                         uint64_t *sum /* [n_areas] */, uint64_t *sumsq /* [n_areas] */);
+/* Space-time ensembles: the same accumulators over the rows of a series -- P(area a has at least k Infected after step s),
+ * the mean and variance of incidence per area and day, a fan chart per age band -- folded on the device, where the series
+ * engine leaves a member's rows.
+ * begin_series: fix what a member contributes and allocate.  x[row * n_cols + col] is, cell for cell, what the series call that
+ *        (where, what) names would return for the member with the same first_step, n_rows and stride:
+ *          where = ESIM_AREA_HOME or ESIM_AREA_CURRENT, what = ESIM_SUSCEPTIBLE .. ESIM_VACCINATED
+ *                                                     esim_area_status_series(where, what)
+ *          where = ESIM_AREA_HOME,    what = 5        esim_area_status_series(ESIM_AREA_HOME, ESIM_AREA_SERIES_INCIDENCE)
+ *          where = ESIM_AREA_CURRENT, what = 5        esim_area_series(ESIM_SERIES_EXPOSURES)
+ *          where = ESIM_BY_GROUP,     what = 0 .. 5   esim_group_series(what)
+ *        n_cols = n_areas, or n_groups by group.  Held on the device from here on: hit (u32), sum and sumsq (u64) per cell --
+ *        20 B per cell -- and the member counter, zeroed on the stream; the row plane the engine writes into, 4 B per cell, two
+ *        of them for status rows by ESIM_AREA_CURRENT; 8 B per column of occupancy and 1 B per step of the record log's
+ *        capacity (also pinned on the host); and, from the first fold under a vaccination programme on, the 4 B per citizen
+ *        of the vaccination replay.  A fold allocates nothing proportional to rows x columns.  A begin with the same n_rows,
+ *        n_cols and number of planes zeroes what is there; any other shape is allocated first and the earlier one freed then,
+ *        so ESIM_ENOMEM leaves the context and every earlier accumulator as they were.  The accumulators of the other two
+ *        kinds are left alone, and theirs leave these alone: one kind is in force at a time, a begin of any kind replaces it.
+ *        ESIM_EINVAL: a null context, an unknown `where` or `what`, stride 0, no rows.  ESIM_ESTATE: before a population is
+ *        uploaded; by group without labels; on a context whose communicator has more than one rank (the rule of
+ *        esim_restart).  ESIM_ERANGE: first_step == 0.  ESIM_ENOMEM: no device memory.
+ * fold:  esim_ensemble_fold with this kind in force runs the series engine for the state as it stands into the kept planes and
+ *        then one pass over the cells: members += 1; hit[cell] += (x >= min_cases); sum[cell] += x; sumsq[cell] += x * x.
+ *        Nothing proportional to rows x columns goes to the host.  Unlike the other two kinds it WAITS FOR THE STREAM ONCE, in
+ *        front of its own work: the at-work bit of every step and the step that started the vaccination programme are derived
+ *        on the host from the records (64 B per step run), as the series calls derive them.  ESIM_ERANGE, with nothing folded
+ *        and members as it was, when the last row's step lies beyond the steps the member has run (a member that stopped early
+ *        has no rows behind its last step); a sticky device-side error and the ESIM_ESTATE of a shard under a vaccination
+ *        programme are reported as the series calls report them.  Leaves the simulation state, the records, the snapshot and
+ *        the group labels as they are.
+ * read_series: rows [first_row, first_row + n) of the accumulators, hit[(r - first_row) * n_cols + col] and the same for sum and
+ *        sumsq; any pointer may be NULL.  ESIM_ERANGE for rows outside the accumulators; ESIM_ESTATE when no series kind is in
+ *        force -- and esim_ensemble_read is ESIM_ESTATE while one is.
+ * Lifetime as above: kept through esim_reset, esim_restart, esim_restart_seeded, esim_rollback and esim_snapshot, dropped by a
+ * new upload and by esim_destroy, invalidated by esim_set_groups when begun by group. */
+int  esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                                uint32_t min_cases);
+int  esim_ensemble_read_series(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *hit /* [n * n_cols] */,
+                               uint64_t *sum /* [n * n_cols] */, uint64_t *sumsq /* [n * n_cols] */);
 /* The same picture for the steps already run, derived after the fact from what the device holds (exposure log, citizen
  * words, the records' lockdown flags): a run that never asks pays nothing.  Row i describes step
  * s_i = first_step + i * stride (1-based, s_i <= steps run so far), out[i * n_areas + area]:
