@@ -163,7 +163,7 @@ struct ChunkPass {
     void mark(int kind) const { if (kd) kd_mark(c, kind); }
     // the Infected census of the next n steps; their decisions and how many of them form the chunk (parallel: one pass may draw it)
     void future(uint32_t n) const { mark(ESIM_CK_FUTURE); hipLaunchKernelGGL(k_future, dim3(1), dim3(FIN_TPB), 0, c->stream, c->d, n, limit_t); }
-    void decide(uint32_t n, int parallel, int sharded) const { mark(ESIM_CK_DECIDE); hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, c->d, n, limit_t, parallel, sharded); }
+    void decide(uint32_t n, int parallel, int vax_in_census) const { mark(ESIM_CK_DECIDE); hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, c->d, n, limit_t, parallel, vax_in_census); }
     // the plan of the chunk's vaccinations; unsharded, one more workgroup makes the census ahead (a sharded chunk's k_future has)
     void vax_plan(int sharded) const { mark(ESIM_CK_VAX); hipLaunchKernelGGL(k_chunk_vax<false>, dim3(FREE_MAX + (sharded ? 0u : 1u)), dim3(FIN_TPB), 0, c->stream, c->d, n_ahead(), limit_t, sharded); }
     // bus exposures of citizens the plan vaccinates later: lost finds them, vax_repair walks the plan again (one ESIM_CK_VAX_REPAIR)

@@ -9,7 +9,7 @@
 //
 // While no vaccination programme runs, everything a step needs from the past except who is still Susceptible is known
 // up to exposed_time steps ahead (who is Infected, where everybody stands, the intervention decisions).  Then a chunk
-// of <= 96 steps is drawn in ONE pass (esim_kernels_chunk.h: a citizen's exposure step is the earliest step at which
+// of <= 96 steps is drawn in ONE pass (esim_kernels_marks.h, esim_kernels_draw.h: a citizen's exposure step is the earliest step at which
 // any of its draws succeeds -- one atomicMin on its word), or, when it does not fit that form, as one k_pipe launch
 // per step with the books written once per chunk.
 //
@@ -23,7 +23,11 @@
 // thresholds ceil(q*2^32) from a host-built LUT, so every comparison is exact integer work.
 #include "esim_kernels_common.h"
 #include "esim_kernels_step.h"
-#include "esim_kernels_chunk.h"
+#include "esim_chunk_sets.h"
+#include "esim_kernels_plan.h"
+#include "esim_kernels_marks.h"
+#include "esim_kernels_draw.h"
+#include "esim_kernels_books.h"
 #include "esim_kernels_tiny.h"
 #include "esim_kernels_state.h"
 #include "esim_kernels_area.h"

@@ -93,6 +93,25 @@ __device__ __forceinline__ void append(uint32_t *list, uint32_t *len, uint32_t v
     list[atomicAdd(len, 1u)] = v;
 }
 
+// Steps a chunk that starts at step t0 may look ahead: up to step limit_t, max_ahead at most.
+__device__ __forceinline__ uint32_t steps_ahead(uint32_t t0, uint32_t limit_t, uint32_t max_ahead) { return t0 > limit_t ? 0u : (limit_t - t0 + 1u < max_ahead ? limit_t - t0 + 1u : max_ahead); }
+
+// Forget the marks of ring slot q (the step before): whoever runs the exposures of a step, or a one-pass chunk, does so for the
+// slot that nobody reads any more.  Thread tid of nth.
+__device__ __forceinline__ void clear_marks(const Dev &d, const Ctrl *ctrl, uint32_t q, uint32_t tid, uint32_t nth)
+{
+    const uint32_t ob = ctrl->n_touched_bld[q], orr = ctrl->n_touched_room[q], ort = ctrl->n_touched_route[q], orb = ctrl->n_touched_route_big[q];
+    for (uint32_t i = tid; i < ob; i += nth) d.cnt_bld[q][d.touched_bld[q][i]] = 0u;
+    for (uint32_t i = tid; i < orr; i += nth) d.cnt_room[q][d.touched_room[q][i]] = 0u;
+    for (uint32_t i = tid; i < ort; i += nth) d.route_flag[q][d.touched_route[q][i]] = 0u;
+    for (uint32_t i = tid; i < orb; i += nth) d.route_flag[q][d.touched_route_big[q][i]] = 0u;
+}
+
+// Sub-list r of the newly exposed (expose_min appends to it): its entries, and how many counter hot_base + r says it holds (HOT_NEWEXP:
+// the chunk in flight; HOT_PREV_NEWEXP: k_chunk_books' copy for k_chunk_scatter), read past the L1 for every caller (DESIGN.md 3.15 iv).
+__device__ __forceinline__ const uint32_t *newexp_list(const Dev &d, uint32_t r) { return d.newexp + (size_t)r * d.newexp_cap; }
+__device__ __forceinline__ uint32_t newexp_len(const Dev &d, uint32_t hot_base, uint32_t r) { return min(ld(&d.hot[(hot_base + r) * HOT_STRIDE]), d.newexp_cap); }
+
 // Diagnostics build (make prof): every wavefront of the chunk-pass kernels stores its timers in its own row of
 // d.prof_buf -- no atomics, so the measurement does not serialise the kernel it measures.
 #ifdef ESIM_WAVE_PROFILE

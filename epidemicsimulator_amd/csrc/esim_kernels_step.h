@@ -166,15 +166,7 @@ __device__ __forceinline__ void expose_phase(const Dev &d, Ctrl *ctrl, const Ste
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (vb * blockDim.x + threadIdx.x) >> 6, n_waves = (nvb * blockDim.x) >> 6;
     uint32_t n_exp = 0;
-    // (0) forget the marks of the previous step (other parity); nobody reads them any more
-    {
-        const uint32_t tid = vb * blockDim.x + threadIdx.x, nth = nvb * blockDim.x;
-        const uint32_t ob = ctrl->n_touched_bld[q], orr = ctrl->n_touched_room[q], ort = ctrl->n_touched_route[q], orb = ctrl->n_touched_route_big[q];
-        for (uint32_t i = tid; i < ob; i += nth) d.cnt_bld[q][d.touched_bld[q][i]] = 0u;
-        for (uint32_t i = tid; i < orr; i += nth) d.cnt_room[q][d.touched_room[q][i]] = 0u;
-        for (uint32_t i = tid; i < ort; i += nth) d.route_flag[q][d.touched_route[q][i]] = 0u;
-        for (uint32_t i = tid; i < orb; i += nth) d.route_flag[q][d.touched_route_big[q][i]] = 0u;
-    }
+    clear_marks(d, ctrl, q, vb * blockDim.x + threadIdx.x, nvb * blockDim.x);   // (0) the marks of the previous step: nobody reads them any more
     // (1) marked buildings and school rooms: groups of 8 lanes per item, 8 items per wavefront pass
     const uint32_t grp = lane >> 3, gl = lane & 7u;
     for (uint32_t base = wave * 8u; base < nb + nr; base += n_waves * 8u) {

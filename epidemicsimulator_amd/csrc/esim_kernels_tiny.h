@@ -11,6 +11,11 @@
 // A chunk it cannot take (more than TINY_E Infected, a vaccination plan, shards) it turns into a no-op: the steps do not advance,
 // the host sees that in its read-back and enqueues the wide form (esim_host_run.h run_steps).
 #pragma once
+#include "esim_kernels_common.h"
+#include "esim_chunk_sets.h"
+#include "esim_kernels_plan.h"
+#include "esim_kernels_draw.h"
+#include "esim_kernels_books.h"
 
 #define TINY_E 64u                 // Infected (log entries) of a chunk the one-workgroup form takes
 #define TINY_WAVES (FIN_TPB / 64u)
@@ -46,11 +51,20 @@ __device__ __forceinline__ void tiny_counts(const TinyShared &ts, uint32_t E, ui
     }
 }
 
-// One member list of an item, pairs [p_lo, p_hi) of it.
-__device__ __forceinline__ void tiny_list(const Dev &d, Ctrl *ctrl, const ChunkShared &sm, WaveScratch &ws, const uint32_t *idx, uint32_t lo,
-                                          uint32_t p_lo, uint32_t p_hi, uint32_t lane, uint32_t kind, uint32_t S, uint32_t t0 WORK_ARG)
+// One member list of item `key` (n_mem members from lo; pre_m / pre_w: the first 64 and their words): a short one is drawn here,
+// a long one becomes units of TINY_INLINE pairs for everybody (ts.task); what the queue cannot hold this wavefront draws itself.
+__device__ __forceinline__ void tiny_list_or_units(const Dev &d, Ctrl *ctrl, const ChunkShared &sm, WaveScratch &ws, TinyShared &ts, const uint32_t *idx,
+                                                   uint32_t lo, uint32_t n_mem, uint32_t key, uint32_t lane, uint32_t kind, uint32_t S, uint32_t t0 WORK_ARG,
+                                                   uint32_t pre_m, uint32_t pre_w)
 {
-    if (p_lo < p_hi) member_pairs(d, ctrl, sm, ws, idx, lo, p_lo, p_hi, lane, kind, S, t0 WORK_PASS);
+    const uint32_t pairs = n_mem * S;
+    if (pairs == 0u) return;
+    if (pairs <= TINY_INLINE) { member_pairs(d, ctrl, sm, ws, idx, lo, 0u, pairs, lane, kind, S, t0 WORK_PASS, true, pre_m, pre_w); return; }
+    const uint32_t nu = (pairs + TINY_INLINE - 1u) / TINY_INLINE;
+    uint32_t at = 0u; if (lane == 0) at = atomicAdd(&ts.n_tasks, nu); at = FX(at, 0);
+    const uint32_t fit = at >= TINY_TASKS ? 0u : min(nu, TINY_TASKS - at);
+    for (uint32_t q = lane; q < fit; q += 64u) { ts.task[at + q][0] = key; ts.task[at + q][1] = kind; ts.task[at + q][2] = q * TINY_INLINE; }
+    if (fit < nu) member_pairs(d, ctrl, sm, ws, idx, lo, fit * TINY_INLINE, pairs, lane, kind, S, t0 WORK_PASS);
 }
 
 __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int do_next, uint32_t max_ahead, uint32_t limit_t)
@@ -86,26 +100,13 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
     }
     if (run) {
         WORK_TALLY;
-        {
-            // the marks of step t0 - 1 (made by a sequential or pipelined step) would have been cleared by the exposure pass of
-            // step t0; this chunk has none, so clear them here (as k_chunk_marks does)
-            const uint32_t q = (t0 + MARK_SLOTS - 1u) & (MARK_SLOTS - 1u);
-            const uint32_t ob = ctrl->n_touched_bld[q], orr = ctrl->n_touched_room[q], ort = ctrl->n_touched_route[q], orb = ctrl->n_touched_route_big[q];
-            for (uint32_t i = tid; i < ob; i += FIN_TPB) d.cnt_bld[q][d.touched_bld[q][i]] = 0u;
-            for (uint32_t i = tid; i < orr; i += FIN_TPB) d.cnt_room[q][d.touched_room[q][i]] = 0u;
-            for (uint32_t i = tid; i < ort; i += FIN_TPB) d.route_flag[q][d.touched_route[q][i]] = 0u;
-            for (uint32_t i = tid; i < orb; i += FIN_TPB) d.route_flag[q][d.touched_route_big[q][i]] = 0u;
-        }
-        for (uint32_t i = tid; i < n; i += FIN_TPB) sm.dec[i] = d.dec[i];
-        for (uint32_t i = tid; i < 512u; i += FIN_TPB) sm.thr[i] = d.thr[i];
+        // (as k_chunk_marks does: the marks of step t0 - 1, which no exposure pass of step t0 will clear)
+        clear_marks(d, ctrl, (t0 + MARK_SLOTS - 1u) & (MARK_SLOTS - 1u), tid, FIN_TPB);
+        stage_chunk(d, sm, n, FIN_TPB);
         if (tid == 0) { ts.n_uniq = 0u; ts.n_tasks = 0u; ts.n_big = 0u; }
         __syncthreads();
         TINY_PROF(d, 3);
-        const Decision q0 = lane < n ? sm.dec[lane] : Decision{ 0u, 0u, 0u, 0u };
-        const Decision q1 = 64u + lane < n ? sm.dec[64u + lane] : Decision{ 0u, 0u, 0u, 0u };
-        M96 AW, BUS;
-        schedule_masks(lane, n, q0, q1, AW, BUS);
-        const M96 EV = { __ballot(lane < n && q0.mask == ESIM_MASK_EVERYWHERE), (uint32_t)__ballot(64u + lane < n && q1.mask == ESIM_MASK_EVERYWHERE) };
+        const auto [AW, BUS, EV] = chunk_masks(sm.dec, lane, n);
         // (1) the chunk's Infected, one thread each: the stretch of the chunk in which each is Infected, where it stands in it, its keys
         if (tid < TINY_E) {
             uint32_t c = 0u, w = 0u, iv = 0u, key[4] = { TINY_NONE, TINY_NONE, TINY_NONE, TINY_NONE };
@@ -113,27 +114,16 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
                 c = d.log[i0 + tid];
                 if (c < d.n) {
                     w = d.cit[c];
-                    const int a_abs = (int)CW_TE(w) - (int)TE_BIAS + (int)d.exposed_time + 1;
-                    const int b_rel = a_abs + (int)d.infected_time - (int)t0;
-                    const uint32_t iv_a = a_abs > (int)t0 ? (uint32_t)(a_abs - (int)t0) : 0u;
-                    const uint32_t iv_b = b_rel < 0 ? 0u : min(min((uint32_t)b_rel, n - 1u), CW_VAX_REL(w));
-                    const bool act = !(CW_TE(w) >= TE_RECOVERED || b_rel < 0 || iv_a > iv_b);
-                    if (act) {
-                        const M96 I = m96_range(iv_a, iv_b);
-                        const M96 onbus = (w & FL_USES_PT) ? m96_and(I, BUS) : M96{ 0ull, 0u };
-                        const M96 rest = m96_andn(I, onbus);
-                        const M96 atw = (w & FL_HAS_WORK) ? m96_and(rest, AW) : M96{ 0ull, 0u };
-                        const M96 ath = m96_andn(rest, atw);
-                        const bool any_home = m96_any(ath), any_work = m96_any(atw), any_bus = m96_any(onbus);
-                        if (any_home || any_work || any_bus) {
-                            WORK_ADD(WK_ENTRIES, 1);
-                            const uint4 k4 = d.where4[c];
-                            if (any_home) key[0] = k4.x;
-                            if (any_work) key[1] = k4.y;
-                            if (any_work && (w & FL_WORK_SCHOOL) && k4.z != 0xFFFFFFFFu) key[2] = d.n_bld + k4.z;
-                            if (any_bus) key[3] = d.n_bld + d.n_room + k4.w;
-                            iv = IV_VALID | iv_a | (iv_b << 7) | ((w & FL_USES_PT) ? IV_PT : 0u) | ((w & FL_HAS_WORK) ? IV_HW : 0u);
-                        }
+                    const Stretch st = infected_stretch(d, w, t0, n, AW, BUS);   // (no stretch in the chunk: its sets are empty)
+                    const bool any_home = m96_any(st.home), any_work = m96_any(st.work), any_bus = m96_any(st.bus);
+                    if (any_home || any_work || any_bus) {
+                        WORK_ADD(WK_ENTRIES, 1);
+                        const uint4 k4 = d.where4[c];
+                        if (any_home) key[0] = k4.x;
+                        if (any_work) key[1] = k4.y;
+                        if (any_work && (w & FL_WORK_SCHOOL) && k4.z != 0xFFFFFFFFu) key[2] = d.n_bld + k4.z;
+                        if (any_bus) key[3] = d.n_bld + d.n_room + k4.w;
+                        iv = stretch_record(st, w);
                     }
                 }
             }
@@ -192,47 +182,20 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
                 if (lane < n_wrk) ww = d.cit[wm];
                 const uint32_t S = item_steps_regs(c0, c1, lane, ws, t0, AW, EV);
                 __builtin_amdgcn_wave_barrier();
-                const uint32_t pr = n_res * S, pw = n_wrk * S;
-                if (pr && pr <= TINY_INLINE) member_pairs(d, ctrl, sm, ws, d.res_idx, b.res_lo, 0u, pr, lane, 0u, S, t0 WORK_PASS, true, rm, rw);
-                else if (!pr) { }
-                else {
-                    // units of TINY_INLINE pairs for everybody; what the queue cannot hold this wavefront draws itself
-                    const uint32_t nu = (pr + TINY_INLINE - 1u) / TINY_INLINE; uint32_t at = 0u; if (lane == 0) at = atomicAdd(&ts.n_tasks, nu); at = FX(at, 0);
-                    const uint32_t fit = at >= TINY_TASKS ? 0u : min(nu, TINY_TASKS - at);
-                    for (uint32_t q = lane; q < fit; q += 64u) { ts.task[at + q][0] = key; ts.task[at + q][1] = 0u; ts.task[at + q][2] = q * TINY_INLINE; }
-                    if (fit < nu) tiny_list(d, ctrl, sm, ws, d.res_idx, b.res_lo, fit * TINY_INLINE, pr, lane, 0u, S, t0 WORK_PASS);
-                }
-                if (pw && pw <= TINY_INLINE) member_pairs(d, ctrl, sm, ws, d.wrk_idx, b.wrk_lo, 0u, pw, lane, 1u, S, t0 WORK_PASS, true, wm, ww);
-                else if (!pw) { }
-                else {
-                    // units of TINY_INLINE pairs for everybody; what the queue cannot hold this wavefront draws itself
-                    const uint32_t nu = (pw + TINY_INLINE - 1u) / TINY_INLINE; uint32_t at = 0u; if (lane == 0) at = atomicAdd(&ts.n_tasks, nu); at = FX(at, 0);
-                    const uint32_t fit = at >= TINY_TASKS ? 0u : min(nu, TINY_TASKS - at);
-                    for (uint32_t q = lane; q < fit; q += 64u) { ts.task[at + q][0] = key; ts.task[at + q][1] = 1u; ts.task[at + q][2] = q * TINY_INLINE; }
-                    if (fit < nu) tiny_list(d, ctrl, sm, ws, d.wrk_idx, b.wrk_lo, fit * TINY_INLINE, pw, lane, 1u, S, t0 WORK_PASS);
-                }
+                tiny_list_or_units(d, ctrl, sm, ws, ts, d.res_idx, b.res_lo, n_res, key, lane, 0u, S, t0 WORK_PASS, rm, rw);
+                tiny_list_or_units(d, ctrl, sm, ws, ts, d.wrk_idx, b.wrk_lo, n_wrk, key, lane, 1u, S, t0 WORK_PASS, wm, ww);
             } else {
                 const uint32_t r = key - d.n_bld;
                 const uint32_t a_lo = d.room_off[r], a_hi = d.room_off[r + 1u], sch = d.room_bld[r];
                 if (a_lo > a_hi || a_hi > d.n_room_idx) { if (lane == 0) RAISE(ctrl, ESIM_ERANGE, ERR_AT_ITEM_CHECK); continue; }
                 uint32_t s0, s1;
                 tiny_counts(ts, E, sch, lane, AW, BUS, s0, s1);                 // infected in the whole school, per step
-                ws.sch[lane] = s0;
-                if (lane < FREE_MAX - 64u) ws.sch[64u + lane] = s1;
+                put_school(ws, lane, s0, s1);
                 uint32_t mm = 0u, mw = 0u;
                 if (lane < a_hi - a_lo) { mm = d.room_idx[a_lo + lane]; mw = d.cit[mm]; }
                 const uint32_t S = item_steps_regs(c0, c1, lane, ws, t0, AW, EV);
                 __builtin_amdgcn_wave_barrier();
-                const uint32_t pm = (a_hi - a_lo) * S;
-                if (pm && pm <= TINY_INLINE) member_pairs(d, ctrl, sm, ws, d.room_idx, a_lo, 0u, pm, lane, 2u, S, t0 WORK_PASS, true, mm, mw);
-                else if (!pm) { }
-                else {
-                    // units of TINY_INLINE pairs for everybody; what the queue cannot hold this wavefront draws itself
-                    const uint32_t nu = (pm + TINY_INLINE - 1u) / TINY_INLINE; uint32_t at = 0u; if (lane == 0) at = atomicAdd(&ts.n_tasks, nu); at = FX(at, 0);
-                    const uint32_t fit = at >= TINY_TASKS ? 0u : min(nu, TINY_TASKS - at);
-                    for (uint32_t q = lane; q < fit; q += 64u) { ts.task[at + q][0] = key; ts.task[at + q][1] = 2u; ts.task[at + q][2] = q * TINY_INLINE; }
-                    if (fit < nu) tiny_list(d, ctrl, sm, ws, d.room_idx, a_lo, fit * TINY_INLINE, pm, lane, 2u, S, t0 WORK_PASS);
-                }
+                tiny_list_or_units(d, ctrl, sm, ws, ts, d.room_idx, a_lo, a_hi - a_lo, key, lane, 2u, S, t0 WORK_PASS, mm, mw);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -249,8 +212,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
                 const uint32_t r = key - d.n_bld;
                 uint32_t s0, s1;
                 tiny_counts(ts, E, d.room_bld[r], lane, AW, BUS, s0, s1);
-                ws.sch[lane] = s0;
-                if (lane < FREE_MAX - 64u) ws.sch[64u + lane] = s1;
+                put_school(ws, lane, s0, s1);
                 lo = d.room_off[r]; n_mem = d.room_off[r + 1u] - lo; idx = d.room_idx;
             } else {
                 const BldRec b = d.bld8[key];
@@ -260,7 +222,7 @@ __global__ __launch_bounds__(FIN_TPB) void k_chunk_tiny(Dev d, int do_first, int
             __builtin_amdgcn_wave_barrier();
             const uint32_t P = n_mem * S;
             WORK_ADD(WK_UNITS, lane == 0 ? 1 : 0);
-            tiny_list(d, ctrl, sm, ws, idx, lo, p_lo, min(P, p_lo + TINY_INLINE), lane, kind, S, t0 WORK_PASS);
+            if (p_lo < P) member_pairs(d, ctrl, sm, ws, idx, lo, p_lo, min(P, p_lo + TINY_INLINE), lane, kind, S, t0 WORK_PASS);
             __builtin_amdgcn_wave_barrier();
         }
         __syncthreads();                                                      // (the wavefronts' scratch becomes the routes' LDS)
