@@ -115,6 +115,13 @@ struct Snapshot {
 // old values, the later ones under those in force (run_shape and the vaccination replay).  step == 0: no seam.
 struct Seam { uint32_t step = 0, rate = 0; uint64_t seed = 0; };
 
+// The same for the exposure draws, which esim_exposure_settings and its kin replay after the fact: a rollback under another seed,
+// exposure_chance or mask_effectiveness leaves the entries of the log up to and including `step` drawn under the snapshot's three
+// values, kept here, and the later ones under those in force.  A record of its own beside Seam: nothing that hangs on Seam (the
+// refusals of esim_snapshot and of the checkpoint calls) reads it.  step == 0: none.  twice: the snapshot itself lay on a
+// branch with such a seam and the rollback changed the values again -- three parameter sets, which the replay does not follow.
+struct DrawSeam { uint32_t step = 0; bool twice = false; uint64_t seed = 0; double chance = 0.0, mask_effectiveness = 0.0; };
+
 // What picks the form and the grids of the kernels: esim_set_* and the tuning knobs of the environment (read at upload).
 struct Tuning {
     uint32_t grid_citizens = 1, grid_infected = 1, grid_expose = 1;
@@ -167,6 +174,8 @@ struct esim_ctx_impl {
     Groups grp;
     Snapshot snap;
     Seam seam;
+    DrawSeam draw_seam;               // of the history the context stands on
+    DrawSeam snap_draw_seam;          // of the history under the snapshot held (esim_snapshot copies it, esim_rollback starts from it)
     Tuning tune;
 };
 

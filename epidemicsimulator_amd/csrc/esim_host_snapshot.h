@@ -93,6 +93,7 @@ extern "C" int esim_snapshot(esim_ctx *ctx)
     s.last_chunk_pairs = c->last_chunk_pairs; s.quiet = c->quiet; s.repair_armed = c->repair_armed; s.elig_seen = c->elig_seen || h.have_elig != 0u;
     s.vax_chunk_steps = c->vax_chunk_steps; s.vax_chunk_cuts = c->vax_chunk_cuts; s.vax_chunk_repairs = c->vax_chunk_repairs;
     s.step = host_t - 1u;
+    c->snap_draw_seam = c->draw_seam;
     return ESIM_OK;
 }
 
@@ -146,6 +147,12 @@ extern "C" int esim_rollback(esim_ctx *ctx, const esim_params *p)
     c->last_chunk_pairs = s.last_chunk_pairs; c->quiet = s.quiet; c->repair_armed = s.repair_armed; c->elig_seen = s.elig_seen;
     c->vax_chunk_steps = s.vax_chunk_steps; c->vax_chunk_cuts = s.vax_chunk_cuts; c->vax_chunk_repairs = s.vax_chunk_repairs;
     if (q.seed != s.P.seed || q.vaccination_rate != s.P.vaccination_rate) { c->seam.step = s.step; c->seam.seed = s.P.seed; c->seam.rate = s.P.vaccination_rate; }
+    // the draw seam (rewind_host cleared it): the one the snapshot's own history has, if any, and one at the snapshot's step when
+    // the branch draws its exposures under other values than the snapshot's
+    const bool redrawn = q.seed != s.P.seed || q.exposure_chance != s.P.exposure_chance || q.mask_effectiveness != s.P.mask_effectiveness;
+    c->draw_seam = c->snap_draw_seam;
+    if (redrawn && c->draw_seam.step) c->draw_seam.twice = true;
+    else if (redrawn) { c->draw_seam.step = s.step; c->draw_seam.seed = s.P.seed; c->draw_seam.chance = s.P.exposure_chance; c->draw_seam.mask_effectiveness = s.P.mask_effectiveness; }
     return ESIM_OK;
 }
 
@@ -169,5 +176,6 @@ extern "C" int esim_snapshot_drop(esim_ctx *ctx)
         for (void *q : { (void *)s.words, (void *)s.hist, (void *)s.log_off, (void *)s.exp_step, (void *)s.records, (void *)s.log }) dev_free(c, q);
     }
     s = Snapshot();
+    c->snap_draw_seam = DrawSeam();
     return ESIM_OK;
 }

@@ -425,6 +425,7 @@ void rewind_host(esim_ctx_impl *c)
     c->pin.track = false; c->pin.ctrl_fresh = false;
     c->rest_t = 0;
     c->seam = Seam();                                              // (the history that starts here is drawn under one parameter set)
+    c->draw_seam = DrawSeam();
     c->tm.clear();
 }
 

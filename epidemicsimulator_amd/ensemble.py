@@ -67,8 +67,9 @@ def _json_number(x):
 
 
 class EnsembleResult:
-    def __init__(self, records, n_done, members, area=None, area_codes=None):
+    def __init__(self, records, n_done, members, area=None, area_codes=None, settings=None):
         self.records = records            # structured [members, n_steps]
+        self.settings = settings          # uint32 [members, n_rows, 4]: every member's setting_series(where="setting"), or None
         self.n_done = np.asarray(n_done, np.uint32)
         self.members = list(members)      # the overrides of every member
         self.area = area                  # area_summary(...) or None
@@ -89,7 +90,8 @@ class EnsembleResult:
         """ensemble_stats.json: per field the mean and the 5/25/50/75/95 % rows over the members; ensemble_areas.json: hit, mean
         and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index (an arrival
         summary's mean and var are null where hit is 0).  A series summary goes to ensemble_area_series.npz instead -- steps,
-        hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary."""
+        hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary.  The members' exposures by setting, where they
+        were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -111,6 +113,8 @@ class EnsembleResult:
                    "areas": {key(i): {"hit": int(a["hit"][i]), "mean": _json_number(a["mean"][i]), "var": _json_number(a["var"][i])} for i in range(len(a["hit"]))}}
         with open(os.path.join(directory, "ensemble_areas.json"), "w") as fh:
             json.dump(doc, fh)
+        if self.settings is not None:
+            np.savez(os.path.join(directory, "ensemble_settings.npz"), settings=self.settings, names=np.asarray(_lib.SETTING_NAMES))
 
 
 _KINDS = ("census", "arrival", "series")
@@ -159,6 +163,27 @@ class Ensemble:
         return (arrival_summary if kind == "arrival" else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
 
     @staticmethod
+    def _settings_rows(who, settings, n_steps, stop_when_done=False):
+        """settings of run() / forecast() checked, before anything runs: the arguments of Simulator.setting_series, or None."""
+        if settings is None:
+            return None
+        unknown = set(settings) - {"first_step", "n_rows", "stride"}
+        if unknown:
+            raise ValueError("Ensemble.%s: settings takes first_step, n_rows and stride, got %s" % (who, sorted(unknown)))
+        if stop_when_done:
+            raise ValueError("Ensemble.%s: settings cannot go with stop_when_done=True (a member that stopped early has no rows "
+                             "behind its last step)" % who)
+        first, stride = int(settings.get("first_step", 1)), int(settings.get("stride", 1))
+        n_rows = settings.get("n_rows")
+        if n_rows is None:
+            n_rows = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
+        return dict(first_step=first, n_rows=int(n_rows), stride=stride)
+
+    @staticmethod
+    def _settings_stack(rows, spec):
+        return None if spec is None else (np.stack(rows) if rows else np.zeros((0, spec["n_rows"], _lib.N_SETTINGS), np.uint32))
+
+    @staticmethod
     def seeds(k, first=1):
         return [{"seed": int(first) + i} for i in range(int(k))]
 
@@ -168,7 +193,7 @@ class Ensemble:
         pop = self.simulator.population
         return [{"seed": int(first) + i, "index_cases": pop.draw_index_cases(n, int(first) + i).tolist()} for i in range(int(k))]
 
-    def run(self, members, n_steps, stop_when_done=False, area=None):
+    def run(self, members, n_steps, stop_when_done=False, area=None, settings=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may
         carry "index_cases": the citizens that start Infected in that member (one without starts from the population's own).
         area: None, or the arguments of esim_ensemble_begin as a dict (where, status_mask, min_cases); where="group" counts by
@@ -176,15 +201,19 @@ class Ensemble:
         horizon=...) for the arrival step instead (esim_ensemble_begin_arrival; the summary's mean and var are then over the
         members that reached the entry, NaN where none did); or dict(kind="series", where=..., what=..., first_step=...,
         n_rows=..., stride=..., min_cases=...) for the rows of a series (Simulator.ensemble_begin_series; the summary is a
-        series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError).  Returns an EnsembleResult."""
+        series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError).
+        settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
+        (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
+        with stop_when_done=True either.  Returns an EnsembleResult."""
         kind, area = self._area_kind("run", area, stop_when_done)
+        spec = self._settings_rows("run", settings, n_steps, stop_when_done)
         sim = self.simulator
         members = [dict(m) for m in members]
         for m in members:
             if "index_cases" in m:
                 m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
         self._begin(kind, area)
-        rows, n_done = [], []
+        rows, n_done, by_setting = [], [], []
         for m in members:
             over = {k: v for k, v in m.items() if k != "index_cases"}
             seeds = m.get("index_cases")
@@ -195,21 +224,24 @@ class Ensemble:
             rec = sim.run(n_steps, stop_when_done=stop_when_done)
             if area is not None:
                 sim.ensemble_fold()
+            if spec is not None:
+                by_setting.append(sim.setting_series("setting", **spec))
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec))
 
-    def forecast(self, history_steps, members, n_steps, area=None):
+    def forecast(self, history_steps, members, n_steps, area=None, settings=None):
         """Given the epidemic as it stands after `history_steps` steps under the base parameters, what happens next: the base
         run is made once and kept on the device (Simulator.snapshot), and every member is a branch from it -- a rollback under
         the base parameters changed by the member's overrides, then the remaining n_steps - history_steps steps.  members as
         for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
-        library refuses them).  area: as for run(), folded once per member.  Returns an EnsembleResult whose records are
+        library refuses them).  area and settings: as for run(), folded / gathered once per member.  Returns an EnsembleResult whose records are
         [members, n_steps], the shared history repeated in every row."""
         kind, area = self._area_kind("forecast", area)
+        spec = self._settings_rows("forecast", settings, n_steps)
         sim = self.simulator
         history_steps, n_steps = int(history_steps), int(n_steps)
         if not 1 <= history_steps <= n_steps:
@@ -222,18 +254,20 @@ class Ensemble:
         self._own_seeds = True
         history = sim.run(history_steps)
         sim.snapshot()
-        rows, n_done = [], []
+        rows, n_done, by_setting = [], [], []
         for m in members:
             sim.rollback(**m)
             rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
             if area is not None:
                 sim.ensemble_fold()
+            if spec is not None:
+                by_setting.append(sim.setting_series("setting", **spec))
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes)
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec))
 
     def close(self):
         self.simulator.close()

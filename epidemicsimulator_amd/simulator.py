@@ -525,6 +525,50 @@ class Simulator:
                 "vaccinated": _lib.VACCINATED, "exposures": _lib.GROUP_SERIES_EXPOSURES}.get(what, what)
         return self._series(self.lib.esim_group_series, (code,), max(1, self._n_groups), first_step, n_rows, stride)
 
+    # -- exposures by setting (esim_exposure_settings, esim_setting_series, esim_building_exposures) -------
+    def exposure_settings(self):
+        """(setting uint8 [n_citizens], building uint32 [n_citizens]): where every citizen was exposed, derived on the device
+        from the exposure log by replaying the household draw (esim_exposure_settings).  setting: _lib.SETTING_HOUSEHOLD,
+        SETTING_WORKPLACE, SETTING_SCHOOL, SETTING_TRANSPORT, or SETTING_NONE for a citizen never exposed and for the index
+        cases; building: the building credited, _lib.NO_ROOM for public transport and for SETTING_NONE.  A tie between the
+        household and the work side is credited to the household."""
+        n = self.population.n_citizens
+        setting, building = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        _lib.check(self.lib.esim_exposure_settings(self._ctx, setting.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   building.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return setting, building
+
+    @staticmethod
+    def _setting_mask(settings):
+        if settings is None:
+            return (1 << _lib.N_SETTINGS) - 1
+        if isinstance(settings, (str, int, np.integer)):
+            settings = (settings,)
+        mask = 0
+        for s in settings:
+            code = _lib.SETTING_NAMES.index(s) if isinstance(s, str) else int(s)
+            if not 0 <= code < _lib.N_SETTINGS:
+                raise ValueError("setting_series: unknown setting %r" % (s,))
+            mask |= 1 << code
+        return mask
+
+    def setting_series(self, where="setting", settings=None, first_step=1, n_rows=None, stride=1):
+        """uint32 [n_rows, n_cols] over the steps already run (esim_setting_series): row i holds the exposures, in buildings
+        and on public transport, of the `stride` steps from first_step + i * stride on, restricted to `settings` (names out
+        of "household", "workplace", "school", "transport", or their codes; None: all four).  where: "setting" (four columns),
+        "home" (by the Output Area of the household) or "group".  n_rows=None: up to the last step run."""
+        place = {"setting": _lib.BY_SETTING, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        n_cols = _lib.N_SETTINGS if place == _lib.BY_SETTING else max(1, self._n_groups) if place == _lib.BY_GROUP else self.population.n_areas
+        return self._series(self.lib.esim_setting_series, (place, self._setting_mask(settings)), n_cols, first_step, n_rows, stride)
+
+    def building_exposures(self, first_step=1, last_step=None):
+        """uint32 [n_buildings]: the exposures of steps first_step .. last_step (None: the last step run) per building
+        credited -- the hot-spot map (esim_building_exposures).  Public transport is not counted."""
+        out = np.zeros(self.population.n_buildings, np.uint32)
+        last = self._steps if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_building_exposures(self._ctx, int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

@@ -405,6 +405,56 @@ int  esim_set_groups(esim_ctx *ctx, const uint16_t *group /* [n_citizens] */, ui
 int  esim_group_census(esim_ctx *ctx, uint32_t *counts /* [n_groups * 5] */);
 int  esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride,
                        uint32_t *out /* [n_rows * n_groups] */);
+/* Where infections happen: every exposure by SETTING -- household, work place, school, public transport -- and by the building
+ * credited (the reference's ID::Building / ID::PublicTransport tally, statistics.rs:105-106,181-195), derived after the fact
+ * from what the device holds: a run that never asks pays nothing, and no step kernel knows of it.  Every draw is a pure function
+ * of (seed, global citizen, step, slot), and a building exposure of citizen c in step ts can only have come through the list of
+ * its household or through its work-side list, so one replay of the household draw decides it.  The rule, per entry of the
+ * exposure log (the initially infected citizens are in the log and get ESIM_SETTING_NONE):
+ *   1. exposed on public transport -> ESIM_SETTING_TRANSPORT, no building;
+ *   2. n_home = the residents of the household that are Infected in step ts (their exposure steps taken from the log; still
+ *      Infected in the step at whose end they were vaccinated, which is walked again as for the series) and stand in it: not on
+ *      a bus and not at work in that step, both global bits per step derived from the records' lockdown flags;
+ *   3. c takes the household draw iff n_home > 0 and it stands in the household's area (always, except a commuter to another
+ *      area while at work); the draw succeeds iff its Philox word of slot 0 lies below thresholds[row][n_home & 255], row as
+ *      the step drew it (esim_threshold_lut; 256 Infected give threshold 0, the `as u8` of citizen.rs:239);
+ *   4. success -> ESIM_SETTING_HOUSEHOLD, the household's building;
+ *   5. otherwise the work side: ESIM_SETTING_SCHOOL for a school member, else ESIM_SETTING_WORKPLACE, the work building --
+ *      legal only for a citizen with a work place that is in its home area or at work in that step.  An entry for which
+ *      neither side is possible is UNEXPLAINED: they are counted on the device, carry ESIM_SETTING_NONE, and the call returns
+ *      ESIM_ESIM with their number in esim_last_error after delivering everything else.  On a correct run there is none: the
+ *      calls double as an audit of the log.
+ * The tie is a stated contract: when the household draw and a work-side draw both succeed in one step, the HOUSEHOLD is
+ * credited.  (The reference credits whichever building its hash map visits first: no rule.  The work side is never replayed.)
+ * After an esim_rollback under another seed, exposure_chance or mask_effectiveness the entries up to the snapshot's step are
+ * replayed under the snapshot's values and the later ones under those in force; a snapshot taken on such a branch and rolled
+ * back to under yet other values is ESIM_ESTATE here (a history mixed twice is not built).
+ * esim_exposure_settings: setting[c] and building[c] per citizen; ESIM_SETTING_NONE / ESIM_NO_ROOM for a citizen never
+ *        exposed and for the initially infected, ESIM_NO_ROOM for public transport.  Either pointer may be NULL; with both
+ *        NULL the audit still runs and its result is returned.
+ * esim_setting_series: event rows addressed and clipped exactly as the incidence rows of esim_area_status_series -- row i holds
+ *        the exposures of steps [first_step + i * stride, + stride), buildings and public transport, the initially infected
+ *        not counted -- restricted to the settings whose bit (1 << ESIM_SETTING_*) is in setting_mask:
+ *          where = ESIM_BY_SETTING   4 columns, out[i * 4 + setting]
+ *          where = ESIM_AREA_HOME    n_areas columns, by the Output Area of the household
+ *          where = ESIM_BY_GROUP     n_groups columns (ESIM_ESTATE without labels)
+ *        ESIM_AREA_CURRENT is ESIM_EINVAL (a bus has no area), and so are an empty mask and a bit beyond ESIM_SETTING_TRANSPORT.
+ * esim_building_exposures: counts[b] = the exposures of steps [first_step, last_step] credited to building b, the hot-spot map;
+ *        public transport is not counted.  ESIM_ERANGE: first_step == 0, last_step < first_step or beyond the steps run.
+ * All three: ESIM_EINVAL for a null context or output and unknown arguments; ESIM_ESTATE before an upload and on a context
+ * whose communicator has more than one rank (the rule of esim_restart) or that holds a shard; ESIM_ERANGE / ESIM_ENOMEM as
+ * the series calls give them; a sticky device-side error is reported as the series calls report it.  They leave the
+ * simulation state, the records, the snapshot, the ensemble accumulators and the labels as they are.  Temporary device memory,
+ * freed when the call returns: 4 B per citizen for the exposure steps, 1 B per citizen for the setting, 1 B per step for each
+ * of the two bits, 4 B per citizen for the vaccination replay once a programme has run, 4 KB for the earlier LUT behind a
+ * seam, and the rows or the building table (4 B per cell).  The work per exposure is one walk over its household. */
+enum { ESIM_SETTING_HOUSEHOLD = 0, ESIM_SETTING_WORKPLACE = 1, ESIM_SETTING_SCHOOL = 2, ESIM_SETTING_TRANSPORT = 3, ESIM_N_SETTINGS = 4 };
+#define ESIM_SETTING_NONE 0xFFu
+enum { ESIM_BY_SETTING = 3 };                  /* `where` of esim_setting_series, beside ESIM_AREA_HOME and ESIM_BY_GROUP */
+int  esim_exposure_settings(esim_ctx *ctx, uint8_t *setting /* [n_citizens] or NULL */, uint32_t *building /* [n_citizens] or NULL */);
+int  esim_setting_series(esim_ctx *ctx, int where, uint32_t setting_mask, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                         uint32_t *out /* [n_rows * n_cols] */);
+int  esim_building_exposures(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts /* [n_buildings] */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
