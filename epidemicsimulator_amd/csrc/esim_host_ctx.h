@@ -120,7 +120,9 @@ struct Seam { uint32_t step = 0, rate = 0; uint64_t seed = 0; };
 // values, kept here, and the later ones under those in force.  A record of its own beside Seam: nothing that hangs on Seam (the
 // refusals of esim_snapshot and of the checkpoint calls) reads it.  step == 0: none.  twice: the snapshot itself lay on a
 // branch with such a seam and the rollback changed the values again -- three parameter sets, which the replay does not follow.
-struct DrawSeam { uint32_t step = 0; bool twice = false; uint64_t seed = 0; double chance = 0.0, mask_effectiveness = 0.0; };
+// two_capacities: a rollback changed bus_capacity, the buses of the history were filled under two values (esim_transmission_tree
+// and its kin, which replay the bus assignment, refuse that).
+struct DrawSeam { uint32_t step = 0; bool twice = false, two_capacities = false; uint64_t seed = 0; double chance = 0.0, mask_effectiveness = 0.0; };
 
 // What picks the form and the grids of the kernels: esim_set_* and the tuning knobs of the environment (read at upload).
 struct Tuning {

@@ -153,6 +153,7 @@ extern "C" int esim_rollback(esim_ctx *ctx, const esim_params *p)
     c->draw_seam = c->snap_draw_seam;
     if (redrawn && c->draw_seam.step) c->draw_seam.twice = true;
     else if (redrawn) { c->draw_seam.step = s.step; c->draw_seam.seed = s.P.seed; c->draw_seam.chance = s.P.exposure_chance; c->draw_seam.mask_effectiveness = s.P.mask_effectiveness; }
+    if (q.bus_capacity != s.P.bus_capacity) c->draw_seam.two_capacities = true;
     return ESIM_OK;
 }
 

@@ -32,21 +32,32 @@ __global__ __launch_bounds__(TPB) void k_setting_scatter(Dev d, Setting q, uint3
     }
 }
 
-// Was resident m Infected in step ts and standing in its household's building?  Infected during the infected_time + 1 steps
-// behind the Exposed ones (status_of), still so in the step at whose end it was vaccinated; away while on a bus or at work.
-__device__ __forceinline__ bool infected_at_home(const Dev &d, const Setting &q, uint32_t m, int ts, bool work_hour, bool bus_hour)
+// Does step ts lie in the infected_time + 1 Infected steps of citizen m, which follow the Exposed ones behind its exposure step
+// (status_of)?
+__device__ __forceinline__ bool in_infected_steps(const Dev &d, const Setting &q, uint32_t m, int ts)
 {
     const uint32_t tm = q.te_of[m];
     if (tm == SETTING_TE_NONE) return false;
     const int inf = (int)tm - (int)TE_BIAS + (int)d.exposed_time + 1;
-    if (ts < inf || ts > inf + (int)d.infected_time) return false;
+    return ts >= inf && ts <= inf + (int)d.infected_time;
+}
+
+// Was citizen m, whose word is w, set Vaccinated at the end of a step before ts?  (It is still Infected in that step itself.)
+__device__ __forceinline__ bool vaccinated_before(const Setting &q, uint32_t m, uint32_t w, int ts)
+{
+    if (CW_TE(w) != TE_VACCINATED) return false;
+    const uint32_t own = q.vax_of ? q.vax_of[m] : 0xFFFFFFFFu, v = q.t_all < own ? q.t_all : own;
+    return v != 0xFFFFFFFFu && (uint32_t)ts > v;
+}
+
+// Was resident m Infected in step ts and standing in its household's building?  Infected during the infected_time + 1 steps
+// behind the Exposed ones, still so in the step at whose end it was vaccinated; away while on a bus or at work.
+__device__ __forceinline__ bool infected_at_home(const Dev &d, const Setting &q, uint32_t m, int ts, bool work_hour, bool bus_hour)
+{
+    if (!in_infected_steps(d, q, m, ts)) return false;
     const uint32_t w = d.cit[m];
     if ((bus_hour && (w & FL_USES_PT)) || (work_hour && (w & FL_HAS_WORK))) return false;
-    if (CW_TE(w) == TE_VACCINATED) {
-        const uint32_t own = q.vax_of ? q.vax_of[m] : 0xFFFFFFFFu, v = q.t_all < own ? q.t_all : own;
-        if (v != 0xFFFFFFFFu && (uint32_t)ts > v) return false;
-    }
-    return true;
+    return !vaccinated_before(q, m, w, ts);
 }
 
 // A lane per citizen: households are tiny and, in a home-sorted population, neighbouring lanes walk the same few words.

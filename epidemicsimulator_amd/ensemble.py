@@ -67,9 +67,10 @@ def _json_number(x):
 
 
 class EnsembleResult:
-    def __init__(self, records, n_done, members, area=None, area_codes=None, settings=None):
+    def __init__(self, records, n_done, members, area=None, area_codes=None, settings=None, reproduction=None):
         self.records = records            # structured [members, n_steps]
         self.settings = settings          # uint32 [members, n_rows, 4]: every member's setting_series(where="setting"), or None
+        self.reproduction = reproduction  # uint32 [members, n_rows, 2]: every member's reproduction_series("all"), (cases, offspring), or None
         self.n_done = np.asarray(n_done, np.uint32)
         self.members = list(members)      # the overrides of every member
         self.area = area                  # area_summary(...) or None
@@ -91,7 +92,8 @@ class EnsembleResult:
         and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index (an arrival
         summary's mean and var are null where hit is 0).  A series summary goes to ensemble_area_series.npz instead -- steps,
         hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary.  The members' exposures by setting, where they
-        were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names."""
+        were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
+        ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -115,6 +117,8 @@ class EnsembleResult:
             json.dump(doc, fh)
         if self.settings is not None:
             np.savez(os.path.join(directory, "ensemble_settings.npz"), settings=self.settings, names=np.asarray(_lib.SETTING_NAMES))
+        if self.reproduction is not None:
+            np.savez(os.path.join(directory, "ensemble_reproduction.npz"), reproduction=self.reproduction, names=np.asarray(("cases", "offspring")))
 
 
 _KINDS = ("census", "arrival", "series")
@@ -184,6 +188,31 @@ class Ensemble:
         return None if spec is None else (np.stack(rows) if rows else np.zeros((0, spec["n_rows"], _lib.N_SETTINGS), np.uint32))
 
     @staticmethod
+    def _reproduction_rows(who, reproduction, n_steps, stop_when_done=False):
+        """reproduction of run() / forecast() checked, before anything runs: the arguments of Simulator.reproduction_series, or None."""
+        if reproduction is None:
+            return None
+        unknown = set(reproduction) - {"first_step", "n_rows", "stride"}
+        if unknown:
+            raise ValueError("Ensemble.%s: reproduction takes first_step, n_rows and stride, got %s" % (who, sorted(unknown)))
+        if stop_when_done:
+            raise ValueError("Ensemble.%s: reproduction cannot go with stop_when_done=True (a member that stopped early has no "
+                             "rows behind its last step)" % who)
+        first, stride = int(reproduction.get("first_step", 0)), int(reproduction.get("stride", 24))
+        n_rows = reproduction.get("n_rows")
+        if n_rows is None:
+            n_rows = (int(n_steps) - first) // stride + 1 if stride > 0 and 0 <= first <= int(n_steps) else 0
+        return dict(first_step=first, n_rows=int(n_rows), stride=stride)
+
+    @staticmethod
+    def _reproduction_stack(rows, spec):
+        return None if spec is None else (np.stack(rows) if rows else np.zeros((0, spec["n_rows"], 2), np.uint32))
+
+    def _reproduction_of_member(self, spec):
+        cases, offspring = self.simulator.reproduction_series("all", **spec)
+        return np.concatenate([cases, offspring], axis=1)
+
+    @staticmethod
     def seeds(k, first=1):
         return [{"seed": int(first) + i} for i in range(int(k))]
 
@@ -193,7 +222,7 @@ class Ensemble:
         pop = self.simulator.population
         return [{"seed": int(first) + i, "index_cases": pop.draw_index_cases(n, int(first) + i).tolist()} for i in range(int(k))]
 
-    def run(self, members, n_steps, stop_when_done=False, area=None, settings=None):
+    def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may
         carry "index_cases": the citizens that start Infected in that member (one without starts from the population's own).
         area: None, or the arguments of esim_ensemble_begin as a dict (where, status_mask, min_cases); where="group" counts by
@@ -204,16 +233,20 @@ class Ensemble:
         series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError).
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
         (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
-        with stop_when_done=True either.  Returns an EnsembleResult."""
+        with stop_when_done=True either.
+        reproduction: None, or dict(first_step=..., n_rows=..., stride=...): every member's cohort rows
+        (Simulator.reproduction_series("all")) gathered as EnsembleResult.reproduction, [members, n_rows, 2] = (cases,
+        offspring); not with stop_when_done=True either.  Returns an EnsembleResult."""
         kind, area = self._area_kind("run", area, stop_when_done)
         spec = self._settings_rows("run", settings, n_steps, stop_when_done)
+        r_spec = self._reproduction_rows("run", reproduction, n_steps, stop_when_done)
         sim = self.simulator
         members = [dict(m) for m in members]
         for m in members:
             if "index_cases" in m:
                 m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
         self._begin(kind, area)
-        rows, n_done, by_setting = [], [], []
+        rows, n_done, by_setting, by_cohort = [], [], [], []
         for m in members:
             over = {k: v for k, v in m.items() if k != "index_cases"}
             seeds = m.get("index_cases")
@@ -226,22 +259,26 @@ class Ensemble:
                 sim.ensemble_fold()
             if spec is not None:
                 by_setting.append(sim.setting_series("setting", **spec))
+            if r_spec is not None:
+                by_cohort.append(self._reproduction_of_member(r_spec))
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec))
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec),
+                              self._reproduction_stack(by_cohort, r_spec))
 
-    def forecast(self, history_steps, members, n_steps, area=None, settings=None):
+    def forecast(self, history_steps, members, n_steps, area=None, settings=None, reproduction=None):
         """Given the epidemic as it stands after `history_steps` steps under the base parameters, what happens next: the base
         run is made once and kept on the device (Simulator.snapshot), and every member is a branch from it -- a rollback under
         the base parameters changed by the member's overrides, then the remaining n_steps - history_steps steps.  members as
         for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
-        library refuses them).  area and settings: as for run(), folded / gathered once per member.  Returns an EnsembleResult whose records are
+        library refuses them).  area, settings and reproduction: as for run(), folded / gathered once per member.  Returns an EnsembleResult whose records are
         [members, n_steps], the shared history repeated in every row."""
         kind, area = self._area_kind("forecast", area)
         spec = self._settings_rows("forecast", settings, n_steps)
+        r_spec = self._reproduction_rows("forecast", reproduction, n_steps)
         sim = self.simulator
         history_steps, n_steps = int(history_steps), int(n_steps)
         if not 1 <= history_steps <= n_steps:
@@ -254,7 +291,7 @@ class Ensemble:
         self._own_seeds = True
         history = sim.run(history_steps)
         sim.snapshot()
-        rows, n_done, by_setting = [], [], []
+        rows, n_done, by_setting, by_cohort = [], [], [], []
         for m in members:
             sim.rollback(**m)
             rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
@@ -262,12 +299,15 @@ class Ensemble:
                 sim.ensemble_fold()
             if spec is not None:
                 by_setting.append(sim.setting_series("setting", **spec))
+            if r_spec is not None:
+                by_cohort.append(self._reproduction_of_member(r_spec))
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
         by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec))
+        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec),
+                              self._reproduction_stack(by_cohort, r_spec))
 
     def close(self):
         self.simulator.close()

@@ -569,6 +569,50 @@ class Simulator:
         _lib.check(self.lib.esim_building_exposures(self._ctx, int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
+    # -- who infected whom (esim_transmission_tree, esim_offspring, esim_reproduction_series, esim_mixing_matrix) -------
+    def transmission_tree(self):
+        """(infector, n_candidates, generation), uint32 [n_citizens] each, derived on the device from the exposure log
+        (esim_transmission_tree).  infector: the citizen every exposure is credited to -- one of the Infected that stood where
+        it happened, picked by a Philox draw of its own --, _lib.NO_INFECTOR for the index cases and for citizens never
+        exposed; n_candidates: how many there were to pick from; generation: 0 for an index case, the infector's + 1
+        otherwise, _lib.NEVER for a citizen never exposed."""
+        n = self.population.n_citizens
+        out = [np.zeros(n, np.uint32) for _ in range(3)]
+        _lib.check(self.lib.esim_transmission_tree(self._ctx, *(a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out)), self._ctx)
+        return tuple(out)
+
+    def offspring(self, first_step=1, last_step=None):
+        """uint32 [n_citizens]: how many of the citizens exposed in steps first_step .. last_step (None: the last step run)
+        every citizen infected (esim_offspring)."""
+        out = np.zeros(self.population.n_citizens, np.uint32)
+        last = self._steps if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_offspring(self._ctx, int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
+    def reproduction_series(self, where="all", first_step=0, n_rows=None, stride=24):
+        """(cases, offspring), uint32 [n_rows, n_cols] each (esim_reproduction_series): row i is the cohort exposed in the
+        `stride` steps from first_step + i * stride on (step 0: the index cases), `cases` its size and `offspring` the
+        citizens it infected, by the infector's column; offspring / cases is the cohort's case reproduction number.  where:
+        "all" (one column), "home" (by the Output Area of the household) or "group".  n_rows=None: up to the last step run."""
+        place = {"all": _lib.BY_ALL, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        n_cols = 1 if place == _lib.BY_ALL else max(1, self._n_groups) if place == _lib.BY_GROUP else self.population.n_areas
+        if n_rows is None:
+            n_rows = (self._steps - int(first_step)) // int(stride) + 1 if stride and 0 <= first_step <= self._steps else 0
+        cases, offspring = (np.zeros((max(0, int(n_rows)), n_cols), np.uint32) for _ in range(2))
+        _lib.check(self.lib.esim_reproduction_series(self._ctx, int(place), int(first_step), int(n_rows), int(stride),
+                                                     cases.ctypes.data_as(C.POINTER(C.c_uint32)), offspring.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return cases, offspring
+
+    def mixing_matrix(self, settings=None, first_step=1, last_step=None):
+        """uint32 [n_groups, n_groups]: entry [g_infector, g_infectee] counts the transmissions of steps first_step ..
+        last_step (None: the last step run) between the groups of set_groups, restricted to `settings` as setting_series
+        takes them (esim_mixing_matrix)."""
+        g = max(1, self._n_groups)
+        out = np.zeros((g, g), np.uint32)
+        last = self._steps if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_mixing_matrix(self._ctx, self._setting_mask(settings), int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

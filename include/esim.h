@@ -425,7 +425,8 @@ int  esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_
  *      ESIM_ESIM with their number in esim_last_error after delivering everything else.  On a correct run there is none: the
  *      calls double as an audit of the log.
  * The tie is a stated contract: when the household draw and a work-side draw both succeed in one step, the HOUSEHOLD is
- * credited.  (The reference credits whichever building its hash map visits first: no rule.  The work side is never replayed.)
+ * credited.  (The reference credits whichever building its hash map visits first: no rule.  The work side is never replayed by these three
+ * calls; esim_transmission_tree and its kin, below, walk it.)
  * After an esim_rollback under another seed, exposure_chance or mask_effectiveness the entries up to the snapshot's step are
  * replayed under the snapshot's values and the later ones under those in force; a snapshot taken on such a branch and rolled
  * back to under yet other values is ESIM_ESTATE here (a history mixed twice is not built).
@@ -455,6 +456,66 @@ int  esim_exposure_settings(esim_ctx *ctx, uint8_t *setting /* [n_citizens] or N
 int  esim_setting_series(esim_ctx *ctx, int where, uint32_t setting_mask, uint32_t first_step, uint32_t n_rows, uint32_t stride,
                          uint32_t *out /* [n_rows * n_cols] */);
 int  esim_building_exposures(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts /* [n_buildings] */);
+/* Who infected whom: the transmission tree, the offspring of every citizen, the reproduction number by cohort and the
+ * who-acquires-infection-from-whom matrix between citizen groups, derived after the fact like the settings above and on top of
+ * them.  (The reference cannot say: its exposure chance is 1 - (1 - p)^n over the n Infected present, no infector is recorded.)
+ * The rule, per entry (c, ts) of the exposure log with ts >= 1, its setting and building as esim_exposure_settings gives them,
+ * the tie rule included.  The CANDIDATES are the citizens that are Infected after the tick of step ts and stand where the
+ * exposure is credited.  Infected in ts: the exposure step comes from the log, exposed_time + 1 steps later the
+ * infected_time + 1 Infected steps follow; an Infected citizen is still Infected in the step at whose end it was vaccinated;
+ * the index cases are Infected from step 1.
+ *   household         the residents of c's household that are Infected in ts and at home: not on a bus and not at work in that
+ *                     step (the n_home of rule 2 above);
+ *   work place        the workers of c's work building that are Infected in ts, at work and not on a bus (the bus hour before
+ *                     end_hour has both bits set: an Infected rider marks no building then);
+ *   school            the participants of c's own ROOM under the same predicate (the school draws one copy of the room per
+ *                     Infected in it: the infector is somebody of that room, not of the school);
+ *   public transport  the Infected riders of c's bus: the riders of c's route (home area, work area) ordered by (key, position in
+ *                     the route), key = word 0 of Philox4x32-10 over (global citizen, ts, ESIM_SLOT_BUS_ORDER, 0) under the seed --
+ *                     the step is the counter word itself --, bus = rank / bus_capacity; a route of at most bus_capacity riders is
+ *                     one bus and needs no keys.
+ * With k candidates in ascending local citizen index and u the 32-bit Philox word of (seed, global citizen c, ts, slot 5 =
+ * ESIM_SLOT_INFECTOR), the infector is candidate number ((uint64_t)u * k) >> 32.  This is a stated contract as the tie rule is:
+ * given that the exposure happened, every Infected present is equally likely to be its source, and the draw makes the tree
+ * reproducible.  k = 0 means the log holds an exposure nobody can have caused: such entries are counted on the device, get
+ * ESIM_NO_INFECTOR, and the call returns ESIM_ESIM with their number in esim_last_error after delivering everything else -- the
+ * audit of the settings, now for the work side and the buses too.  Index cases and citizens never exposed: ESIM_NO_INFECTOR.
+ * Generation: 0 for an index case, the infector's + 1 otherwise, ESIM_NEVER for a citizen never exposed or unexplained.
+ * After an esim_rollback under another seed the bus keys and the pick of the entries up to the snapshot's step use the
+ * snapshot's seed, as the household replay does.  After a rollback that changed bus_capacity these calls are ESIM_ESTATE (a bus
+ * replay under two capacities is not built) until an esim_restart, esim_reset or upload; on a sharded context and on a history
+ * mixed twice they are ESIM_ESTATE as the calls above.
+ * esim_transmission_tree: infector[c], n_candidates[c] (the k of c's exposure, 0 where there is none) and generation[c] per
+ *        citizen.  Any pointer may be NULL; with all three NULL the audit still runs and its result is returned.
+ * esim_offspring: counts[j] = the citizens exposed in steps [first_step, last_step] whose infector is j.  ESIM_ERANGE as
+ *        esim_building_exposures gives it.
+ * esim_reproduction_series: row i is the COHORT exposed in steps [first_step + i * stride, + stride), clipped to the steps run;
+ *        first_step 0 is allowed here and only here: the index cases are the cohort of step 0.  cases[i * n_cols + col] is the
+ *        size of the cohort, offspring[...] the citizens whose infector lies in that cohort and column -- the column is the
+ *        infector's.  offspring / cases is the case reproduction number of the cohort.  Either output may be NULL, not both.
+ *          where = ESIM_BY_ALL       one column
+ *          where = ESIM_AREA_HOME    n_areas columns, by the Output Area of the household
+ *          where = ESIM_BY_GROUP     n_groups columns (ESIM_ESTATE without labels)
+ *        Any other `where`, ESIM_AREA_CURRENT included, is ESIM_EINVAL, as are stride 0 and no rows; ESIM_ERANGE for rows outside
+ *        the steps run.  A row is COMPLETE -- later steps add nothing to it -- once the last Infected step of a citizen exposed
+ *        in the row's last step s has run: s + exposed_time + 1 + infected_time <= the steps run so far.
+ * esim_mixing_matrix: counts[g_infector * n_groups + g_infectee] over the transmissions of steps [first_step, last_step] whose
+ *        setting has its bit in setting_mask.  ESIM_ESTATE without labels; the mask's errors are those of esim_setting_series,
+ *        ESIM_ERANGE as esim_building_exposures gives it.
+ * All four leave the simulation state, the records, the snapshot, the ensemble accumulators and the labels as they are.
+ * Temporary device memory, freed when the call returns: that of the settings above; 4 B per citizen each for the infector, k and
+ * the generation; 4 B per entry of the exposure log for the queue of the exposures outside households; the rows or the table
+ * (4 B per cell).  The work per exposure is one walk, by a whole wavefront, over the members of the place credited; on a route
+ * longer than a bus every Infected rider is ranked against all riders of the route. */
+#define ESIM_NO_INFECTOR 0xFFFFFFFFu
+enum { ESIM_BY_ALL = 4 };                      /* `where` of esim_reproduction_series, beside ESIM_AREA_HOME and ESIM_BY_GROUP */
+int  esim_transmission_tree(esim_ctx *ctx, uint32_t *infector /* [n_citizens] or NULL */, uint32_t *n_candidates /* [n_citizens] or NULL */,
+                            uint32_t *generation /* [n_citizens] or NULL */);
+int  esim_offspring(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts /* [n_citizens] */);
+int  esim_reproduction_series(esim_ctx *ctx, int where, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                              uint32_t *cases /* [n_rows * n_cols] or NULL */, uint32_t *offspring /* [n_rows * n_cols] or NULL */);
+int  esim_mixing_matrix(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
+                        uint32_t *counts /* [n_groups * n_groups] */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
