@@ -1,5 +1,6 @@
 // esim_host_tree.h -- who infected whom: esim_transmission_tree, esim_offspring, esim_reproduction_series, esim_mixing_matrix (the
-// kernels: esim_kernels_tree.h).  All four run on top of settings_enqueue / settings_finish: the setting of every
+// kernels: esim_kernels_tree.h), and the chains on top of the tree: esim_transmission_chains, esim_outbreaks,
+// esim_transmission_ages (esim_kernels_chains.h).  All of them run on top of settings_enqueue / settings_finish: the setting of every
 // logged exposure first, then its candidates and its infector, in temporary device memory that lives as long as the call.
 namespace {
 
@@ -154,5 +155,126 @@ extern "C" int esim_mixing_matrix(esim_ctx *ctx, uint32_t setting_mask, uint32_t
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (words) HIP_TRY(c, hipMemcpy(counts, tab.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+namespace {
+
+enum : unsigned { CHAIN_UP = 1u, CHAIN_DOWN = 2u, CHAIN_TABLE = 4u, CHAIN_AGE = 8u };   // the passes a call needs
+
+struct ChainWork {
+    TreeWork t;
+    DevTmp<uint32_t> lineage, desc, tab;   // tab: size, depth, last_step [n_seeds] each, the age table, the two audit counters
+    Chain ch;
+};
+
+// The tree (with the generations where the per-seed table is asked for), then the passes in `what`: the index cases numbered
+// and the lineage handed forward, the descendants summed backward -- a launch per window of exposed_time + 1 steps each, as the
+// generations take --, the per-seed table, the ages of steps [first, last].  The allocations live as long as *w.
+int chains_enqueue(esim_ctx_impl *c, const std::string &who, ChainWork *w, unsigned what, uint32_t first, uint32_t last)
+{
+    const Dev &d = c->d;
+    const size_t n = d.n, n_seeds = c->init_log.size(), words = 3 * n_seeds + CHAIN_AGES + 2u;
+    const bool up = (what & CHAIN_UP) != 0u, down = (what & CHAIN_DOWN) != 0u;
+    if ((up && w->lineage.alloc(n) != hipSuccess) || (down && w->desc.alloc(n) != hipSuccess) || w->tab.alloc(words) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, who + ": no device memory for the chains (4 B per citizen each for the lineage and the descendants, 12 B per seed, 8 KB for the ages)");
+    }
+    if (int rc = tree_enqueue(c, who, &w->t, (what & CHAIN_TABLE) != 0u)) return rc;
+    const uint32_t log_len = w->t.s.log_len, t_done = w->t.s.q.t_done;
+    Chain &ch = w->ch;
+    ch.lineage = w->lineage.p; ch.desc = w->desc.p;
+    ch.size = w->tab.p; ch.depth = ch.size + n_seeds; ch.last = ch.depth + n_seeds; ch.ages = ch.last + n_seeds;
+    ch.bad_age = ch.ages + CHAIN_AGES; ch.unrooted = ch.bad_age + 1;
+    ch.n_seeds = (uint32_t)std::min<size_t>(n_seeds, log_len);
+    hipError_t e = hipMemsetAsync(w->tab.p, 0, sizeof(uint32_t) * words, c->stream);
+    if (e == hipSuccess && up) e = hipMemsetAsync(ch.lineage, 0xFF, sizeof(uint32_t) * std::max<size_t>(1, n), c->stream);
+    if (e == hipSuccess && down) e = hipMemsetAsync(ch.desc, 0, sizeof(uint32_t) * std::max<size_t>(1, n), c->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
+    if (up) hipLaunchKernelGGL(k_chain_roots, dim3(grid_for(ch.n_seeds, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d, ch);
+    if ((up || down) && t_done) {
+        const uint32_t span = d.exposed_time + 1u, n_win = (t_done + span - 1u) / span;
+        const uint32_t grid = grid_for((size_t)log_len / n_win * 2u + 1u, TPB, 1024);
+        if (up)
+            for (uint32_t lo = 1u; lo <= t_done; lo += span)
+                hipLaunchKernelGGL(k_chain_up, dim3(grid), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, lo, std::min(t_done, lo + span - 1u), log_len);
+        if (down)
+            for (uint32_t k = n_win; k-- > 0u;) {
+                const uint32_t lo = 1u + k * span;
+                hipLaunchKernelGGL(k_chain_down, dim3(grid), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, lo, std::min(t_done, lo + span - 1u), log_len);
+            }
+    }
+    if (what & CHAIN_TABLE) hipLaunchKernelGGL(k_chain_outbreaks, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, log_len);
+    // (a workgroup of k_chain_ages walks 32 entries per lane at least before it hands over its table of 2048 counters at most)
+    if (what & CHAIN_AGE) hipLaunchKernelGGL(k_chain_ages, dim3(grid_for(log_len, TPB * 32u, 1024)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, first, last, log_len);
+    return ESIM_OK;
+}
+
+// The tail of the three calls: the tree's wait and audits, then the two of the chains -- ESIM_ESIM where a chain does not end at
+// an index case, or a transmission has an infectious age that no Infected citizen has.
+int chains_finish(esim_ctx_impl *c, const std::string &who, ChainWork *w)
+{
+    const int rc = tree_finish(c, who, &w->t);
+    if (rc) return rc;
+    uint32_t bad[2] = { 0u, 0u };
+    HIP_TRY(c, hipMemcpy(bad, w->ch.bad_age, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[1]) return fail(c, ESIM_ESIM, who + ": " + std::to_string(bad[1]) + " exposures of the log lie on a chain that does not end at an index case (they carry ESIM_NO_LINEAGE)");
+    if (bad[0]) return fail(c, ESIM_ESIM, who + ": " + std::to_string(bad[0]) + " transmissions have an infectious age outside 0 .. infected_time: the infector was not Infected in that step (they are not counted)");
+    return ESIM_OK;
+}
+
+}  // namespace
+
+extern "C" int esim_transmission_chains(esim_ctx *ctx, uint32_t *lineage, uint32_t *descendants)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_transmission_chains";
+    if (int rc = tree_check(c, who)) return rc;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    ChainWork w;
+    if (int rc = chains_enqueue(c, who, &w, CHAIN_UP | (descendants ? CHAIN_DOWN : 0u), 0u, 0u)) return rc;   // (the lineage pass carries an audit)
+    const int rc = chains_finish(c, who, &w);
+    if (rc && rc != ESIM_ESIM) return rc;
+    const size_t bytes = sizeof(uint32_t) * (size_t)c->d.n;
+    if (lineage && bytes) HIP_TRY(c, hipMemcpy(lineage, w.ch.lineage, bytes, hipMemcpyDeviceToHost));
+    if (descendants && bytes) HIP_TRY(c, hipMemcpy(descendants, w.ch.desc, bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+extern "C" int esim_outbreaks(esim_ctx *ctx, uint32_t *size, uint32_t *depth, uint32_t *last_step, uint32_t cap, uint32_t *n_out)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_outbreaks";
+    if (!n_out) return fail(c, ESIM_EINVAL, who + ": null n_out");
+    if (int rc = tree_check(c, who)) return rc;
+    const uint32_t n_seeds = (uint32_t)c->init_log.size();
+    *n_out = n_seeds;
+    if (n_seeds > cap) return fail(c, ESIM_ERANGE, who + ": buffers too small (n_out holds the size needed)");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    ChainWork w;
+    if (int rc = chains_enqueue(c, who, &w, CHAIN_UP | CHAIN_DOWN | CHAIN_TABLE, 0u, 0u)) return rc;
+    const int rc = chains_finish(c, who, &w);
+    if (rc && rc != ESIM_ESIM) return rc;
+    const size_t bytes = sizeof(uint32_t) * (size_t)n_seeds;
+    if (size && bytes) HIP_TRY(c, hipMemcpy(size, w.ch.size, bytes, hipMemcpyDeviceToHost));
+    if (depth && bytes) HIP_TRY(c, hipMemcpy(depth, w.ch.depth, bytes, hipMemcpyDeviceToHost));
+    if (last_step && bytes) HIP_TRY(c, hipMemcpy(last_step, w.ch.last, bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+extern "C" int esim_transmission_ages(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_transmission_ages";
+    if (!counts) return fail(c, ESIM_EINVAL, who + ": null output");
+    if (int rc = tree_check(c, who)) return rc;
+    if (first_step == 0 || last_step < first_step || last_step > c->host_t - 1u)
+        return fail(c, ESIM_ERANGE, who + ": steps outside 1 .. the steps run so far, or last_step before first_step");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    ChainWork w;
+    if (int rc = chains_enqueue(c, who, &w, CHAIN_AGE, first_step, last_step)) return rc;
+    const int rc = chains_finish(c, who, &w);
+    if (rc && rc != ESIM_ESIM) return rc;
+    HIP_TRY(c, hipMemcpy(counts, w.ch.ages, sizeof(uint32_t) * CHAIN_AGES, hipMemcpyDeviceToHost));
     return rc;
 }

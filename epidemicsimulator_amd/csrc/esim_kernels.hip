@@ -35,5 +35,6 @@
 #include "esim_kernels_series.h"
 #include "esim_kernels_setting.h"
 #include "esim_kernels_tree.h"
+#include "esim_kernels_chains.h"
 #include "esim_kernels_restart.h"
 #include "esim_kernels_snapshot.h"

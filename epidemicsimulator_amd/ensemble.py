@@ -121,6 +121,44 @@ class EnsembleResult:
             np.savez(os.path.join(directory, "ensemble_reproduction.npz"), reproduction=self.reproduction, names=np.asarray(("cases", "offspring")))
 
 
+class OutbreakResult:
+    """What Ensemble.outbreaks gathers: the outbreak table of every member, one row per member and one column per index case."""
+
+    def __init__(self, members, seeds, size, depth, last_step, ages=None):
+        self.members = list(members)      # the overrides of every member
+        self.seeds = list(seeds)          # per member the index cases in force, in the order of its columns (members may differ in number)
+        self.size = np.asarray(size, np.int64)            # int64 [members, max_seeds]; -1 where a member has fewer seeds
+        self.depth = np.asarray(depth, np.int64)
+        self.last_step = np.asarray(last_step, np.int64)
+        self.ages = ages                  # uint32 [members, 4, 512]: every member's transmission_ages(), or None
+
+    @classmethod
+    def gathered(cls, members, tables, ages=None):
+        """From every member's Simulator.outbreaks() dict, padded with -1 to the largest number of seeds."""
+        width = max([len(t["seeds"]) for t in tables], default=0)
+        cols = {k: np.full((len(tables), width), -1, np.int64) for k in ("size", "depth", "last_step")}
+        for i, t in enumerate(tables):
+            for k in cols:
+                cols[k][i, :len(t["seeds"])] = t[k]
+        return cls(members, [np.asarray(t["seeds"], np.uint32) for t in tables], cols["size"], cols["depth"], cols["last_step"],
+                   None if ages is None else (np.stack(ages) if ages else np.zeros((0, _lib.N_SETTINGS, _lib.AGE_BINS), np.uint32)))
+
+    def extinct(self, min_size=1):
+        """bool [members, max_seeds]: the introductions that infected fewer than min_size citizens (false in the padding)."""
+        return (self.size >= 0) & (self.size < int(min_size))
+
+    def dump(self, directory):
+        """ensemble_outbreaks.npz: size, depth, last_step and seeds (padded with -1 like them), and ages where they were asked for."""
+        os.makedirs(directory, exist_ok=True)
+        seeds = np.full(self.size.shape, -1, np.int64)
+        for i, s in enumerate(self.seeds):
+            seeds[i, :len(s)] = s
+        arrays = dict(size=self.size, depth=self.depth, last_step=self.last_step, seeds=seeds)
+        if self.ages is not None:
+            arrays["ages"] = self.ages
+        np.savez(os.path.join(directory, "ensemble_outbreaks.npz"), **arrays)
+
+
 _KINDS = ("census", "arrival", "series")
 
 
@@ -222,6 +260,40 @@ class Ensemble:
         pop = self.simulator.population
         return [{"seed": int(first) + i, "index_cases": pop.draw_index_cases(n, int(first) + i).tolist()} for i in range(int(k))]
 
+    @staticmethod
+    def _members(members):
+        members = [dict(m) for m in members]
+        for m in members:
+            if "index_cases" in m:
+                m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
+        return members
+
+    def _restart_member(self, m):
+        """The simulator back at step 0 under the base parameters changed by member m's overrides, from m's index cases or,
+        without any, the population's own."""
+        sim = self.simulator
+        over = {k: v for k, v in m.items() if k != "index_cases"}
+        seeds = m.get("index_cases")
+        if seeds is None and not self._own_seeds:
+            seeds = sim.population.seeds
+        sim.restart(self.base, seeds=seeds, **over)
+        self._own_seeds = "index_cases" not in m
+
+    def outbreaks(self, members, n_steps, ages=False):
+        """Which introduction took off: every member (as for run()) is run for n_steps steps and its outbreak table gathered
+        (Simulator.outbreaks: size, depth and last step per index case) and, with ages=True, its infectious-age profile
+        (Simulator.transmission_ages).  Returns an OutbreakResult."""
+        sim = self.simulator
+        members = self._members(members)
+        tables, profiles = [], []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            tables.append(sim.outbreaks())
+            if ages:
+                profiles.append(sim.transmission_ages())
+        return OutbreakResult.gathered(members, tables, profiles if ages else None)
+
     def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may
         carry "index_cases": the citizens that start Infected in that member (one without starts from the population's own).
@@ -241,19 +313,11 @@ class Ensemble:
         spec = self._settings_rows("run", settings, n_steps, stop_when_done)
         r_spec = self._reproduction_rows("run", reproduction, n_steps, stop_when_done)
         sim = self.simulator
-        members = [dict(m) for m in members]
-        for m in members:
-            if "index_cases" in m:
-                m["index_cases"] = [int(x) for x in np.asarray(m["index_cases"]).ravel()]
+        members = self._members(members)
         self._begin(kind, area)
         rows, n_done, by_setting, by_cohort = [], [], [], []
         for m in members:
-            over = {k: v for k, v in m.items() if k != "index_cases"}
-            seeds = m.get("index_cases")
-            if seeds is None and not self._own_seeds:
-                seeds = sim.population.seeds
-            sim.restart(self.base, seeds=seeds, **over)
-            self._own_seeds = "index_cases" not in m
+            self._restart_member(m)
             rec = sim.run(n_steps, stop_when_done=stop_when_done)
             if area is not None:
                 sim.ensemble_fold()

@@ -613,6 +613,35 @@ class Simulator:
         _lib.check(self.lib.esim_mixing_matrix(self._ctx, self._setting_mask(settings), int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
+    # -- transmission chains (esim_transmission_chains, esim_outbreaks, esim_transmission_ages) -------
+    def transmission_chains(self):
+        """(lineage, descendants), uint32 [n_citizens] each (esim_transmission_chains).  lineage: the position in seeds() of
+        the index case at the root of the citizen's chain -- an index case carries its own --, _lib.NO_LINEAGE for a citizen
+        never exposed; descendants: the citizens in the subtree below the citizen, itself not counted."""
+        out = [np.zeros(self.population.n_citizens, np.uint32) for _ in range(2)]
+        _lib.check(self.lib.esim_transmission_chains(self._ctx, *(a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out)), self._ctx)
+        return tuple(out)
+
+    def outbreaks(self):
+        """The outbreak every index case started (esim_outbreaks), a dict of uint32 [n_seeds] arrays in the order of seeds():
+        seeds, size (the descendants of the index case), depth (the largest generation of its lineage, 0 when it infected
+        nobody) and last_step (the last exposure step of its lineage, 0 when none).  Nothing per citizen comes to the host."""
+        seeds = self.seeds()
+        out = {k: np.zeros(len(seeds), np.uint32) for k in ("size", "depth", "last_step")}
+        n = C.c_uint32(0)
+        _lib.check(self.lib.esim_outbreaks(self._ctx, *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in ("size", "depth", "last_step")),
+                                           len(seeds), C.byref(n)), self._ctx)
+        return dict(out, seeds=seeds)
+
+    def transmission_ages(self, first_step=1, last_step=None):
+        """uint32 [4, 512]: entry [setting, a] counts the transmissions of steps first_step .. last_step (None: the last step
+        run; the step is the infectee's) made in step a of the infector's infectious period, a = 0 its first Infected step
+        (esim_transmission_ages).  For an infector that is not an index case the generation interval is a + exposed_time + 1."""
+        out = np.zeros((_lib.N_SETTINGS, _lib.AGE_BINS), np.uint32)
+        last = self._steps if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_transmission_ages(self._ctx, int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

@@ -516,6 +516,47 @@ int  esim_reproduction_series(esim_ctx *ctx, int where, uint32_t first_step, uin
                               uint32_t *cases /* [n_rows * n_cols] or NULL */, uint32_t *offspring /* [n_rows * n_cols] or NULL */);
 int  esim_mixing_matrix(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
                         uint32_t *counts /* [n_groups * n_groups] */);
+/* Transmission chains: which introduction a case descends from, how large the outbreak is that a citizen started, and when
+ * during their infectious period people transmit -- functions of the tree above, computed where it lies, so that nothing of
+ * size [n_citizens] has to go to the host for them.  Per entry (c, ts) of the exposure log; infector, generation and setting
+ * as esim_transmission_tree and esim_exposure_settings define them, the tie rule and the seam of a rollback included.
+ *   lineage[c]      the ordinal, in the order of esim_get_seeds, of the index case at the root of c's chain.  An index case
+ *                   carries its own ordinal; a citizen never exposed, and one whose chain passes through an exposure without a
+ *                   candidate (generation == ESIM_NEVER), carries ESIM_NO_LINEAGE.
+ *   descendants[c]  the citizens in the subtree below c, c itself not counted: 0 for a citizen that infected nobody or was
+ *                   never exposed.  A subtree that reaches no index case still counts inside itself.
+ *   outbreak of index case i:  size[i] = descendants[seed i]; depth[i] the largest generation among the citizens of lineage i
+ *                   (0 when it infected nobody); last_step[i] the last exposure step among them (0 when none).
+ *   infectious age of a transmission:  a = ts - onset(infector), onset = te + exposed_time + 1 for an infector whose exposure
+ *                   step te is in the log, 0 for an index case (Infected from step 1).  0 <= a <= infected_time on a correct
+ *                   run, and esim_create enforces exposed_time + infected_time + 2 <= 512, so ESIM_AGE_BINS bins always
+ *                   suffice.  For an infector that is not an index case the GENERATION INTERVAL -- from its own exposure to
+ *                   the exposure it caused -- is a + exposed_time + 1.
+ * esim_transmission_chains: lineage and descendants per citizen.  Either pointer may be NULL; with both NULL the audits still
+ *        run and their result is returned.
+ * esim_outbreaks: size, depth and last_step per index case, [cap] each, any may be NULL.  *n_out receives the number of
+ *        distinct seeds in force; ESIM_ERANGE, with *n_out set, when cap is smaller (the rule of esim_get_seeds); ESIM_EINVAL
+ *        for a null n_out.  12 B per seed go to the host and nothing per citizen.
+ * esim_transmission_ages: counts[setting * ESIM_AGE_BINS + a] over the transmissions of steps [first_step, last_step] (the
+ *        step is the infectee's).  ESIM_EINVAL for a null output, ESIM_ERANGE as esim_offspring gives it.  A transmission with
+ *        a outside 0 .. infected_time is impossible on a correct run: such entries are skipped and counted on the device, and
+ *        the call returns ESIM_ESIM with their number in esim_last_error after delivering everything else, as the exposures
+ *        without a candidate are reported above.
+ * The audits of the calls above run in all three (ESIM_ESIM after delivering everything else), and esim_transmission_chains
+ * and esim_outbreaks add one: an exposure whose chain does not end at an index case is counted and reported the same way.
+ * Refused as the four calls above: ESIM_ESTATE before an upload, on a sharded context, on a history mixed twice and after a
+ * rollback under another bus_capacity.  All three leave the simulation state, the records, the exposure log, the snapshot, the
+ * ensemble accumulators and the labels as they are, and derive the tree anew (nothing is kept between calls).
+ * Temporary device memory, freed when the call returns: that of esim_transmission_tree; 4 B per citizen each for the lineage
+ * and the descendants (esim_transmission_ages: neither); 12 B per seed and the 8 KB of the age table.  Lineage and descendants
+ * take one launch each per window of exposed_time + 1 steps, as the generations do: with exposed_time == 0 that is a launch
+ * per step. */
+#define ESIM_NO_LINEAGE 0xFFFFFFFFu
+#define ESIM_AGE_BINS   512
+int  esim_transmission_chains(esim_ctx *ctx, uint32_t *lineage /* [n_citizens] or NULL */, uint32_t *descendants /* [n_citizens] or NULL */);
+int  esim_outbreaks(esim_ctx *ctx, uint32_t *size, uint32_t *depth, uint32_t *last_step /* [cap] each, any may be NULL */,
+                    uint32_t cap, uint32_t *n_out);
+int  esim_transmission_ages(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts /* [ESIM_N_SETTINGS * ESIM_AGE_BINS] */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
