@@ -36,5 +36,6 @@
 #include "esim_kernels_setting.h"
 #include "esim_kernels_tree.h"
 #include "esim_kernels_chains.h"
+#include "esim_kernels_household.h"
 #include "esim_kernels_restart.h"
 #include "esim_kernels_snapshot.h"

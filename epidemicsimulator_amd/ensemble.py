@@ -159,6 +159,40 @@ class OutbreakResult:
         np.savez(os.path.join(directory, "ensemble_outbreaks.npz"), **arrays)
 
 
+class HouseholdResult:
+    """What Ensemble.households gathers: the final-size tables and the household pair tables of every member."""
+
+    def __init__(self, members, final_size, introductions, at_risk, secondary):
+        self.members = list(members)      # the overrides of every member
+        self.final_size = np.asarray(final_size, np.uint32)          # uint32 [members, 64, 64]: households of n residents with k cases
+        self.introductions = np.asarray(introductions, np.uint32)    # uint32 [members, 64, 64]: ... with k introductions
+        self.at_risk = np.asarray(at_risk, np.uint64)                # uint64 [members, n_cols, n_cols]: (case, housemate at risk) pairs
+        self.secondary = np.asarray(secondary, np.uint64)            # uint64 [members, n_cols, n_cols]: those infected at home by the case
+
+    @classmethod
+    def gathered(cls, members, sizes, pairs, n_cols=1):
+        """From every member's Simulator.household_final_sizes() and household_sar() tuples."""
+        b = _lib.HH_BINS
+
+        def stack(rows, shape, dtype):
+            return np.stack(rows).astype(dtype) if rows else np.zeros((0,) + shape, dtype)
+        return cls(members, stack([t[0] for t in sizes], (b, b), np.uint32), stack([t[1] for t in sizes], (b, b), np.uint32),
+                   stack([t[0] for t in pairs], (n_cols, n_cols), np.uint64), stack([t[1] for t in pairs], (n_cols, n_cols), np.uint64))
+
+    def sar(self):
+        """float64 [n_cols, n_cols]: the household secondary attack rate pooled over the members -- the sum of secondary
+        divided by the sum of at_risk --, NaN where nobody was at risk."""
+        at, sec = self.at_risk.sum(axis=0).astype(np.float64), self.secondary.sum(axis=0).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(at > 0, sec / at, np.nan)
+
+    def dump(self, directory):
+        """ensemble_households.npz: final_size, introductions, at_risk, secondary and the pooled sar."""
+        os.makedirs(directory, exist_ok=True)
+        np.savez(os.path.join(directory, "ensemble_households.npz"), final_size=self.final_size, introductions=self.introductions,
+                 at_risk=self.at_risk, secondary=self.secondary, sar=self.sar())
+
+
 _KINDS = ("census", "arrival", "series")
 
 
@@ -293,6 +327,21 @@ class Ensemble:
             if ages:
                 profiles.append(sim.transmission_ages())
         return OutbreakResult.gathered(members, tables, profiles if ages else None)
+
+    def households(self, members, n_steps, where="all", first_step=0, last_step=None):
+        """Household outbreaks over an ensemble: every member (as for run()) is run for n_steps steps and its final-size tables
+        (Simulator.household_final_sizes) and household pair tables (Simulator.household_sar(where, first_step, last_step),
+        complete cohorts only) gathered.  where="group" counts by the groups given to Ensemble(...).  Returns a HouseholdResult."""
+        sim = self.simulator
+        members = self._members(members)
+        sizes, pairs = [], []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            sizes.append(sim.household_final_sizes())
+            pairs.append(sim.household_sar(where, first_step, last_step))
+        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
+        return HouseholdResult.gathered(members, sizes, pairs, n_cols)
 
     def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may

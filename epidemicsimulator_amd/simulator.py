@@ -642,6 +642,45 @@ class Simulator:
         _lib.check(self.lib.esim_transmission_ages(self._ctx, int(first_step), last, out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
         return out
 
+    # -- household outbreaks (esim_household_outbreaks, esim_household_final_sizes, esim_household_sar) -------
+    def household_outbreaks(self):
+        """Per building, a dict of uint32 [n_buildings] arrays (esim_household_outbreaks): cases (the residents in the exposure
+        log, index cases included), introductions (of those, the index cases and the cases not infected at home) and first_step
+        (the smallest cohort step among them, _lib.NEVER without a case)."""
+        keys = ("cases", "introductions", "first_step")
+        out = {k: np.zeros(self.population.n_buildings, np.uint32) for k in keys}
+        _lib.check(self.lib.esim_household_outbreaks(self._ctx, *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in keys)), self._ctx)
+        return out
+
+    def household_final_sizes(self):
+        """(final_size, introductions), uint32 [64, 64] each (esim_household_final_sizes): entry [n, k] counts the households
+        of n residents with k cases, or with k introductions; the last bin of either index holds everything from 63 on.
+        Nothing per building or per citizen comes to the host."""
+        out = [np.zeros((_lib.HH_BINS, _lib.HH_BINS), np.uint32) for _ in range(2)]
+        _lib.check(self.lib.esim_household_final_sizes(self._ctx, *(a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out)), self._ctx)
+        return tuple(out)
+
+    def household_sar(self, where="all", first_step=0, last_step=None, complete=True):
+        """(at_risk, secondary), uint64 [n_cols, n_cols] each (esim_household_sar): over the cases of cohort steps first_step ..
+        last_step (step 0: the index cases), entry [g_case, g_contact] of at_risk counts the housemates still Susceptible when
+        the case became infectious, of secondary those it infected at home; secondary / at_risk is the household secondary
+        attack rate.  where: "all" (one cell) or "group".  last_step=None: the last step run.  complete=True clips last_step to
+        the last complete cohort -- last_step + exposed_time + 1 + infected_time <= the steps run -- and raises ValueError when
+        there is none; complete=False counts cohorts whose cases may still infect."""
+        place = {"all": _lib.BY_ALL, "group": _lib.BY_GROUP}.get(where, where)
+        n_cols = max(1, self._n_groups) if place == _lib.BY_GROUP else 1
+        first = int(first_step)
+        last = self._steps if last_step is None else int(last_step)
+        if complete:
+            done = self._steps - int(self.params.exposed_time) - 1 - int(self.params.infected_time)
+            last = min(last, done)
+            if last < max(first, 0):
+                raise ValueError("household_sar: no complete cohort in steps %d..%d after %d steps (complete=False counts the open ones)" % (first, last if last_step is None else int(last_step), self._steps))
+        at_risk, secondary = (np.zeros((n_cols, n_cols), np.uint64) for _ in range(2))
+        _lib.check(self.lib.esim_household_sar(self._ctx, int(place), first, last, at_risk.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               secondary.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
+        return at_risk, secondary
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

@@ -557,6 +557,53 @@ int  esim_transmission_chains(esim_ctx *ctx, uint32_t *lineage /* [n_citizens] o
 int  esim_outbreaks(esim_ctx *ctx, uint32_t *size, uint32_t *depth, uint32_t *last_step /* [cap] each, any may be NULL */,
                     uint32_t cap, uint32_t *n_out);
 int  esim_transmission_ages(esim_ctx *ctx, uint32_t first_step, uint32_t last_step, uint32_t *counts /* [ESIM_N_SETTINGS * ESIM_AGE_BINS] */);
+/* Household outbreaks: the household is the one setting with a fixed contact list, so the outputs above get a denominator there --
+ * the household SECONDARY ATTACK RATE (of the housemates still Susceptible when a case became infectious, the share that case
+ * infected at home) and the FINAL-SIZE distribution (how many households of size n ended with k cases, and how many of those
+ * were introduced from outside).  Computed on the device from the resident lists, the exposure log, the vaccination replay and
+ * the tree; nothing of size [n_citizens] goes to the host.  (The reference cannot give them: it records no infector.)  Settings,
+ * infectors and the tie rule are those of esim_exposure_settings and esim_transmission_tree, the seam of a rollback included.
+ *   household      a building with at least one resident (a citizen whose home_building it is); its size is their number.
+ *   case           a citizen in the exposure log, the index cases included.  Its cohort step te is its exposure step, 0 for an
+ *                  index case; onset = te + exposed_time + 1, 0 for an index case; its first infectious step f = max(onset, 1)
+ *                  -- the conventions of esim_reproduction_series and esim_transmission_ages.
+ *   at risk        housemate m != j of case j is at risk from j iff m is Susceptible after step f_j - 1 ("after step 0": the
+ *                  initial state; the state after a step includes that step's vaccinations, as in the area and group tables).
+ *                  With sus_until[m] the smaller of (exposure step of m) - 1 and (step at whose end m was set Vaccinated) - 1,
+ *                  whichever exist -- -1 for an index case, unbounded for a citizen never touched --: sus_until[m] >= f_j - 1.
+ *                  A case with f_j beyond the steps run has not become infectious and contributes nothing.
+ *   secondary case an at-risk housemate m of j with infector[m] == j and setting[m] == ESIM_SETTING_HOUSEHOLD.  Everybody that
+ *                  j infected at home is at risk from j by construction: secondary <= at_risk cell for cell.
+ *   per household  cases[b]: its residents that are cases; introductions[b]: of those, the index cases and the cases whose
+ *                  setting is not ESIM_SETTING_HOUSEHOLD (work place, school, transport, unexplained entries); first_step[b]:
+ *                  the smallest cohort step among its cases, ESIM_NEVER without one.  All 0 / ESIM_NEVER for a building
+ *                  nobody lives in.
+ * esim_household_outbreaks: the three per building, any may be NULL.
+ * esim_household_final_sizes: final_size[min(size, 63) * ESIM_HH_BINS + min(cases, 63)] counts the households, introductions[...]
+ *        the same with min(introductions, 63) as the second index; either may be NULL.  32 KB go to the host and nothing per
+ *        building or per citizen.
+ * esim_household_sar: the pairs (case j, housemate at risk from j) in at_risk, those that are secondary cases in secondary, over
+ *        the cases whose cohort step lies in [first_step, last_step] and that have become infectious (f_j <= the steps run).
+ *          where = ESIM_BY_ALL       one cell
+ *          where = ESIM_BY_GROUP     n_groups x n_groups, index g_case * n_groups + g_contact (ESIM_ESTATE without labels)
+ *        Any other `where` is ESIM_EINVAL.  first_step 0 is allowed, as for the reproduction rows, and brings in the index cases.
+ *        ESIM_ERANGE for last_step < first_step or last_step beyond the steps run.  Either output may be NULL, not both
+ *        (ESIM_EINVAL).  secondary / at_risk is the secondary attack rate.  A cohort is COMPLETE -- later steps add no secondary
+ *        case to it -- once the last Infected step of a citizen exposed in step last_step has run: last_step + exposed_time + 1 +
+ *        infected_time <= the steps run so far.  The counters are 64 bits wide, on the device too: a cell holds up to cases x
+ *        (household size - 1).
+ * esim_household_outbreaks and esim_household_final_sizes are refused as esim_exposure_settings is (ESIM_ESTATE before an upload,
+ * on a sharded context, on a history mixed twice), esim_household_sar as esim_transmission_tree is (also after a rollback under
+ * another bus_capacity).  The audits of those calls run too: ESIM_ESIM after delivering everything else; with all outputs NULL
+ * the first two still run theirs.  All three leave the simulation state, the records, the exposure log, the snapshot, the
+ * ensemble accumulators and the labels as they are.  Temporary device memory, freed when the call returns: that of
+ * esim_exposure_settings, 12 B per building and 32 KB for the two tables (the first two); that of esim_transmission_tree and
+ * 16 B per cell (esim_household_sar).  The work is one pass over the residents, or one walk over its household per case. */
+#define ESIM_HH_BINS 64
+int  esim_household_outbreaks(esim_ctx *ctx, uint32_t *cases, uint32_t *introductions, uint32_t *first_step /* [n_buildings] each, any may be NULL */);
+int  esim_household_final_sizes(esim_ctx *ctx, uint32_t *final_size /* [ESIM_HH_BINS * ESIM_HH_BINS] or NULL */, uint32_t *introductions /* same shape, or NULL */);
+int  esim_household_sar(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step,
+                        uint64_t *at_risk, uint64_t *secondary /* [n_cols * n_cols] each, either may be NULL, not both */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
