@@ -138,6 +138,13 @@ struct Tuning {
     uint32_t small_grid = 64, small_mult = 4;   // chunks with few Infected: workgroups of the marks / fold kernels, multiplier of the draw kernels (0: off)
     uint32_t draw_mult = 4, units_mult = 4;     // k_chunk_draw / k_chunk_units run this many times the marks grid: more, shorter wavefronts than the chip holds at once
     uint32_t small_max = 128;                   // infected-slice length up to which the persistent single-workgroup kernel runs a step
+    uint32_t pair_log2 = 0;                     // ESIM_PAIR_LOG2: the pair table of esim_area_flows / esim_lineage_areas has 1 << this many slots (0: sized by the log)
+};
+
+// What the pair engine (esim_host_flows.h) did in the last call that used it: esim_pair_stats.
+struct PairStats {
+    double ms[3] = { 0.0, 0.0, 0.0 };           // insert (the emptying of the table included), compact, sort (the read of the count included)
+    uint32_t distinct = 0, capacity = 0, dropped = 0;
 };
 
 struct esim_ctx_impl {
@@ -169,6 +176,7 @@ struct esim_ctx_impl {
     uint32_t rest_t = 0;                        // host_t for which pin.ctrl is known to hold the control block at rest (0: not known; esim_snapshot)
     uint64_t vax_chunk_steps = 0, vax_chunk_cuts = 0, vax_chunk_repairs = 0;
     Timing tm;
+    PairStats pair_stats;
     Comm comm;
     Pinned pin;
     RestartStaging rs;

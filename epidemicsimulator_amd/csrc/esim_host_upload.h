@@ -368,6 +368,8 @@ void upload_tuning(esim_ctx_impl *c, const UploadHost &u)
     if (const char *e = std::getenv("ESIM_DRAW_MULT")) t.draw_mult = (uint32_t)std::min(4, std::max(1, std::atoi(e)));      // (16 384 wavefronts at most: Dev::pair_cnt)
     if (const char *e = std::getenv("ESIM_UNITS_MULT")) t.units_mult = (uint32_t)std::min(16, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("ESIM_GRID_EXPOSE")) t.grid_expose = (uint32_t)std::max(1, std::atoi(e));
+    t.pair_log2 = 0u;
+    if (const char *e = std::getenv("ESIM_PAIR_LOG2")) t.pair_log2 = (uint32_t)std::min(31, std::max(6, std::atoi(e)));     // (at least 64 slots)
 }
 
 }  // namespace

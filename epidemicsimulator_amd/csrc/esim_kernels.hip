@@ -37,5 +37,6 @@
 #include "esim_kernels_tree.h"
 #include "esim_kernels_chains.h"
 #include "esim_kernels_household.h"
+#include "esim_kernels_flows.h"
 #include "esim_kernels_restart.h"
 #include "esim_kernels_snapshot.h"

@@ -193,6 +193,42 @@ class HouseholdResult:
                  at_risk=self.at_risk, secondary=self.secondary, sar=self.sar())
 
 
+class FlowResult:
+    """What Ensemble.flows gathers: the imports table and the invasion tree of every member, one row per member and one column
+    per Output Area."""
+
+    def __init__(self, members, local, imported, exported, step, source_area):
+        self.members = list(members)      # the overrides of every member
+        self.local = np.asarray(local, np.uint32)                    # uint32 [members, n_areas]: transmissions inside the area
+        self.imported = np.asarray(imported, np.uint32)              # ... into the area from elsewhere
+        self.exported = np.asarray(exported, np.uint32)              # ... out of the area
+        self.step = np.asarray(step, np.uint32)                      # cohort step of the area's first case, _lib.NEVER without one
+        self.source_area = np.asarray(source_area, np.uint32)        # the area it was infected from, _lib.NO_AREA for an index case or no case
+
+    @classmethod
+    def gathered(cls, members, imports, invasions, n_areas):
+        """From every member's Simulator.area_imports() and area_invasion() dicts."""
+        def stack(rows):
+            return np.stack(rows).astype(np.uint32) if rows else np.zeros((0, n_areas), np.uint32)
+        return cls(members, *(stack([t[k] for t in imports]) for k in ("local", "imported", "exported")),
+                   *(stack([t[k] for t in invasions]) for k in ("step", "source_area")))
+
+    def imported_share(self):
+        """float64 [n_areas]: of the area's infected residents whose infector is known, the share infected by a resident of
+        another area, pooled over the members -- the sum of imported divided by the sum of imported + local --, NaN where there
+        are no cases."""
+        imp = self.imported.sum(axis=0, dtype=np.uint64).astype(np.float64)
+        tot = imp + self.local.sum(axis=0, dtype=np.uint64).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tot > 0, imp / tot, np.nan)
+
+    def dump(self, directory):
+        """ensemble_flows.npz: local, imported, exported, step, source_area and the pooled imported_share."""
+        os.makedirs(directory, exist_ok=True)
+        np.savez(os.path.join(directory, "ensemble_flows.npz"), local=self.local, imported=self.imported, exported=self.exported,
+                 step=self.step, source_area=self.source_area, imported_share=self.imported_share())
+
+
 _KINDS = ("census", "arrival", "series")
 
 
@@ -342,6 +378,20 @@ class Ensemble:
             pairs.append(sim.household_sar(where, first_step, last_step))
         n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
         return HouseholdResult.gathered(members, sizes, pairs, n_cols)
+
+    def flows(self, members, n_steps, settings=None, first_step=1, last_step=None):
+        """How the epidemic travels, over an ensemble: every member (as for run()) is run for n_steps steps and its imports table
+        (Simulator.area_imports(settings, first_step, last_step)) and invasion tree (Simulator.area_invasion) gathered.  Returns a
+        FlowResult."""
+        sim = self.simulator
+        members = self._members(members)
+        imports, invasions = [], []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            imports.append(sim.area_imports(settings, first_step, last_step))
+            invasions.append(sim.area_invasion())
+        return FlowResult.gathered(members, imports, invasions, sim.population.n_areas)
 
     def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may

@@ -681,6 +681,63 @@ class Simulator:
                                                secondary.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
         return at_risk, secondary
 
+    # -- area flows (esim_area_flows, esim_area_imports, esim_area_invasion, esim_lineage_areas) -------
+    def _pairs(self, call, args):
+        """The three [n] arrays of a sparse output: one call with cap=0 for the number of pairs, then the real one -- two
+        replays, but buffers of 12 B per pair instead of 12 B per entry of the exposure log."""
+        n = C.c_uint32(0)
+        code = call(self._ctx, *args, None, None, None, 0, C.byref(n))
+        out = [np.zeros(n.value, np.uint32) for _ in range(3)]
+        if code == _lib.ESIM_ERANGE:      # buffers of n pairs are needed -- or the steps lie outside the run, which the second call says again
+            code = call(self._ctx, *args, *(a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out), n.value, C.byref(n))
+        _lib.check(code, self._ctx)
+        return tuple(out)
+
+    def area_flows(self, settings=None, first_step=1, last_step=None):
+        """(src, dst, count), uint32 [n_pairs] each (esim_area_flows): the distinct pairs (Output Area of the infector, of the
+        infectee) over the transmissions of steps first_step .. last_step (None: the last step run), restricted to `settings`
+        as setting_series takes them, ascending by (src, dst), and how many transmissions each pair saw.  Sized by one call with
+        cap=0 before the real one.  Nothing per citizen comes to the host."""
+        last = self._steps if last_step is None else int(last_step)
+        return self._pairs(self.lib.esim_area_flows, (self._setting_mask(settings), int(first_step), last))
+
+    def area_imports(self, settings=None, first_step=1, last_step=None):
+        """Per Output Area, a dict of uint32 [n_areas] arrays (esim_area_imports) over the same transmissions as area_flows:
+        local (both ends in the area), imported (the infectee lives there, the infector elsewhere) and exported (the other way
+        round)."""
+        keys = ("local", "imported", "exported")
+        out = {k: np.zeros(self.population.n_areas, np.uint32) for k in keys}
+        last = self._steps if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_area_imports(self._ctx, self._setting_mask(settings), int(first_step), last,
+                                              *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in keys)), self._ctx)
+        return out
+
+    def area_invasion(self):
+        """The between-area invasion tree, a dict of [n_areas] arrays (esim_area_invasion): first_case (the earliest case
+        living in the area, of several in one step the smallest citizen index; _lib.NO_INFECTOR without one), step (its cohort
+        step, 0 for an index case, _lib.NEVER without a case: area_arrival("home")), source_area (the area of its infector,
+        _lib.NO_AREA for an index case or no case) and setting (uint8, _lib.SETTING_NONE likewise).  step[source_area[a]] <
+        step[a] wherever a source exists: a forest rooted at the areas of the index cases."""
+        na = self.population.n_areas
+        out = {k: np.zeros(na, np.uint32) for k in ("first_case", "step", "source_area")}
+        out["setting"] = np.zeros(na, np.uint8)
+        _lib.check(self.lib.esim_area_invasion(self._ctx, *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in ("first_case", "step", "source_area")),
+                                               out["setting"].ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return out
+
+    def lineage_areas(self):
+        """(lineage, area, count), uint32 [n_pairs] each (esim_lineage_areas): the distinct pairs (position in seeds() of the
+        index case at the root of the chain, Output Area) over all cases that have a lineage, ascending, and how many cases of
+        that lineage live there.  np.bincount(lineage) is the number of areas every introduction reached."""
+        return self._pairs(self.lib.esim_lineage_areas, ())
+
+    def pair_stats(self):
+        """What the pair engine did in the last area_flows() / lineage_areas() call (esim_pair_stats): a dict of insert_ms,
+        compact_ms, sort_ms (device time, HIP events), distinct, capacity and dropped."""
+        ms, counts = (C.c_double * 3)(), (C.c_uint32 * 3)()
+        _lib.check(self.lib.esim_pair_stats(self._ctx, ms, counts), self._ctx)
+        return dict(insert_ms=ms[0], compact_ms=ms[1], sort_ms=ms[2], distinct=int(counts[0]), capacity=int(counts[1]), dropped=int(counts[2]))
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

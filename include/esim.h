@@ -604,6 +604,61 @@ int  esim_household_outbreaks(esim_ctx *ctx, uint32_t *cases, uint32_t *introduc
 int  esim_household_final_sizes(esim_ctx *ctx, uint32_t *final_size /* [ESIM_HH_BINS * ESIM_HH_BINS] or NULL */, uint32_t *introductions /* same shape, or NULL */);
 int  esim_household_sar(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step,
                         uint64_t *at_risk, uint64_t *secondary /* [n_cols * n_cols] each, either may be NULL, not both */);
+/* How the epidemic travels: which Output Area seeds which, how many of an area's cases were imported, and through which area and
+ * setting the epidemic first entered every area -- computed on the device from the tree, the lineage and the home area of every
+ * citizen, so that nothing of size [n_citizens] goes to the host.  (A dense [n_areas][n_areas] table would be 340 GB at the
+ * 290 000 areas of uk64m: the two sparse outputs are aggregated in a hash table, compacted and sorted on the device.)
+ *   area           of a citizen: the Output Area of its household, building_area[home_building].
+ *   transmission   an entry (c, ts) of the exposure log with ts >= 1 and infector[c] != ESIM_NO_INFECTOR; its step is ts, the
+ *                  infectee's.  Setting, infector, the tie rule and the seam of a rollback are those of esim_exposure_settings
+ *                  and esim_transmission_tree.  An exposure without a candidate is no transmission and is not counted.
+ *   case           a citizen in the exposure log, the index cases included; its cohort step is its exposure step, 0 for an index
+ *                  case -- the convention of esim_reproduction_series, esim_outbreaks and esim_household_outbreaks.
+ * esim_area_flows: the distinct pairs (area of the infector, area of the infectee) over the transmissions of steps [first_step,
+ *        last_step] whose setting is in setting_mask, ascending by (src, dst), every pair once; count[i] is the number of such
+ *        transmissions of pair i.  src, dst, count: [cap] each, any may be NULL.  *n_out receives the number of distinct pairs;
+ *        ESIM_ERANGE, with *n_out set, when cap is smaller (the rule of esim_outbreaks; nothing is delivered then, and a call
+ *        with cap 0 is the way to ask for the size); ESIM_EINVAL for a null n_out.  The mask is checked as esim_mixing_matrix
+ *        checks it, the steps as esim_offspring checks them.  12 B per distinct pair go to the host and nothing per citizen.
+ * esim_area_imports: over the same transmissions, local[a] those with both ends in a, imported[a] those with the infectee in a
+ *        and the infector elsewhere, exported[a] those with the infector in a and the infectee elsewhere.  [n_areas] each, any
+ *        may be NULL; with all three NULL the audits still run.  Mask and steps as above.  The diagonal of the flows is local,
+ *        the rest of row a sums to exported[a], the rest of column a to imported[a].
+ * esim_area_invasion: the between-area invasion tree.  first_case[a] is the case living in a with the smallest cohort step, of
+ *        several in that step the one with the smallest local citizen index (a stated contract, as the tie rule of the settings
+ *        is), ESIM_NO_INFECTOR for an area without a case; step[a] its cohort step, ESIM_NEVER without a case -- what
+ *        esim_area_arrival(ESIM_AREA_HOME) returns; source_area[a] the area of its infector, ESIM_NO_AREA for an index case, for
+ *        an area without a case and for an exposure without a candidate; setting[a] the setting of that transmission,
+ *        ESIM_SETTING_NONE likewise.  [n_areas] each, any may be NULL.  An infector was exposed at least exposed_time + 1 steps
+ *        before its infectee, and it is a case of its own area: step[source_area[a]] < step[a] wherever a source exists, no area
+ *        is its own source, and the result is a forest rooted at the areas an index case lives in.
+ * esim_lineage_areas: the distinct pairs (lineage ordinal, area) over all cases that have a lineage (esim_transmission_chains),
+ *        the index cases included, ascending; count[i] is the number of cases of that lineage living in that area.  cap and
+ *        n_out as for esim_area_flows.  The areas an introduction reached are the run lengths of `lineage`.
+ * The first three are refused as esim_transmission_tree is, esim_lineage_areas as esim_transmission_chains is: ESIM_ESTATE before
+ * an upload, on a sharded context, on a history mixed twice and after a rollback under another bus_capacity.  The audits of
+ * those calls run too: ESIM_ESIM after delivering everything else.  All four leave the simulation state, the records, the
+ * exposure log, the snapshot, the ensemble accumulators and the labels as they are.
+ * Temporary device memory, freed when the call returns: that of esim_transmission_tree (esim_lineage_areas: of
+ * esim_transmission_chains); 12 B per area (imports), 21 B per area (invasion); for the two sparse outputs a table of 12 B per
+ * slot -- the smallest power of two >= twice the entries of the exposure log, at least 64, so that it is never more than half
+ * full -- and a dense array of 12 B per entry of the log, rounded up to a power of two.  ESIM_PAIR_LOG2 in the environment (read
+ * when a population is uploaded) forces 1 << value slots instead; a table that cannot hold every distinct pair then makes the
+ * call ESIM_ENOMEM, with the knob and the number of keys dropped in esim_last_error.  The host reads the number of distinct
+ * pairs once in the middle of these two calls, to size the launches of the sort.
+ * esim_pair_stats: what the pair engine did in the last esim_area_flows or esim_lineage_areas of this context -- ms[0..2] the
+ *        device time of insert (the emptying of the table included), compact and sort (the read of the count included), from
+ *        HIP events; counts[0..2] the distinct pairs, the slots of the table and the keys dropped.  Either may be NULL. */
+#define ESIM_NO_AREA 0xFFFFFFFFu
+int  esim_area_flows(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
+                     uint32_t *src, uint32_t *dst, uint32_t *count /* [cap] each, any may be NULL */, uint32_t cap, uint32_t *n_out);
+int  esim_area_imports(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
+                       uint32_t *local, uint32_t *imported, uint32_t *exported /* [n_areas] each, any may be NULL */);
+int  esim_area_invasion(esim_ctx *ctx, uint32_t *first_case, uint32_t *step, uint32_t *source_area /* [n_areas] each, any may be NULL */,
+                        uint8_t *setting /* [n_areas] or NULL */);
+int  esim_lineage_areas(esim_ctx *ctx, uint32_t *lineage, uint32_t *area, uint32_t *count /* [cap] each, any may be NULL */,
+                        uint32_t cap, uint32_t *n_out);
+int  esim_pair_stats(esim_ctx *ctx, double *ms /* [3] or NULL */, uint32_t *counts /* [3] or NULL */);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
