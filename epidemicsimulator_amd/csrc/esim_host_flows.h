@@ -40,17 +40,26 @@ int pairs_begin(esim_ctx_impl *c, const std::string &who, PairWork *w, uint32_t 
     return ESIM_OK;
 }
 
-// Compact, the one read of the number of distinct pairs (the stream is waited for: the calls wait for it anyway), sort.  Leaves
-// w->n and w->dropped; the sorted pairs lie in w->out_key / w->out_cnt once the stream has been waited for again.
-int pairs_sorted(esim_ctx_impl *c, PairWork *w)
+// Compact -- every pair, or with min_count > 1 those counted at least that often --, and the one read of the number of pairs kept
+// (the stream is waited for: the calls wait for it anyway).  Leaves w->n and w->dropped.
+int pairs_compacted(esim_ctx_impl *c, PairWork *w, uint32_t min_count)
 {
     HIP_TRY(c, hipEventRecord(w->ev[1], c->stream));
-    hipLaunchKernelGGL(k_pairs_compact, dim3(grid_for(w->t.cap, PAIR_TPB, 4096)), dim3(PAIR_TPB), 0, c->stream, w->t, w->out_key.p, w->out_cnt.p, w->dense, w->counters.p);
+    const dim3 grid(grid_for(w->t.cap, PAIR_TPB, 4096)), block(PAIR_TPB);
+    if (min_count > 1u) hipLaunchKernelGGL(k_pairs_compact_min, grid, block, 0, c->stream, w->t, min_count, w->out_key.p, w->out_cnt.p, w->dense, w->counters.p);
+    else hipLaunchKernelGGL(k_pairs_compact, grid, block, 0, c->stream, w->t, w->out_key.p, w->out_cnt.p, w->dense, w->counters.p);
     HIP_TRY(c, hipEventRecord(w->ev[2], c->stream));
     uint32_t h[2] = { 0u, 0u };
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(h, w->counters.p, sizeof h, hipMemcpyDeviceToHost));
     w->n = std::min(h[0], w->dense); w->dropped = h[1];
+    return ESIM_OK;
+}
+
+// Compact, read, sort.  The sorted pairs lie in w->out_key / w->out_cnt once the stream has been waited for again.
+int pairs_sorted(esim_ctx_impl *c, PairWork *w)
+{
+    if (int rc = pairs_compacted(c, w, 1u)) return rc;
     pairs_sort_enqueue(w->out_key.p, w->out_cnt.p, pair_pow2(w->n), c->stream);
     HIP_TRY(c, hipEventRecord(w->ev[3], c->stream));
     return ESIM_OK;

@@ -15,19 +15,20 @@ int tree_check(esim_ctx_impl *c, const std::string &who)
 
 struct TreeWork {
     SettingWork s;
-    DevTmp<uint32_t> infector, n_cand, gen, queue, counters;
+    DevTmp<uint32_t> infector, n_cand, gen, queue, counters, bus;
     Tree t;
 };
 
 // The settings, then the tree: infector and candidates per citizen (households in place, the rest through the queue and the wide
-// kernel) and, where asked for, the generations, a launch per window of exposed_time + 1 steps.
-int tree_enqueue(esim_ctx_impl *c, const std::string &who, TreeWork *w, bool generations)
+// kernel) and, where asked for, the generations, a launch per window of exposed_time + 1 steps; with `buses` the bus number of
+// every transport exposure too (esim_transmission_events), 4 B per citizen more.
+int tree_enqueue(esim_ctx_impl *c, const std::string &who, TreeWork *w, bool generations, bool buses = false)
 {
     if (int rc = settings_enqueue(c, who, &w->s)) return rc;
     const Dev &d = c->d;
     const uint32_t log_len = w->s.log_len, t_done = w->s.q.t_done;
     if (w->infector.alloc(d.n) != hipSuccess || w->n_cand.alloc(d.n) != hipSuccess || w->gen.alloc(d.n) != hipSuccess || w->queue.alloc(log_len) != hipSuccess ||
-        w->counters.alloc(3) != hipSuccess) {
+        w->counters.alloc(3) != hipSuccess || (buses && w->bus.alloc(d.n) != hipSuccess)) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(c->stream);                         // (the settings' kernels still read the host vectors of w->s)
         return fail(c, ESIM_ENOMEM, who + ": no device memory for the tree (12 B per citizen and 4 B per entry of the exposure log)");
@@ -35,7 +36,9 @@ int tree_enqueue(esim_ctx_impl *c, const std::string &who, TreeWork *w, bool gen
     Tree &t = w->t;
     t.infector = w->infector.p; t.n_cand = w->n_cand.p; t.gen = w->gen.p; t.queue = w->queue.p; t.q_cap = log_len;
     t.n_queue = w->counters.p; t.n_long = w->counters.p + 1; t.orphans = w->counters.p + 2;
-    const hipError_t e = hipMemsetAsync(w->counters.p, 0, 3 * sizeof(uint32_t), c->stream);
+    t.bus = buses ? w->bus.p : nullptr;
+    hipError_t e = hipMemsetAsync(w->counters.p, 0, 3 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess && buses) e = hipMemsetAsync(w->bus.p, 0, sizeof(uint32_t) * std::max<size_t>(1, d.n), c->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
     hipLaunchKernelGGL(k_tree_home, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);
     hipLaunchKernelGGL(k_tree_wide, dim3(grid_for(log_len, TPB / 64u, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);

@@ -157,6 +157,13 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     d.n = N; d.n_global = u.n_global; d.id_base = pop->citizen_id_base; d.n_bld = B; d.n_room = R;
     d.n_pt = (uint32_t)u.riders.size(); d.n_routes = u.n_routes; c->n_routes = u.n_routes;
     d.max_route = u.max_route;
+    c->route_tab.assign(3 * (size_t)u.n_routes, 0u);
+    for (uint32_t r = 0; r < u.n_routes; ++r) {
+        const uint32_t first = u.riders[u.route_off[r]];             // (every route has a rider)
+        c->route_tab[r] = pop->building_area[pop->home_building[first]];
+        c->route_tab[u.n_routes + r] = pop->building_area[pop->work_building[first]];
+        c->route_tab[2 * (size_t)u.n_routes + r] = u.route_off[r + 1] - u.route_off[r];
+    }
     int rc;
     if ((rc = dev_alloc(c, &d.cit, (size_t)N + 1))) return rc;
     if ((rc = dev_upload(c, &d.home, pop->home_building, N)) || (rc = dev_upload(c, &d.work, pop->work_building, N))) return rc;

@@ -38,5 +38,6 @@
 #include "esim_kernels_chains.h"
 #include "esim_kernels_household.h"
 #include "esim_kernels_flows.h"
+#include "esim_kernels_events.h"
 #include "esim_kernels_restart.h"
 #include "esim_kernels_snapshot.h"

@@ -19,6 +19,7 @@ struct Tree {
     uint32_t q_cap;                      // (a route longer than a bus) from the back
     uint32_t *n_queue, *n_long;          // entries at the front, at the back
     uint32_t *orphans;                   // exposures without a candidate
+    uint32_t *bus = nullptr;             // [n] zeroed by the caller, or nullptr: the bus number of an exposure on a route longer than a bus
 };
 
 // The seed an exposure of step ts was drawn under: the snapshot's up to the seam of a rollback.
@@ -238,13 +239,14 @@ __device__ __forceinline__ uint32_t tree_route_take(const Dev &d, const TreeShar
 // A route longer than a bus: the Infected riders of c's bus.  With more than TREE_QCAP Infected on the route they are ranked in
 // rounds, once to count and once more up to the round that holds the pick.
 __device__ __forceinline__ uint32_t tree_route_long(const Dev &d, const Setting &q, TreeShared &sm, uint32_t off, uint32_t sz, uint32_t c, int ts,
-                                                    uint32_t lane, uint32_t *k_out)
+                                                    uint32_t lane, uint32_t *k_out, uint32_t *bus_out)
 {
     const uint64_t seed = tree_seed(d, q, ts);
     const bool keep = sz <= CHUNK_ROUTE_MAX;
     uint32_t front = 0u, k = 0u;
     const uint32_t n_inf = tree_route_scan(d, q, sm, off, sz, c, ts, seed, keep, 0u, lane, &front);
     const uint32_t bus = front / d.bus_capacity;
+    *bus_out = bus;
     for (uint32_t q_lo = 0u; q_lo < n_inf; q_lo += TREE_QCAP) {
         if (q_lo) (void)tree_route_scan(d, q, sm, off, sz, c, ts, seed, keep, q_lo, lane, &front);
         k += tree_route_rank(d, sm, off, sz, ts, seed, keep, n_inf - q_lo < TREE_QCAP ? n_inf - q_lo : TREE_QCAP, bus, lane);
@@ -318,11 +320,12 @@ __global__ __launch_bounds__(64) void k_tree_route(Dev d, Setting q, Tree t)
         const int ts = (int)te - (int)TE_BIAS;
         if (te == SETTING_TE_NONE || ts < 1 || ts > (int)q.t_done || r >= d.n_routes) continue;
         const uint32_t off = d.route_off[r], end = d.route_off[r + 1u];
-        uint32_t who = ESIM_NO_INFECTOR, k = 0u;
-        if (off <= end && end <= d.n_pt && end - off > d.bus_capacity) who = tree_route_long(d, q, sm, off, end - off, c, ts, lane, &k);
+        uint32_t who = ESIM_NO_INFECTOR, k = 0u, bus = 0u;
+        if (off <= end && end <= d.n_pt && end - off > d.bus_capacity) who = tree_route_long(d, q, sm, off, end - off, c, ts, lane, &k, &bus);
         if (lane == 0u) {
             t.infector[c] = who;
             t.n_cand[c] = k;
+            if (t.bus) t.bus[c] = bus;
             if (!k) atomicAdd(t.orphans, 1u);
         }
         __syncthreads();

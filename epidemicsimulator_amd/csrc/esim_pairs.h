@@ -6,6 +6,7 @@
 //            atomicAdd counts.  A key that finds no slot bumps *overflow and is dropped: the loop cannot spin.
 //   compact  k_pairs_compact, a lane per slot: the occupied slots of a wavefront are counted with one ballot and reserved with
 //            one atomic, and their (key, count) pairs go to a dense array -- in the order the wavefronts happened to arrive.
+//            k_pairs_compact_min keeps only the slots that count at least min_count.
 //   sort     ascending by key, which makes the output canonical.  Keys are unique after aggregation, so a bitonic network is
 //            enough and stability does not arise.  The dense array is padded to a power of two with PAIR_EMPTY, which sorts
 //            last.  k_pairs_sort_tile runs every step whose stride fits a tile of PAIR_SORT_TILE pairs in LDS,
@@ -73,6 +74,28 @@ __global__ __launch_bounds__(PAIR_TPB) void k_pairs_compact(PairTable t, unsigne
         base = __shfl(base, lead, 64);
         const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         if (full && at < out_cap) { out_key[at] = k; out_cnt[at] = t.cnt[s]; }
+    }
+}
+
+// The same for the slots that count at least min_count (>= 1): a caller that wants only the keys seen several times keeps the
+// dense array, and the sort behind it, as small as they are.  min_count 1 delivers what k_pairs_compact does.
+__global__ __launch_bounds__(PAIR_TPB) void k_pairs_compact_min(PairTable t, uint32_t min_count, unsigned long long *out_key, uint32_t *out_cnt, uint32_t out_cap,
+                                                                uint32_t *n_out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t s0 = (uint64_t)blockIdx.x * PAIR_TPB; s0 < (uint64_t)t.cap; s0 += (uint64_t)gridDim.x * PAIR_TPB) {
+        const uint64_t s = s0 + threadIdx.x;
+        const unsigned long long k = s < (uint64_t)t.cap ? t.key[s] : PAIR_EMPTY;
+        const uint32_t n = k != PAIR_EMPTY ? t.cnt[s] : 0u;
+        const bool full = k != PAIR_EMPTY && n >= min_count;
+        const unsigned long long m = __ballot(full);
+        if (!m) continue;
+        const uint32_t lead = (uint32_t)__ffsll((long long)m) - 1u;
+        uint32_t base = 0u;
+        if (lane == lead) base = atomicAdd(n_out, (uint32_t)__popcll(m));
+        base = __shfl(base, lead, 64);
+        const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (full && at < out_cap) { out_key[at] = k; out_cnt[at] = n; }
     }
 }
 

@@ -229,6 +229,45 @@ class FlowResult:
                  step=self.step, source_area=self.source_area, imported_share=self.imported_share())
 
 
+class EventResult:
+    """What Ensemble.events gathers: the event-size table of every member and its `top` largest events, one row per member."""
+
+    KEYS = ("step", "setting", "place", "bus", "size")
+
+    def __init__(self, members, sizes, step, setting, place, bus, size):
+        self.members = list(members)      # the overrides of every member
+        self.sizes = np.asarray(sizes, np.uint32)                    # uint32 [members, 4, 256]: events per setting and size, the last bin open-ended
+        self.step = np.asarray(step, np.uint32)                      # [members, top] each, descending by size; _lib.NEVER behind a member's last event
+        self.setting = np.asarray(setting, np.uint32)
+        self.place = np.asarray(place, np.uint32)
+        self.bus = np.asarray(bus, np.uint32)
+        self.size = np.asarray(size, np.uint32)
+
+    @classmethod
+    def gathered(cls, members, sizes, tops, top):
+        """From every member's Simulator.event_sizes() table and Simulator.transmission_events(order="size", limit=top) dict."""
+        table = np.stack(sizes).astype(np.uint32) if sizes else np.zeros((0, _lib.N_SETTINGS, _lib.EVENT_BINS), np.uint32)
+        rows = {k: np.full((len(tops), int(top)), _lib.NEVER, np.uint32) for k in cls.KEYS}
+        for i, t in enumerate(tops):
+            for k in cls.KEYS:
+                rows[k][i, :len(t[k])] = t[k]
+        return cls(members, table, *(rows[k] for k in cls.KEYS))
+
+    def share_in_events(self, min_size):
+        """float64 [members, 4]: of the transmissions of a member in a setting, the share that took place in events of at least
+        min_size transmissions, NaN without a transmission.  Exact while the last bin is empty: an event there counts as 255."""
+        b = np.arange(_lib.EVENT_BINS, dtype=np.float64)
+        weight = self.sizes.astype(np.float64) * b
+        tot, big = weight.sum(axis=2), weight[:, :, min(int(min_size), _lib.EVENT_BINS):].sum(axis=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(tot > 0, big / tot, np.nan)
+
+    def dump(self, directory):
+        """ensemble_events.npz: sizes and the five [members, top] arrays of the largest events."""
+        os.makedirs(directory, exist_ok=True)
+        np.savez(os.path.join(directory, "ensemble_events.npz"), sizes=self.sizes, **{k: getattr(self, k) for k in self.KEYS})
+
+
 _KINDS = ("census", "arrival", "series")
 
 
@@ -392,6 +431,20 @@ class Ensemble:
             imports.append(sim.area_imports(settings, first_step, last_step))
             invasions.append(sim.area_invasion())
         return FlowResult.gathered(members, imports, invasions, sim.population.n_areas)
+
+    def events(self, members, n_steps, settings=None, first_step=1, last_step=None, top=16):
+        """Superspreading events over an ensemble: every member (as for run()) is run for n_steps steps and its event-size table
+        (Simulator.event_sizes(settings, first_step, last_step)) and its `top` largest events
+        (Simulator.transmission_events(..., order="size", limit=top)) gathered.  Returns an EventResult."""
+        sim = self.simulator
+        members = self._members(members)
+        sizes, tops = [], []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            sizes.append(sim.event_sizes(settings, first_step, last_step))
+            tops.append(sim.transmission_events(settings, first_step, last_step, order="size", limit=top))
+        return EventResult.gathered(members, sizes, tops, top)
 
     def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may

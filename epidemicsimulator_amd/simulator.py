@@ -738,6 +738,66 @@ class Simulator:
         _lib.check(self.lib.esim_pair_stats(self._ctx, ms, counts), self._ctx)
         return dict(insert_ms=ms[0], compact_ms=ms[1], sort_ms=ms[2], distinct=int(counts[0]), capacity=int(counts[1]), dropped=int(counts[2]))
 
+    # -- superspreading events (esim_transmission_events, esim_routes) -------
+    _EVENT_KEYS = ("step", "setting", "place", "bus", "size")
+
+    def _events(self, mask, first, last, min_size, order, out, cap, sizes=None):
+        """One esim_transmission_events call into the arrays of `out` (None: no lists): (code, number of events)."""
+        n = C.c_uint32(0)
+        ptrs = [None] * 5 if out is None else [out[k].ctypes.data_as(C.POINTER(C.c_uint8 if k == "setting" else C.c_uint32)) for k in self._EVENT_KEYS]
+        code = self.lib.esim_transmission_events(self._ctx, mask, first, last, int(min_size), int(order), *ptrs, int(cap), C.byref(n),
+                                                 None if sizes is None else sizes.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return code, n.value
+
+    def transmission_events(self, settings=None, first_step=1, last_step=None, min_size=1, order="key", limit=None):
+        """The superspreading events (esim_transmission_events), a dict of [n_events] arrays: step, setting (uint8), place (the
+        building, the room, or the position of the route in routes()), bus (0 off public transport) and size -- the
+        transmissions of one step in one gathering (household, work place, school room, bus), over steps first_step ..
+        last_step (None: the last step run), restricted to `settings` as setting_series takes them, events of at least
+        min_size transmissions only.  order="key": ascending by (step, setting, place, bus), sized by one call with cap=0 before
+        the real one; order="size": descending by size, ties ascending by that key, the first `limit` of them (None: all, sized
+        the same way) in one call.  Nothing per citizen comes to the host."""
+        if order not in ("key", "size"):
+            raise ValueError("transmission_events: order must be 'key' or 'size', got %r" % (order,))
+        mask, first = self._setting_mask(settings), int(first_step)
+        last = self._steps if last_step is None else int(last_step)
+        by = _lib.EVENTS_BY_SIZE if order == "size" else _lib.EVENTS_BY_KEY
+
+        def arrays(n):
+            return {k: np.zeros(n, np.uint8 if k == "setting" else np.uint32) for k in self._EVENT_KEYS}
+        if order == "size" and limit is not None:
+            out = arrays(int(limit))
+            code, n = self._events(mask, first, last, min_size, by, out, int(limit))
+            _lib.check(code, self._ctx)
+            return {k: v[:min(n, int(limit))] for k, v in out.items()}
+        code, n = self._events(mask, first, last, min_size, _lib.EVENTS_BY_KEY, None, 0)
+        out = arrays(n)
+        if code == _lib.ESIM_ERANGE:      # buffers of n events are needed -- or the steps lie outside the run, which the second call says again
+            code, n = self._events(mask, first, last, min_size, by, out, n)
+        _lib.check(code, self._ctx)
+        return out
+
+    def event_sizes(self, settings=None, first_step=1, last_step=None):
+        """uint32 [4, 256] (the size table of esim_transmission_events): entry [s, b] counts the events of setting s with b
+        transmissions over the window and the settings, the last bin open-ended; no list is built or sorted."""
+        sizes = np.zeros((_lib.N_SETTINGS, _lib.EVENT_BINS), np.uint32)
+        last = self._steps if last_step is None else int(last_step)
+        code, _ = self._events(self._setting_mask(settings), int(first_step), last, 1, _lib.EVENTS_BY_SIZE, None, 0, sizes)
+        _lib.check(code, self._ctx)
+        return sizes
+
+    def routes(self):
+        """The public transport routes (esim_routes), a dict of uint32 [n_routes] arrays: home_area, work_area and n_riders, in
+        the order transmission_events numbers them (ascending by home area, then work area)."""
+        n = C.c_uint32(0)
+        code = self.lib.esim_routes(self._ctx, None, None, None, 0, C.byref(n))
+        keys = ("home_area", "work_area", "n_riders")
+        out = {k: np.zeros(n.value, np.uint32) for k in keys}
+        if code == _lib.ESIM_ERANGE:
+            code = self.lib.esim_routes(self._ctx, *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in keys), n.value, C.byref(n))
+        _lib.check(code, self._ctx)
+        return out
+
     def enable_kernel_timing(self, stride):
         _lib.check(self.lib.esim_enable_kernel_timing(self._ctx, int(stride)), self._ctx)
 

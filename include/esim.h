@@ -659,6 +659,43 @@ int  esim_area_invasion(esim_ctx *ctx, uint32_t *first_case, uint32_t *step, uin
 int  esim_lineage_areas(esim_ctx *ctx, uint32_t *lineage, uint32_t *area, uint32_t *count /* [cap] each, any may be NULL */,
                         uint32_t cap, uint32_t *n_out);
 int  esim_pair_stats(esim_ctx *ctx, double *ms /* [3] or NULL */, uint32_t *counts /* [3] or NULL */);
+/* Superspreading events: which gatherings drove the epidemic.  The exposure rule is per gathering -- 1 - (1 - p)^n over the n
+ * Infected standing in one place in one step --, so the unit is the (place, step) event.
+ *   transmission   as for esim_area_flows: a log entry (c, ts) with ts >= 1, a setting in the mask and an infector.
+ *   gathering      the member list esim_transmission_tree walks for the candidates of c: the home building (household), the work
+ *                  building (work place), c's own room (school; the index of esim_population.room), c's bus (public transport):
+ *                  (route, bus number).  A route is named by its ordinal among the distinct (home area, work area) pairs that
+ *                  have a rider, ascending by home area, then work area (esim_routes); the bus number is the rider's rank in
+ *                  that step's order of the route / bus_capacity, and 0 on a route of at most bus_capacity riders.
+ *   event          the transmissions of one step in one gathering; its size is their number.  An entry whose place cannot be
+ *                  formed (an index outside the tables) is not counted.
+ * esim_transmission_events: over the transmissions of steps [first_step, last_step] whose setting is in setting_mask,
+ *        sizes[s * ESIM_EVENT_BINS + min(size, ESIM_EVENT_BINS - 1)] counts ALL events of setting s, whatever min_size is (bin 0
+ *        stays 0; the sum over b of b * sizes[s][b] is the number of transmissions of s unless the last bin is occupied), and
+ *        *n_out receives the number of events with size >= min_size (>= 1; 0 is ESIM_EINVAL).  They are listed in step[],
+ *        setting[], place[] (building, room or route ordinal), bus[] (0 off public transport) and size[], [cap] each, any may be
+ *        NULL:
+ *          ESIM_EVENTS_BY_KEY   ascending by (step, setting, place, bus); ESIM_ERANGE, with *n_out set and no list delivered,
+ *                               when cap is smaller than *n_out (the rule of esim_area_flows; cap 0 asks for the size);
+ *          ESIM_EVENTS_BY_SIZE  descending by size, ties ascending by that key; the first min(cap, *n_out) are delivered and a
+ *                               smaller cap is no error: the top-K list.
+ *        With every list pointer NULL nothing is sorted; with sizes NULL too the audits still run.  ESIM_EINVAL for a null n_out
+ *        or an unknown order; mask and steps are checked as esim_area_flows checks them, ESIM_ERANGE after more than 2^30 steps.
+ *        Refusals and audits are those of esim_transmission_tree (ESIM_ESIM after delivering everything else).  The simulation
+ *        state, the records, the exposure log, the snapshot, the ensemble accumulators and the labels stay as they are, and
+ *        nothing is kept between calls.  Temporary device memory: that of esim_transmission_tree and 4 B per citizen for the
+ *        buses, the pair table and dense array of esim_area_flows (ESIM_PAIR_LOG2 holds here too), 4 KB for the size table,
+ *        17 B per event delivered and, by size, 12 B per event of the list.  esim_pair_stats reports this call too: the sort
+ *        time includes the second sort and the split into arrays.
+ * esim_routes: the route table, 12 B per route and nothing per citizen: home_area[r], work_area[r], n_riders[r], [cap] each, any
+ *        may be NULL.  *n_out receives the number of routes; ESIM_ERANGE, with *n_out set, when cap is smaller (the rule of
+ *        esim_get_seeds); ESIM_EINVAL for a null n_out, ESIM_ESTATE before an upload. */
+#define ESIM_EVENT_BINS 256
+enum { ESIM_EVENTS_BY_KEY = 0, ESIM_EVENTS_BY_SIZE = 1 };
+int  esim_transmission_events(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step, uint32_t min_size, int order,
+                              uint32_t *step, uint8_t *setting, uint32_t *place, uint32_t *bus, uint32_t *size /* [cap] each, any may be NULL */,
+                              uint32_t cap, uint32_t *n_out, uint32_t *sizes /* [ESIM_N_SETTINGS * ESIM_EVENT_BINS] or NULL */);
+int  esim_routes(esim_ctx *ctx, uint32_t *home_area, uint32_t *work_area, uint32_t *n_riders /* [cap] each, any may be NULL */, uint32_t cap, uint32_t *n_out);
 /* Checkpoint / resume (the reference has none for the simulation state): everything a step reads that is
  * not part of the uploaded population -- the citizen words, the census histogram, the exposure log, the control block,
  * the records so far.  Restore goes into a context that holds the SAME population (or shard) and parameters; the run
