@@ -23,6 +23,7 @@
 #include "esim_host_outputs.h"
 #include "esim_host_settings.h"
 #include "esim_host_tree.h"
+#include "esim_host_ensrows.h"
 #include "esim_host_household.h"
 #include "esim_host_flows.h"
 #include "esim_host_events.h"

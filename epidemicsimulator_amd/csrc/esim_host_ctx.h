@@ -80,12 +80,21 @@ struct Ensemble {
     // writes a member's rows into and the engine's small temporaries -- all kept from the begin on, so that a fold allocates
     // nothing proportional to rows x columns (the 4 B per citizen of the vaccination replay: at the first fold that needs them).
     // series == true: this kind is in force (where, n and valid as for the other two).
+    // esim_ensemble_begin_settings and esim_ensemble_begin_reproduction (esim_host_ensrows.h) are kinds of the same family:
+    // rows.kind tells them apart.  The settings kind keeps hit, sum, sumsq and plane 0 only; the reproduction kind keeps hit,
+    // sum and sumsq for the cases, both planes (cases, offspring) and the four accumulators below.
+    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2 };
     struct Rows {
         uint32_t *hit = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
         unsigned long long *sum = nullptr, *sumsq = nullptr;
         uint8_t *aw = nullptr;
         int what = 0; uint32_t first = 0, n_rows = 0, stride = 0, min = 0, n_cols = 0;
-        bool two = false;                         // p1 is allocated: status rows by the area stood in
+        bool two = false;                         // p1 is allocated: status rows by the area stood in, or the offspring plane
+        int kind = ROWS_SERIES;
+        uint32_t mask = 0;                        // ROWS_SETTINGS: the setting mask
+        uint32_t r_num = 0, r_den = 0;            // ROWS_REPRODUCTION: hit where offspring / cases >= r_num / r_den (min: the smallest cohort)
+        uint32_t *defined = nullptr;              // ROWS_REPRODUCTION: members with a cohort in the cell
+        unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
     } rows;
     bool series = false;
 };

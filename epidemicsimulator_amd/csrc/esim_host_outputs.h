@@ -302,7 +302,8 @@ SeriesSpec fold_spec(int where, int what)
 // The accumulators and kept buffers of a series kind back to the device (nothing may still be using them).
 void rows_free(esim_ctx_impl *c, Ensemble::Rows *r)
 {
-    for (void *q : { (void *)r->hit, (void *)r->members, (void *)r->p0, (void *)r->p1, (void *)r->occ, (void *)r->vax, (void *)r->sum, (void *)r->sumsq, (void *)r->aw }) dev_free(c, q);
+    for (void *q : { (void *)r->hit, (void *)r->members, (void *)r->p0, (void *)r->p1, (void *)r->occ, (void *)r->vax, (void *)r->sum, (void *)r->sumsq, (void *)r->aw,
+                     (void *)r->defined, (void *)r->sum_o, (void *)r->sumsq_o, (void *)r->cross }) dev_free(c, q);
     *r = Ensemble::Rows();
 }
 
@@ -327,6 +328,8 @@ int fold_series(esim_ctx_impl *c)
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
+
+int fold_transmission(esim_ctx_impl *c);   // (esim_host_ensrows.h: the settings and the reproduction kind)
 }  // namespace
 
 extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
@@ -383,7 +386,7 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (!c->uploaded || !c->ens.valid || !(c->ens.series ? c->ens.rows.hit : c->ens.hit))
         return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
-    if (c->ens.series) return fold_series(c);
+    if (c->ens.series) return c->ens.rows.kind == Ensemble::ROWS_SERIES ? fold_series(c) : fold_transmission(c);
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;
     const bool by_group = c->ens.where == ESIM_BY_GROUP;
@@ -405,7 +408,7 @@ extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hi
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (c->uploaded && c->ens.valid && c->ens.series)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read: the accumulators in force were begun by esim_ensemble_begin_series (read them with esim_ensemble_read_series)");
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read: the accumulators in force were begun over rows (read them with esim_ensemble_read_series, or with esim_ensemble_read_reproduction those of esim_ensemble_begin_reproduction)");
     if (!c->uploaded || !c->ens.hit || !c->ens.valid)
         return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
@@ -435,7 +438,7 @@ extern "C" int esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, ui
     const bool two = s.key == KEY_STOOD && s.what != SERIES_EVENTS;
     const size_t cells = (size_t)n_rows * cols;
     Ensemble::Rows &old = c->ens.rows;
-    if (!old.hit || old.n_rows != n_rows || old.n_cols != cols || old.two != two) {
+    if (!old.hit || old.kind != Ensemble::ROWS_SERIES || old.n_rows != n_rows || old.n_cols != cols || old.two != two) {
         // another shape: the new one is allocated before the old one goes, so that a refusal leaves everything as it was
         Ensemble::Rows r;
         int rc;
@@ -453,7 +456,7 @@ extern "C" int esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, ui
         old = r;
     }
     Ensemble::Rows &r = c->ens.rows;
-    r.what = what; r.first = first_step; r.n_rows = n_rows; r.stride = stride; r.min = min_cases; r.n_cols = cols; r.two = two;
+    r.kind = Ensemble::ROWS_SERIES; r.what = what; r.first = first_step; r.n_rows = n_rows; r.stride = stride; r.min = min_cases; r.n_cols = cols; r.two = two;
     HIP_TRY(c, hipMemsetAsync(r.hit, 0, sizeof(uint32_t) * cells, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.sum, 0, sizeof(unsigned long long) * cells, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.sumsq, 0, sizeof(unsigned long long) * cells, c->stream));
@@ -466,8 +469,10 @@ extern "C" int esim_ensemble_read_series(esim_ctx *ctx, uint32_t first_row, uint
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: no population uploaded, or no esim_ensemble_begin_series in force since the upload (or, by group, since esim_set_groups)");
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: no population uploaded, or no esim_ensemble_begin_series or esim_ensemble_begin_settings in force since the upload (or, by group, since esim_set_groups)");
     const Ensemble::Rows &r = c->ens.rows;
+    if (r.kind == Ensemble::ROWS_REPRODUCTION)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_reproduction (read them with esim_ensemble_read_reproduction)");
     if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, "esim_ensemble_read_series: rows outside the accumulators");
     HIP_TRY(c, hipSetDevice(c->P.device));
     Ctrl h; int rc;

@@ -1,6 +1,6 @@
 // esim_kernels_restart.h -- ensembles on one uploaded population: the initial state rebuilt on the device (esim_restart)
 // and the per-Output-Area accumulators over the members of an ensemble (esim_ensemble_fold), by census, by arrival step or
-// over the rows of a series.
+// over the rows of a series, of the exposures by setting or of the cohort reproduction rows.
 // No stepping kernel is here.
 #pragma once
 
@@ -106,5 +106,76 @@ __global__ __launch_bounds__(TPB) void k_ensemble_fold_rows(const uint32_t *x, u
         const uint32_t v = x[tail];
         if (v >= min_cases) hit[tail] += 1u;
         if (v) { sum[tail] += v; sumsq[tail] += (unsigned long long)v * v; }
+    }
+}
+
+// The accumulators of esim_ensemble_begin_reproduction, [cells] each but the member counter: two counters and five sums a cell.
+struct RatioAcc {
+    uint32_t *defined, *hit, *members;
+    unsigned long long *sum_c, *sum_o, *sq_c, *sq_o, *cross;
+};
+
+// hit of one cell with a cohort: offspring / cases >= r_num / r_den, in integers (both products fit 64 bits).
+__device__ __forceinline__ uint32_t ratio_hit(uint32_t c, uint32_t o, uint32_t r_num, uint32_t r_den)
+{
+    return (unsigned long long)o * r_den >= (unsigned long long)c * r_num;
+}
+
+// The five sums of cells 2 * j and 2 * j + 1, 16 bytes each way.
+__device__ __forceinline__ void ratio_pair(const RatioAcc &a, uint64_t j, uint32_t c0, uint32_t c1, uint32_t o0, uint32_t o1)
+{
+    ulonglong2 *sc = reinterpret_cast<ulonglong2 *>(a.sum_c) + j, *so = reinterpret_cast<ulonglong2 *>(a.sum_o) + j;
+    ulonglong2 *qc = reinterpret_cast<ulonglong2 *>(a.sq_c) + j, *qo = reinterpret_cast<ulonglong2 *>(a.sq_o) + j, *x = reinterpret_cast<ulonglong2 *>(a.cross) + j;
+    ulonglong2 vsc = *sc, vso = *so, vqc = *qc, vqo = *qo, vx = *x;
+    vsc.x += c0; vsc.y += c1; vso.x += o0; vso.y += o1;
+    vqc.x += (unsigned long long)c0 * c0; vqc.y += (unsigned long long)c1 * c1;
+    vqo.x += (unsigned long long)o0 * o0; vqo.y += (unsigned long long)o1 * o1;
+    vx.x += (unsigned long long)c0 * o0; vx.y += (unsigned long long)c1 * o1;
+    *sc = vsc; *so = vso; *qc = vqc; *qo = vqo; *x = vx;
+}
+
+// The same over the cohort rows (esim_ensemble_begin_reproduction): c[cell] and o[cell] are the cases and the offspring
+// k_tree_rows has just left in the two kept planes.  Per cell: defined += (c >= min_cohort), min_cohort >= 1; hit += 1 where
+// that holds and o / c >= r_num / r_den; the five sums always.  The shape of k_ensemble_fold_rows: a lane owns its cells (plain
+// loads and stores), four cells per lane and trip, 16-byte loads of both planes and of defined and hit, 16-byte loads and stores
+// of the sums, two cells each; a grid capped by the caller strides over the rest, and the up to three cells behind the last
+// whole four are taken by the first lanes of workgroup 0.  Four cells whose c | o is all zero are neither read nor written in the
+// accumulators -- nor are the counters of four cells without a cohort, the hits of four cells without a hit and the sums of two
+// zero cells: before the epidemic has arrived a window costs the 8 B per cell of the planes and little else.  A cell with
+// offspring but no cases (a cohort the window's column does not hold) still adds to the sums: nothing here relies on o > 0
+// implying c > 0.
+__global__ __launch_bounds__(TPB) void k_ensemble_fold_ratio(const uint32_t *c, const uint32_t *o, uint64_t cells, uint32_t min_cohort, uint32_t r_num, uint32_t r_den, RatioAcc a)
+{
+    if (blockIdx.x == 0u && threadIdx.x == 0u) *a.members += 1u;
+    const uint4 *c4 = reinterpret_cast<const uint4 *>(c), *o4 = reinterpret_cast<const uint4 *>(o);
+    uint4 *d4 = reinterpret_cast<uint4 *>(a.defined), *h4 = reinterpret_cast<uint4 *>(a.hit);
+    const uint64_t n4 = cells >> 2, stride = (uint64_t)gridDim.x * TPB;
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += stride) {
+        const uint4 vc = c4[i], vo = o4[i];
+        if (!(vc.x | vc.y | vc.z | vc.w | vo.x | vo.y | vo.z | vo.w)) continue;
+        const uint32_t dx = vc.x >= min_cohort, dy = vc.y >= min_cohort, dz = vc.z >= min_cohort, dw = vc.w >= min_cohort;
+        if (dx | dy | dz | dw) {
+            uint4 d = d4[i];
+            d.x += dx; d.y += dy; d.z += dz; d.w += dw;
+            d4[i] = d;
+            const uint32_t hx = dx & ratio_hit(vc.x, vo.x, r_num, r_den), hy = dy & ratio_hit(vc.y, vo.y, r_num, r_den);
+            const uint32_t hz = dz & ratio_hit(vc.z, vo.z, r_num, r_den), hw = dw & ratio_hit(vc.w, vo.w, r_num, r_den);
+            if (hx | hy | hz | hw) {
+                uint4 h = h4[i];
+                h.x += hx; h.y += hy; h.z += hz; h.w += hw;
+                h4[i] = h;
+            }
+        }
+        if (vc.x | vc.y | vo.x | vo.y) ratio_pair(a, 2u * i, vc.x, vc.y, vo.x, vo.y);
+        if (vc.z | vc.w | vo.z | vo.w) ratio_pair(a, 2u * i + 1u, vc.z, vc.w, vo.z, vo.w);
+    }
+    const uint64_t tail = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0u && threadIdx.x < (uint32_t)(cells & 3u)) {
+        const uint32_t vc = c[tail], vo = o[tail];
+        if (vc >= min_cohort) { a.defined[tail] += 1u; if (ratio_hit(vc, vo, r_num, r_den)) a.hit[tail] += 1u; }
+        if (vc | vo) {
+            a.sum_c[tail] += vc; a.sum_o[tail] += vo;
+            a.sq_c[tail] += (unsigned long long)vc * vc; a.sq_o[tail] += (unsigned long long)vo * vo; a.cross[tail] += (unsigned long long)vc * vo;
+        }
     }
 }

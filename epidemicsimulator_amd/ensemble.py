@@ -61,13 +61,50 @@ def series_summary(members, hit, total, sumsq, first_step=1, stride=1):
     return out
 
 
+def _ratio_residuals(sx, sy, sxx, syy, sxy):
+    """sum over members of (y_i * Sx - Sy * x_i)^2 = Sx^2 * sum y^2 - 2 Sx Sy * sum xy + Sy^2 * sum x^2 per cell, exactly, from the
+    integer sums (Sx = sum x, Sy = sum y) and as float64: in int64 where every term stays below 2^60, in Python integers
+    otherwise -- in floating point the three terms cancel to nothing where offspring is nearly proportional to cases."""
+    arrays = [np.asarray(a, np.uint64) for a in (sx, sy, sxx, syy, sxy)]
+    top = [int(a.max()) if a.size else 0 for a in arrays]
+    if max(top[0], top[1]) ** 2 * max(top[2:]) < 1 << 60:
+        sx, sy, sxx, syy, sxy = (a.astype(np.int64) for a in arrays)
+    else:
+        sx, sy, sxx, syy, sxy = (a.astype(object) for a in arrays)
+    return (sx * sx * syy - 2 * sx * sy * sxy + sy * sy * sxx).astype(np.float64)
+
+
+def reproduction_summary(acc, first_step=0, stride=24):
+    """From Simulator.ensemble_read_reproduction(): members, defined, hit; cases_mean and offspring_mean over the members; r,
+    the pooled case reproduction number sum_offspring / sum_cases of the cell, NaN where no member had a case; p_r = hit /
+    defined, the share of the members with a cohort in the cell whose offspring / cases reached the threshold, NaN where none
+    had one; r_se, the standard error of r by the delta method over members -- Var(r) = (s_oo - 2 r s_co + r^2 s_cc) / (members *
+    cases_mean^2) with the sample covariances (ddof = 1) of cases and offspring over the members, which is sum_i (o_i - r c_i)^2 /
+    (members - 1) in the numerator --, NaN for fewer than two members or no cases; and steps, the first step of every row's
+    cohort."""
+    m = int(acc["members"])
+    sx, sy = np.asarray(acc["sum_cases"], np.uint64), np.asarray(acc["sum_offspring"], np.uint64)
+    defined, hit = np.asarray(acc["defined"], np.uint32), np.asarray(acc["hit"], np.uint32)
+    fx, fy = sx.astype(np.float64), sy.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.where(sx > 0, fy / fx, np.nan)
+        p_r = np.where(defined > 0, hit.astype(np.float64) / defined.astype(np.float64), np.nan)
+        if m >= 2:
+            resid = _ratio_residuals(sx, sy, acc["sumsq_cases"], acc["sumsq_offspring"], acc["sum_cross"])
+            r_se = np.where(sx > 0, np.sqrt(resid * (m / (m - 1.0))) / (fx * fx), np.nan)
+        else:
+            r_se = np.full(sx.shape, np.nan)
+    return {"members": m, "defined": defined, "hit": hit, "cases_mean": fx / m if m else np.zeros_like(fx), "offspring_mean": fy / m if m else np.zeros_like(fy),
+            "r": r, "p_r": p_r, "r_se": r_se, "steps": int(first_step) + int(stride) * np.arange(sx.shape[0], dtype=np.int64)}
+
+
 def _json_number(x):
     x = float(x)
     return None if x != x else x          # NaN (an arrival mean nobody contributed to) is written as null
 
 
 class EnsembleResult:
-    def __init__(self, records, n_done, members, area=None, area_codes=None, settings=None, reproduction=None):
+    def __init__(self, records, n_done, members, area=None, area_codes=None, settings=None, reproduction=None, area_kind=None):
         self.records = records            # structured [members, n_steps]
         self.settings = settings          # uint32 [members, n_rows, 4]: every member's setting_series(where="setting"), or None
         self.reproduction = reproduction  # uint32 [members, n_rows, 2]: every member's reproduction_series("all"), (cases, offspring), or None
@@ -75,6 +112,7 @@ class EnsembleResult:
         self.members = list(members)      # the overrides of every member
         self.area = area                  # area_summary(...) or None
         self.area_codes = area_codes
+        self.area_kind = area_kind        # the kind of run(area=dict(kind=...)) the summary came from, or None
 
     def quantiles(self, field, qs):
         """[len(qs), n_steps]: the quantiles of `field` over the members, per step."""
@@ -91,7 +129,9 @@ class EnsembleResult:
         """ensemble_stats.json: per field the mean and the 5/25/50/75/95 % rows over the members; ensemble_areas.json: hit, mean
         and var per Output Area, keyed by its code where the Ensemble was given area_codes, else by its index (an arrival
         summary's mean and var are null where hit is 0).  A series summary goes to ensemble_area_series.npz instead -- steps,
-        hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary.  The members' exposures by setting, where they
+        hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary; the
+        summary of area kind "settings" goes to ensemble_area_settings.npz the same way, that of kind "reproduction" to
+        ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes.  The members' exposures by setting, where they
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
         ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names."""
         os.makedirs(directory, exist_ok=True)
@@ -102,12 +142,16 @@ class EnsembleResult:
         with open(os.path.join(directory, "ensemble_stats.json"), "w") as fh:
             json.dump(stats, fh)
         doc = None
-        if self.area is not None and "steps" in self.area:     # a series summary: arrays by (row, column), too many for JSON
+        if self.area is not None and "steps" in self.area:     # a summary over rows: arrays by (row, column), too many for JSON
             a = self.area
-            arrays = {k: a[k] for k in ("steps", "hit", "mean", "var")}
+            ratio = "r" in a
+            arrays = {k: a[k] for k in (("steps", "defined", "hit", "cases_mean", "offspring_mean", "r", "p_r", "r_se") if ratio else ("steps", "hit", "mean", "var"))}
+            if ratio:
+                arrays["members"] = np.asarray(a["members"], np.uint32)
             if self.area_codes is not None:
                 arrays["codes"] = np.asarray(self.area_codes)
-            np.savez(os.path.join(directory, "ensemble_area_series.npz"), **arrays)
+            name = "ensemble_area_reproduction.npz" if ratio else "ensemble_area_settings.npz" if self.area_kind == "settings" else "ensemble_area_series.npz"
+            np.savez(os.path.join(directory, name), **arrays)
         elif self.area is not None:
             a = self.area
             key = (lambda i: self.area_codes[i]) if self.area_codes is not None else (lambda i: str(i))
@@ -268,7 +312,8 @@ class EventResult:
         np.savez(os.path.join(directory, "ensemble_events.npz"), sizes=self.sizes, **{k: getattr(self, k) for k in self.KEYS})
 
 
-_KINDS = ("census", "arrival", "series")
+_KINDS = ("census", "arrival", "series", "settings", "reproduction")
+_ROW_KINDS = ("series", "settings", "reproduction")      # a member that stopped early has no rows behind its last step
 
 
 class Ensemble:
@@ -284,34 +329,60 @@ class Ensemble:
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
         self._own_seeds = True            # the seeds in force are the uploaded population's
 
-    @staticmethod
-    def _area_kind(who, area, stop_when_done=False):
-        """area of run() / forecast() checked, before anything runs: (kind, the area dict without its kind), or (None, None)."""
+    def _area_kind(self, who, area, n_steps, stop_when_done=False):
+        """area of run() / forecast() checked, before anything runs: (kind, the area dict without its kind), or (None, None).
+        For the reproduction kind `complete` is resolved here: with complete=True (the default) and n_rows=None only the rows
+        are taken whose cohort has had its whole infectious period by step n_steps."""
         if area is None:
             return None, None
         area = dict(area)
         kind = area.pop("kind", "census")
         if kind not in _KINDS:
-            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', got %r" % (who, kind))
-        if kind == "series" and stop_when_done:
-            raise ValueError("Ensemble.%s: area kind 'series' cannot go with stop_when_done=True (a member that stopped early has no "
-                             "rows behind its last step, and the library refuses the fold)" % who)
+            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings' or 'reproduction', got %r" % (who, kind))
+        if kind in _ROW_KINDS and stop_when_done:
+            raise ValueError("Ensemble.%s: area kind %r cannot go with stop_when_done=True (a member that stopped early has no "
+                             "rows behind its last step, and the library refuses the fold)" % (who, kind))
+        if kind == "settings" and area.get("n_rows") is None:
+            first, stride = int(area.get("first_step", 1)), int(area.get("stride", 1))
+            area["n_rows"] = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
+        if kind == "reproduction":
+            complete = area.pop("complete", True)
+            if area.get("n_rows") is None:
+                first, stride = int(area.get("first_step", 0)), int(area.get("stride", 24))
+                last = int(n_steps)
+                if complete:      # a row is complete when its last step s satisfies s + exposed_time + 1 + infected_time <= n_steps (Simulator.household_sar)
+                    last -= int(self.base.exposed_time) + 1 + int(self.base.infected_time)
+                    n_rows = (last - first + 1) // stride if stride > 0 and first >= 0 else 0
+                    if n_rows < 1:
+                        raise ValueError("Ensemble.%s: no complete cohort row from step %d with stride %d after %d steps (a cohort exposed in step s is complete "
+                                         "once s + exposed_time + 1 + infected_time steps have run; complete=False takes the open rows too)" % (who, first, stride, int(n_steps)))
+                else:
+                    n_rows = (last - first) // stride + 1 if stride > 0 and 0 <= first <= last else 0
+                area["n_rows"] = n_rows
         return kind, area
 
     def _begin(self, kind, area):
         sim = self.simulator
         if kind is not None:
-            getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series"}[kind])(**area)
+            getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
+                          "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction"}[kind])(**area)
 
     def _summary(self, kind, area):
         sim = self.simulator
         if kind is None:
             return None
-        if kind == "series":
+        if kind == "reproduction":
+            return reproduction_summary(sim.ensemble_read_reproduction(), area.get("first_step", 0), area.get("stride", 24))
+        if kind in ("series", "settings"):
             r = sim.ensemble_read_series()
             return series_summary(r["members"], r["hit"], r["sum"], r["sumsq"], area.get("first_step", 1), area.get("stride", 1))
         r = sim.ensemble_read()
         return (arrival_summary if kind == "arrival" else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
+
+    def _codes(self, area):
+        """The area codes that name the summary's columns: none where they are groups, settings or the one column of "all"."""
+        by_area = area is not None and area.get("where", "home") in ("home", "current", _lib.AREA_HOME, _lib.AREA_CURRENT)
+        return self.area_codes if by_area or area is None else None
 
     @staticmethod
     def _settings_rows(who, settings, n_steps, stop_when_done=False):
@@ -454,14 +525,20 @@ class Ensemble:
         horizon=...) for the arrival step instead (esim_ensemble_begin_arrival; the summary's mean and var are then over the
         members that reached the entry, NaN where none did); or dict(kind="series", where=..., what=..., first_step=...,
         n_rows=..., stride=..., min_cases=...) for the rows of a series (Simulator.ensemble_begin_series; the summary is a
-        series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError).
+        series_summary, [n_rows, n_cols]; not with stop_when_done=True: ValueError); or dict(kind="settings", where=...,
+        settings=..., first_step=..., n_rows=..., stride=..., min_cases=...) for the exposures by setting per Output Area or
+        group (Simulator.ensemble_begin_settings; a series_summary again); or dict(kind="reproduction", where=..., first_step=...,
+        n_rows=..., stride=..., min_cohort=..., r=(num, den), complete=True) for the cohort rows (Simulator.
+        ensemble_begin_reproduction; the summary is a reproduction_summary).  With complete=True and n_rows=None only complete
+        cohort rows are taken -- an incomplete cohort biases R down -- and ValueError is raised when there is none.  Neither goes
+        with stop_when_done=True.
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
         (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
         with stop_when_done=True either.
         reproduction: None, or dict(first_step=..., n_rows=..., stride=...): every member's cohort rows
         (Simulator.reproduction_series("all")) gathered as EnsembleResult.reproduction, [members, n_rows, 2] = (cases,
         offspring); not with stop_when_done=True either.  Returns an EnsembleResult."""
-        kind, area = self._area_kind("run", area, stop_when_done)
+        kind, area = self._area_kind("run", area, n_steps, stop_when_done)
         spec = self._settings_rows("run", settings, n_steps, stop_when_done)
         r_spec = self._reproduction_rows("run", reproduction, n_steps, stop_when_done)
         sim = self.simulator
@@ -481,9 +558,8 @@ class Ensemble:
             rows.append(pad_records(rec, n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
-        by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec),
-                              self._reproduction_stack(by_cohort, r_spec))
+        return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
+                              self._reproduction_stack(by_cohort, r_spec), kind)
 
     def forecast(self, history_steps, members, n_steps, area=None, settings=None, reproduction=None):
         """Given the epidemic as it stands after `history_steps` steps under the base parameters, what happens next: the base
@@ -492,7 +568,7 @@ class Ensemble:
         for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
         library refuses them).  area, settings and reproduction: as for run(), folded / gathered once per member.  Returns an EnsembleResult whose records are
         [members, n_steps], the shared history repeated in every row."""
-        kind, area = self._area_kind("forecast", area)
+        kind, area = self._area_kind("forecast", area, n_steps)
         spec = self._settings_rows("forecast", settings, n_steps)
         r_spec = self._reproduction_rows("forecast", reproduction, n_steps)
         sim = self.simulator
@@ -521,9 +597,8 @@ class Ensemble:
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
         summary = self._summary(kind, area)
-        by_group = area is not None and area.get("where") in ("group", _lib.BY_GROUP)
-        return EnsembleResult(records, n_done, members, summary, None if by_group else self.area_codes, self._settings_stack(by_setting, spec),
-                              self._reproduction_stack(by_cohort, r_spec))
+        return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
+                              self._reproduction_stack(by_cohort, r_spec), kind)
 
     def close(self):
         self.simulator.close()

@@ -326,6 +326,49 @@ class Simulator:
                                                       tot.ctypes.data_as(C.POINTER(C.c_uint64)), sq.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
         return {"members": int(members.value), "hit": hit, "sum": tot, "sumsq": sq}
 
+    def ensemble_begin_settings(self, where="home", settings=None, first_step=1, n_rows=None, stride=1, min_cases=1):
+        """Accumulators over the exposures by setting (esim_ensemble_begin_settings): a member contributes, cell for cell, the
+        rows setting_series(where, settings, first_step, n_rows, stride) would return for it.  where: "setting" (four columns),
+        "home" or "group"; settings as setting_series takes them.  n_rows=None: up to the last step of the run
+        (params.max_steps).  ensemble_fold adds hit += (x >= min_cases), sum += x, sumsq += x * x per cell on the device;
+        ensemble_read_series reads them."""
+        place = {"setting": _lib.BY_SETTING, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        if n_rows is None:
+            last = int(self.params.max_steps)
+            n_rows = (last - int(first_step)) // int(stride) + 1 if stride and 1 <= first_step <= last else 0
+        _lib.check(self.lib.esim_ensemble_begin_settings(self._ctx, int(place), self._setting_mask(settings), int(first_step), int(n_rows), int(stride), int(min_cases)), self._ctx)
+        self._ens_rows = int(n_rows)
+        self._ens_n = _lib.N_SETTINGS if place == _lib.BY_SETTING else self._n_groups if place == _lib.BY_GROUP else self.population.n_areas
+
+    def ensemble_begin_reproduction(self, where="home", first_step=0, n_rows=None, stride=24, min_cohort=1, r=(1, 1)):
+        """Accumulators over the cohort rows (esim_ensemble_begin_reproduction): a member contributes the (cases, offspring) rows
+        reproduction_series(where, first_step, n_rows, stride) would return for it.  where: "all" (one column), "home" or
+        "group".  Per cell ensemble_fold counts the members with a cohort of at least min_cohort cases (defined), those of them
+        with offspring / cases >= r[0] / r[1] (hit), and sums cases, offspring, their squares and their product, in integers on
+        the device.  n_rows=None: up to the last step of the run (params.max_steps); ensemble_read_reproduction reads them."""
+        place = {"all": _lib.BY_ALL, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        if n_rows is None:
+            last = int(self.params.max_steps)
+            n_rows = (last - int(first_step)) // int(stride) + 1 if stride and 0 <= first_step <= last else 0
+        _lib.check(self.lib.esim_ensemble_begin_reproduction(self._ctx, int(place), int(first_step), int(n_rows), int(stride), int(min_cohort), int(r[0]), int(r[1])), self._ctx)
+        self._ens_rows = int(n_rows)
+        self._ens_n = 1 if place == _lib.BY_ALL else self._n_groups if place == _lib.BY_GROUP else self.population.n_areas
+
+    REPRODUCTION_KEYS = ("defined", "hit", "sum_cases", "sum_offspring", "sumsq_cases", "sumsq_offspring", "sum_cross")
+
+    def ensemble_read_reproduction(self, first_row=0, n_rows=None):
+        """{"members": int, "defined", "hit": uint32 [n, n_cols], "sum_cases", "sum_offspring", "sumsq_cases", "sumsq_offspring",
+        "sum_cross": uint64 [n, n_cols]}: rows [first_row, first_row + n) of the accumulators begun by
+        ensemble_begin_reproduction; n_rows=None: all from first_row on."""
+        total = getattr(self, "_ens_rows", 0)
+        n = max(0, total - int(first_row)) if n_rows is None else int(n_rows)
+        cols = getattr(self, "_ens_n", self.population.n_areas)
+        members = C.c_uint32(0)
+        out = {k: np.zeros((n, cols), np.uint32 if i < 2 else np.uint64) for i, k in enumerate(self.REPRODUCTION_KEYS)}
+        ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint32 if i < 2 else C.c_uint64)) for i, k in enumerate(self.REPRODUCTION_KEYS)]
+        _lib.check(self.lib.esim_ensemble_read_reproduction(self._ctx, int(first_row), n, C.byref(members), *ptrs), self._ctx)
+        return dict(out, members=int(members.value))
+
     def download_state(self):
         n = self.population.n_citizens
         out = {"status": np.zeros(n, np.uint8), "timer": np.zeros(n, np.uint16),

@@ -516,6 +516,55 @@ int  esim_reproduction_series(esim_ctx *ctx, int where, uint32_t first_step, uin
                               uint32_t *cases /* [n_rows * n_cols] or NULL */, uint32_t *offspring /* [n_rows * n_cols] or NULL */);
 int  esim_mixing_matrix(esim_ctx *ctx, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
                         uint32_t *counts /* [n_groups * n_groups] */);
+/* Ensemble maps of transmission: two more kinds of the accumulators over rows of esim_ensemble_begin_series, for the two
+ * transmission outputs that are rows already -- "how often does an area see at least k household-acquired cases in the week
+ * after the lockdown", "in how many futures is R at least 1 in this area this week" -- folded on the device where the replay
+ * leaves a member's rows.  One kind of accumulator is in force at a time (census, arrival, series, settings, reproduction); a
+ * begin of any kind replaces it.  Lifetime as for esim_ensemble_begin_series: kept through esim_reset, esim_restart,
+ * esim_restart_seeded, esim_snapshot and esim_rollback, dropped by a new upload and by esim_destroy, invalidated by
+ * esim_set_groups when begun by group.  A begin with the kind, n_rows and n_cols in force zeroes what is there; any other shape
+ * is allocated first and the earlier one freed then, so ESIM_ENOMEM leaves the context and every earlier accumulator as they
+ * were.  A run that never asks pays nothing.
+ * begin_settings: x[row * n_cols + col] is, cell for cell, what esim_setting_series(where, setting_mask, first_step, n_rows,
+ *        stride) would return for the member; where = ESIM_BY_SETTING (4 columns), ESIM_AREA_HOME or ESIM_BY_GROUP.  The
+ *        accumulators are those of the series kind -- hit (u32), sum and sumsq (u64) per cell, 20 B, and the member counter --
+ *        beside one row plane of 4 B per cell; a fold adds members += 1; hit += (x >= min_cases); sum += x; sumsq += x * x, and
+ *        esim_ensemble_read_series reads them.  ESIM_EINVAL: a null context, any other `where`, a mask that is empty or names a
+ *        setting beyond ESIM_SETTING_TRANSPORT, stride 0, no rows.  ESIM_ESTATE: before a population is uploaded; by group
+ *        without labels; on a context whose communicator has more than one rank.  ESIM_ERANGE: first_step == 0.
+ * begin_reproduction: a member contributes the cohort rows of esim_reproduction_series(where, first_step, n_rows, stride), c =
+ *        cases[cell] and o = offspring[cell]; where = ESIM_BY_ALL (one column), ESIM_AREA_HOME or ESIM_BY_GROUP; first_step 0
+ *        is allowed, as there.  A fold adds members += 1 once and per cell
+ *          if c >= min_cohort:  defined += 1, and hit += 1 iff (uint64_t)o * r_den >= (uint64_t)c * r_num
+ *          always:              sum_cases += c; sum_offspring += o; sumsq_cases += c * c; sumsq_offspring += o * o;
+ *                               sum_cross += c * o
+ *        in integers: two u32 and five u64 per cell, 48 B, beside two row planes of 4 B per cell each.  sum_offspring /
+ *        sum_cases is the pooled R of the cell, hit / defined is P(R >= r_num / r_den) among the members that had a cohort
+ *        there, and the five sums give the delta-method variance of the ratio over members.  A row whose cohort can still
+ *        infect (esim_reproduction_series: not COMPLETE) biases R down; the window is the caller's to choose.  ESIM_EINVAL: a
+ *        null context, any other `where`, stride 0, no rows, min_cohort == 0, r_den == 0.  ESIM_ESTATE as begin_settings.
+ * fold:  esim_ensemble_fold with one of the two in force first makes the checks of the series call the kind stands for --
+ *        ESIM_ESTATE on a sharded context, on a history mixed twice and, the reproduction kind, after a rollback under another
+ *        bus_capacity; ESIM_ERANGE when the last row lies beyond the steps the member has run -- and on any of them folds
+ *        nothing and leaves members as it was.  Then, on the context's stream: the kept plane(s) zeroed, the replay of the
+ *        settings (and of the tree, without generations), the rows into the kept planes, one pass over the cells.  It WAITS FOR
+ *        THE STREAM, as every call on top of the replay does, and reports the audits their way: the member IS folded, then
+ *        ESIM_ESIM is returned with the count in esim_last_error.  Nothing proportional to rows x columns goes to the host or is
+ *        allocated; the replay's temporaries are those of esim_setting_series / esim_reproduction_series without their rows.
+ *        Leaves the simulation state, the records, the exposure log, the snapshot and the labels as they are.
+ * read_reproduction: rows [first_row, first_row + n) of the accumulators of the reproduction kind, [(r - first_row) * n_cols +
+ *        col] each; members is one counter; any pointer may be NULL.  ESIM_ERANGE for rows outside the accumulators; ESIM_ESTATE
+ *        when another kind is in force -- and esim_ensemble_read and esim_ensemble_read_series are ESIM_ESTATE while this one
+ *        is (esim_ensemble_read_series serves the settings kind). */
+int  esim_ensemble_begin_settings(esim_ctx *ctx, int where, uint32_t setting_mask, uint32_t first_step, uint32_t n_rows,
+                                  uint32_t stride, uint32_t min_cases);
+int  esim_ensemble_begin_reproduction(esim_ctx *ctx, int where, uint32_t first_step, uint32_t n_rows, uint32_t stride,
+                                      uint32_t min_cohort, uint32_t r_num, uint32_t r_den);
+int  esim_ensemble_read_reproduction(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members,
+                                     uint32_t *defined /* [n * n_cols] */, uint32_t *hit /* [n * n_cols] */,
+                                     uint64_t *sum_cases /* [n * n_cols] */, uint64_t *sum_offspring /* [n * n_cols] */,
+                                     uint64_t *sumsq_cases /* [n * n_cols] */, uint64_t *sumsq_offspring /* [n * n_cols] */,
+                                     uint64_t *sum_cross /* [n * n_cols] */);
 /* Transmission chains: which introduction a case descends from, how large the outbreak is that a citizen started, and when
  * during their infectious period people transmit -- functions of the tree above, computed where it lies, so that nothing of
  * size [n_citizens] has to go to the host for them.  Per entry (c, ts) of the exposure log; infector, generation and setting
