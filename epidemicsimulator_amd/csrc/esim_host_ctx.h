@@ -169,6 +169,7 @@ struct esim_ctx_impl {
     uint32_t *cnt_base = nullptr;
     uint32_t n_routes = 0;
     std::vector<uint32_t> route_tab;      // esim_routes: home area, work area and riders of every route, [3][n_routes]
+    uint32_t longest_list = 0;            // members of the longest household, work place, room or route (esim_contact_hours: the range of per_case)
     size_t xa_n = 0, xb_n = 0, xf_n = 0;
     uint64_t pop_hash = 0;        // of the uploaded population arrays: a checkpoint only goes back into the population it came from
     uint64_t pop_hash_head = 0;   // the same hash before it mixes the seeds (esim_restart_seeded finishes it with its own list)

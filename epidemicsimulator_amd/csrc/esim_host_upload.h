@@ -237,6 +237,9 @@ int upload_chunk_tables(esim_ctx_impl *c, const UploadHost &u)
     std::vector<uint32_t> ovf_off(u.res_off.size());
     for (size_t i = 0; i < u.res_off.size(); ++i) ovf_off[i] = u.res_off[i] + u.wrk_off[i] + sch_members[i];
     if ((rc = dev_upload(c, &d.ovf_off, ovf_off.data(), ovf_off.size()))) return rc;
+    c->longest_list = u.max_route;
+    for (const std::vector<uint32_t> *off : { &u.res_off, &u.wrk_off, &u.room_off })
+        for (size_t i = 1; i < off->size(); ++i) c->longest_list = std::max(c->longest_list, (*off)[i] - (*off)[i - 1]);
     {
         std::vector<int32_t> sch_of(B ? B : 1, -1);
         uint32_t n_sch = 0;

@@ -237,6 +237,34 @@ class HouseholdResult:
                  at_risk=self.at_risk, secondary=self.secondary, sar=self.sar())
 
 
+class ContactResult:
+    """What Ensemble.contacts gathers: the contact-hours and the transmissions of every member by setting."""
+
+    def __init__(self, members, hours, transmissions):
+        self.members = list(members)      # the overrides of every member
+        self.hours = np.asarray(hours, np.uint64)                    # uint64 [members, 4, n_cols, n_cols]: contact-hours at risk
+        self.transmissions = np.asarray(transmissions, np.uint64)    # uint64 [members, 4, n_cols, n_cols]: the transmissions among them
+
+    @classmethod
+    def gathered(cls, members, tables, n_cols=1):
+        """From every member's Simulator.contact_hours() dict."""
+        def stack(key):
+            return np.stack([t[key] for t in tables]).astype(np.uint64) if tables else np.zeros((0, _lib.N_SETTINGS, n_cols, n_cols), np.uint64)
+        return cls(members, stack("hours"), stack("transmissions"))
+
+    def rate(self):
+        """float64 [4, n_cols, n_cols]: transmissions per contact-hour pooled over the members -- the sum of transmissions
+        divided by the sum of hours --, NaN where there was no contact-hour."""
+        h, t = self.hours.sum(axis=0).astype(np.float64), self.transmissions.sum(axis=0).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(h > 0, t / h, np.nan)
+
+    def dump(self, directory):
+        """ensemble_contacts.npz: hours, transmissions and the pooled rate."""
+        os.makedirs(directory, exist_ok=True)
+        np.savez(os.path.join(directory, "ensemble_contacts.npz"), hours=self.hours, transmissions=self.transmissions, rate=self.rate())
+
+
 class FlowResult:
     """What Ensemble.flows gathers: the imports table and the invasion tree of every member, one row per member and one column
     per Output Area."""
@@ -488,6 +516,20 @@ class Ensemble:
             pairs.append(sim.household_sar(where, first_step, last_step))
         n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
         return HouseholdResult.gathered(members, sizes, pairs, n_cols)
+
+    def contacts(self, members, n_steps, where="all", settings=None, first_step=1, last_step=None):
+        """Contact-hours at risk over an ensemble: every member (as for run()) is run for n_steps steps and its two tables
+        (Simulator.contact_hours(where, settings, first_step, last_step)) gathered.  where="group" counts by the groups given to
+        Ensemble(...).  Returns a ContactResult."""
+        sim = self.simulator
+        members = self._members(members)
+        tables = []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            tables.append(sim.contact_hours(where, settings, first_step, last_step))
+        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
+        return ContactResult.gathered(members, tables, n_cols)
 
     def flows(self, members, n_steps, settings=None, first_step=1, last_step=None):
         """How the epidemic travels, over an ensemble: every member (as for run()) is run for n_steps steps and its imports table

@@ -724,6 +724,40 @@ class Simulator:
                                                secondary.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
         return at_risk, secondary
 
+    # -- contact-hours at risk (esim_contact_hours) -------
+    def contact_hours(self, where="all", settings=None, first_step=1, last_step=None, per_case=False):
+        """dict: hours and transmissions, uint64 [4, n_cols, n_cols] each, and with per_case=True per_case, uint32 [n_citizens]
+        (esim_contact_hours).  hours[s, g_infected, g_susceptible] counts the contact-hours of setting s in steps first_step ..
+        last_step (None: the last step run): a Susceptible citizen taking the draw of a gathering in a step in which an
+        Infected citizen is a candidate of it.  transmissions is the mixing matrix split by setting; transmissions <= hours
+        cell for cell.  per_case[j]: the contact-hours with j as the Infected side.  where: "all" (one cell) or "group";
+        settings as setting_series takes them (the planes of the others stay 0)."""
+        place = {"all": _lib.BY_ALL, "group": _lib.BY_GROUP}.get(where, where)
+        n_cols = max(1, self._n_groups) if place == _lib.BY_GROUP else 1
+        last = self._steps if last_step is None else int(last_step)
+        out = {k: np.zeros((_lib.N_SETTINGS, n_cols, n_cols), np.uint64) for k in ("hours", "transmissions")}
+        cases = np.zeros(self.population.n_citizens, np.uint32) if per_case else None
+        u64p = C.POINTER(C.c_uint64)
+        _lib.check(self.lib.esim_contact_hours(self._ctx, int(place), self._setting_mask(settings), int(first_step), last, out["hours"].ctypes.data_as(u64p),
+                                               out["transmissions"].ctypes.data_as(u64p), cases.ctypes.data_as(C.POINTER(C.c_uint32)) if per_case else None), self._ctx)
+        if per_case:
+            out["per_case"] = cases
+        return out
+
+    @staticmethod
+    def _rate(transmissions, hours):
+        """transmissions / hours as float64, NaN where hours == 0."""
+        t, h = np.asarray(transmissions, np.float64), np.asarray(hours, np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(h > 0, t / h, np.nan)
+
+    def contact_rates(self, where="all", settings=None, first_step=1, last_step=None):
+        """float64 [4, n_cols, n_cols]: transmissions per contact-hour, contact_hours()'s transmissions / hours, NaN where there
+        was no contact-hour.  In households, work places and buses this is close to exposure_chance; in school rooms far above
+        it (a room draw uses the Infected count of the whole school and is taken once per Infected of the room)."""
+        got = self.contact_hours(where, settings, first_step, last_step)
+        return self._rate(got["transmissions"], got["hours"])
+
     # -- area flows (esim_area_flows, esim_area_imports, esim_area_invasion, esim_lineage_areas) -------
     def _pairs(self, call, args):
         """The three [n] arrays of a sparse output: one call with cap=0 for the number of pairs, then the real one -- two

@@ -653,6 +653,50 @@ int  esim_household_outbreaks(esim_ctx *ctx, uint32_t *cases, uint32_t *introduc
 int  esim_household_final_sizes(esim_ctx *ctx, uint32_t *final_size /* [ESIM_HH_BINS * ESIM_HH_BINS] or NULL */, uint32_t *introductions /* same shape, or NULL */);
 int  esim_household_sar(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step,
                         uint64_t *at_risk, uint64_t *secondary /* [n_cols * n_cols] each, either may be NULL, not both */);
+/* Contact-hours at risk: the denominator of the transmissions above, for every setting and not only the household -- how many
+ * times a Susceptible citizen took a gathering's draw while a given Infected citizen was a candidate of it.  Derived after the
+ * fact like the tree and on top of it; a run that never asks pays nothing.  This is a stated contract, as the tie rule and the
+ * infector pick are.
+ *   contact-hour   a triple (j, m, ts), j != m: in step ts citizen j is a CANDIDATE of a gathering exactly as
+ *                  esim_transmission_tree defines candidates, and citizen m TAKES that gathering's draw.
+ *   j Infected     the exposure step te comes from the log; the Infected steps are te + exposed_time + 1 .. + infected_time, for
+ *                  an index case steps 1 .. infected_time; j is still Infected in the step at whose end it was vaccinated.
+ *   m takes a draw m is Susceptible after step ts - 1: ts <= the smaller of its exposure step and the step at whose end it was set
+ *                  Vaccinated (an index case: never), and
+ *     household         j is a resident of m's household and at home: not (bus bit and uses transport), not (work bit and has a
+ *                       work place); m is not (work bit, has a work place, and the work place is in another area);
+ *     work place        j is a worker of m's non-school work building, the work bit is set, j is not (bus bit and uses transport);
+ *                       m has a work place, and (its work place is in its home area, or the work bit is set);
+ *     school            the same over the participants of m's own ROOM (a room draw uses the threshold of the Infected count of
+ *                       the whole school and is taken once per Infected of the room: per contact-hour the school transmits far
+ *                       more often than exposure_chance -- the reference's behaviour, which this output makes visible);
+ *     public transport  the bus bit is set, j is a rider of m's route on m's bus of that step (rank by (key, position) /
+ *                       bus_capacity, keys as for the tree; a route of at most bus_capacity riders is one bus); m is a rider and
+ *                       was not exposed in a building in step ts itself -- buildings are drawn before buses.
+ *                  A citizen exposed at home in ts still counts for its work-side draw of ts: both draws are taken, the tie rule
+ *                  decides only the credit.  After a rollback under another seed the bus keys up to the seam use the snapshot's seed.
+ * esim_contact_hours: hours[s * n_cols^2 + col(j) * n_cols + col(m)] = the contact-hours of setting s with ts in [first_step,
+ *        last_step]; transmissions[...] = the transmissions of the tree with setting s, infector j, infectee m and the infectee's
+ *        step in the same window: the mixing matrix split by setting.  Every transmission is one of the contact-hours:
+ *        transmissions <= hours cell for cell.  per_case[j] = the contact-hours with j as the Infected side, summed over the
+ *        settings of the mask and the window; beside esim_offspring it separates "had many contacts" from "was lucky".
+ *          where = ESIM_BY_ALL       one column
+ *          where = ESIM_BY_GROUP     n_groups columns (ESIM_ESTATE without labels)
+ *        Any other `where`, an empty mask or a bit beyond ESIM_SETTING_TRANSPORT is ESIM_EINVAL; the planes of settings outside
+ *        the mask stay 0.  ESIM_ERANGE for steps outside 1 .. the steps run so far or last_step < first_step, and, before any
+ *        launch, where per_case is asked for and (infected_time + 1) x 3 x (the longest member list) does not fit its 32 bits.
+ *        Any output may be NULL; with all three NULL the audits of the tree still run.  Refused as esim_transmission_tree is
+ *        (ESIM_ESTATE before an upload, on a sharded context, on a history mixed twice, after a rollback under another
+ *        bus_capacity); ESIM_ESIM from the audits after delivering everything else.  The call leaves the simulation state, the
+ *        records, the exposure log, the snapshot, the ensemble accumulators and the labels as they are and keeps nothing between
+ *        calls.  Temporary device memory, freed when the call returns: that of esim_transmission_tree, 64 B per cell, 16 B per
+ *        step run, 4 B per citizen with per_case and, with routes longer than a bus in the mask, 4 B per bus step of the window,
+ *        a bit per (route, bus step) up to 64 MB at a time and 8 B per rider of the longest route for each of up to 2048
+ *        workgroups.  No kernel walks the steps of a pair: buildings, rooms and one-bus routes cost a difference of prefix counts
+ *        per pair; longer routes one ranking of the route per (route, bus step) that has an Infected rider. */
+int  esim_contact_hours(esim_ctx *ctx, int where, uint32_t setting_mask, uint32_t first_step, uint32_t last_step,
+                        uint64_t *hours /* [4 * n_cols * n_cols] or NULL */, uint64_t *transmissions /* same, or NULL */,
+                        uint32_t *per_case /* [n_citizens] or NULL */);
 /* How the epidemic travels: which Output Area seeds which, how many of an area's cases were imported, and through which area and
  * setting the epidemic first entered every area -- computed on the device from the tree, the lineage and the home area of every
  * citizen, so that nothing of size [n_citizens] goes to the host.  (A dense [n_areas][n_areas] table would be 340 GB at the
