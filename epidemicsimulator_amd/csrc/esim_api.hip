@@ -25,6 +25,7 @@
 #include "esim_host_tree.h"
 #include "esim_host_ensrows.h"
 #include "esim_host_household.h"
+#include "esim_host_places.h"
 #include "esim_host_contacts.h"
 #include "esim_host_flows.h"
 #include "esim_host_events.h"

@@ -37,6 +37,7 @@
 #include "esim_kernels_tree.h"
 #include "esim_kernels_chains.h"
 #include "esim_kernels_household.h"
+#include "esim_kernels_places.h"
 #include "esim_kernels_contacts.h"
 #include "esim_kernels_flows.h"
 #include "esim_kernels_events.h"

@@ -237,6 +237,48 @@ class HouseholdResult:
                  at_risk=self.at_risk, secondary=self.secondary, sar=self.sar())
 
 
+class PlaceResult:
+    """What Ensemble.places gathers: the size tables and the pair tables of the work places, rooms or schools of every member."""
+
+    def __init__(self, members, final_size, introduced, at_risk, secondary):
+        self.members = list(members)      # the overrides of every member
+        self.final_size = np.asarray(final_size, np.uint32)          # uint32 [members, 32, 32]: places of bin(size) with bin(k) cases
+        self.introduced = np.asarray(introduced, np.uint32)          # uint32 [members, 32, 32]: ... with bin(k) introductions
+        self.at_risk = np.asarray(at_risk, np.uint64)                # uint64 [members, n_cols, n_cols]: (case, member at risk) pairs
+        self.secondary = np.asarray(secondary, np.uint64)            # uint64 [members, n_cols, n_cols]: those infected there by the case
+
+    @classmethod
+    def gathered(cls, members, sizes, pairs, n_cols=1):
+        """From every member's Simulator.place_sizes() and place_sar() tuples."""
+        b = _lib.PLACE_BINS
+
+        def stack(rows, shape, dtype):
+            return np.stack(rows).astype(dtype) if rows else np.zeros((0,) + shape, dtype)
+        return cls(members, stack([t[0] for t in sizes], (b, b), np.uint32), stack([t[1] for t in sizes], (b, b), np.uint32),
+                   stack([t[0] for t in pairs], (n_cols, n_cols), np.uint64), stack([t[1] for t in pairs], (n_cols, n_cols), np.uint64))
+
+    def sar(self):
+        """float64 [n_cols, n_cols]: the secondary attack rate pooled over the members -- the sum of secondary divided by the
+        sum of at_risk --, NaN where nobody was at risk."""
+        at, sec = self.at_risk.sum(axis=0).astype(np.float64), self.secondary.sum(axis=0).astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(at > 0, sec / at, np.nan)
+
+    def attack_rate_by_size(self):
+        """float64 [32]: per size bin, the share of the places (pooled over the members) that had at least one case, NaN for a
+        bin without a place."""
+        tab = self.final_size.sum(axis=0).astype(np.float64)
+        places = tab.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(places > 0, (places - tab[:, 0]) / places, np.nan)
+
+    def dump(self, directory):
+        """ensemble_places.npz: final_size, introduced, at_risk, secondary, the pooled sar and attack_rate_by_size."""
+        os.makedirs(directory, exist_ok=True)
+        np.savez(os.path.join(directory, "ensemble_places.npz"), final_size=self.final_size, introduced=self.introduced,
+                 at_risk=self.at_risk, secondary=self.secondary, sar=self.sar(), attack_rate_by_size=self.attack_rate_by_size())
+
+
 class ContactResult:
     """What Ensemble.contacts gathers: the contact-hours and the transmissions of every member by setting."""
 
@@ -516,6 +558,25 @@ class Ensemble:
             pairs.append(sim.household_sar(where, first_step, last_step))
         n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
         return HouseholdResult.gathered(members, sizes, pairs, n_cols)
+
+    def places(self, members, n_steps, kind="work", where="all", first_step=0, last_step=None):
+        """Work place or school outbreaks over an ensemble: every member (as for run()) is run for n_steps steps and its size
+        tables (Simulator.place_sizes(kind)) and, for kind "work" or "room", its pair tables (Simulator.place_sar(kind, where,
+        first_step, last_step), complete cohorts only) gathered; kind "school" has no pairs, its two pair tables stay 0.
+        where="group" counts by the groups given to Ensemble(...).  Returns a PlaceResult."""
+        sim = self.simulator
+        members = self._members(members)
+        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
+        sizes, pairs = [], []
+        for m in members:
+            self._restart_member(m)
+            sim.run(n_steps)
+            sizes.append(sim.place_sizes(kind))
+            if kind in ("school", _lib.PLACE_SCHOOL):
+                pairs.append((np.zeros((n_cols, n_cols), np.uint64),) * 2)
+            else:
+                pairs.append(sim.place_sar(kind, where, first_step, last_step))
+        return PlaceResult.gathered(members, sizes, pairs, n_cols)
 
     def contacts(self, members, n_steps, where="all", settings=None, first_step=1, last_step=None):
         """Contact-hours at risk over an ensemble: every member (as for run()) is run for n_steps steps and its two tables

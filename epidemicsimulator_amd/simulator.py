@@ -724,6 +724,50 @@ class Simulator:
                                                secondary.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
         return at_risk, secondary
 
+    # -- work place and school outbreaks (esim_place_outbreaks, esim_place_sizes, esim_place_sar) -------
+    @staticmethod
+    def _place_kind(kind):
+        return {"work": _lib.PLACE_WORK, "room": _lib.PLACE_ROOM, "school": _lib.PLACE_SCHOOL}.get(kind, kind)
+
+    def place_outbreaks(self, kind="work"):
+        """Per place, a dict of uint32 arrays (esim_place_outbreaks): members, cases (the members in the exposure log, index
+        cases included), introductions (of those, the index cases and the cases not infected in the place's own setting) and
+        first_step (the smallest cohort step among them, _lib.NEVER without a case).  kind: "work" (the non-school buildings
+        and their workers, [n_buildings]), "room" (the school rooms and their participants, [n_rooms]) or "school" (the school
+        buildings, all their rooms together, [n_buildings]).  A building or room without a member has 0 everywhere."""
+        kind = self._place_kind(kind)
+        n = self.population.n_rooms if kind == _lib.PLACE_ROOM else self.population.n_buildings
+        keys = ("members", "cases", "introductions", "first_step")
+        out = {k: np.zeros(n, np.uint32) for k in keys}
+        _lib.check(self.lib.esim_place_outbreaks(self._ctx, int(kind), *(out[k].ctypes.data_as(C.POINTER(C.c_uint32)) for k in keys)), self._ctx)
+        return out
+
+    def place_sizes(self, kind="work"):
+        """(final_size, introduced), uint32 [32, 32] each (esim_place_sizes): entry [bin(members), bin(k)] counts the places of
+        the kind with k cases, or with k introductions; bin(x) = x below 16, then 16 for 16..31, 17 for 32..63 and so on."""
+        out = [np.zeros((_lib.PLACE_BINS, _lib.PLACE_BINS), np.uint32) for _ in range(2)]
+        _lib.check(self.lib.esim_place_sizes(self._ctx, int(self._place_kind(kind)), *(a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out)), self._ctx)
+        return tuple(out)
+
+    def place_sar(self, kind="work", where="all", first_step=0, last_step=None, complete=True):
+        """(at_risk, secondary), uint64 [n_cols, n_cols] each (esim_place_sar): household_sar for the work places (kind="work")
+        or the school rooms (kind="room") -- entry [g_case, g_contact] of at_risk counts the colleagues or class-mates still
+        Susceptible when the case became infectious, of secondary those it infected there.  where, first_step, last_step and
+        complete as for household_sar, with the same clipping and the same ValueError."""
+        place = {"all": _lib.BY_ALL, "group": _lib.BY_GROUP}.get(where, where)
+        n_cols = max(1, self._n_groups) if place == _lib.BY_GROUP else 1
+        first = int(first_step)
+        last = self._steps if last_step is None else int(last_step)
+        if complete:
+            done = self._steps - int(self.params.exposed_time) - 1 - int(self.params.infected_time)
+            last = min(last, done)
+            if last < max(first, 0):
+                raise ValueError("place_sar: no complete cohort in steps %d..%d after %d steps (complete=False counts the open ones)" % (first, last if last_step is None else int(last_step), self._steps))
+        at_risk, secondary = (np.zeros((n_cols, n_cols), np.uint64) for _ in range(2))
+        _lib.check(self.lib.esim_place_sar(self._ctx, int(self._place_kind(kind)), int(place), first, last, at_risk.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           secondary.ctypes.data_as(C.POINTER(C.c_uint64))), self._ctx)
+        return at_risk, secondary
+
     # -- contact-hours at risk (esim_contact_hours) -------
     def contact_hours(self, where="all", settings=None, first_step=1, last_step=None, per_case=False):
         """dict: hours and transmissions, uint64 [4, n_cols, n_cols] each, and with per_case=True per_case, uint32 [n_citizens]

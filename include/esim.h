@@ -653,6 +653,56 @@ int  esim_household_outbreaks(esim_ctx *ctx, uint32_t *cases, uint32_t *introduc
 int  esim_household_final_sizes(esim_ctx *ctx, uint32_t *final_size /* [ESIM_HH_BINS * ESIM_HH_BINS] or NULL */, uint32_t *introductions /* same shape, or NULL */);
 int  esim_household_sar(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step,
                         uint64_t *at_risk, uint64_t *secondary /* [n_cols * n_cols] each, either may be NULL, not both */);
+/* Work place and school outbreaks: a work place and a school room have a fixed member list too -- the lists the draws themselves
+ * use -- and they are the two settings the interventions act on.  The same outputs as for the household, per place: how many
+ * places had an outbreak, how large against their size, how many of their cases were brought in from outside, and which share
+ * of the members still Susceptible a case infected there.  Case, cohort step te, first infectious step f = max(te +
+ * exposed_time + 1, 1), "Susceptible after step f - 1" (sus_until[m] >= f_j - 1), settings, infectors, the tie rule and the
+ * seam of a rollback are those of the household block above, unchanged.
+ *   kind           ESIM_PLACE_WORK    the non-school buildings with at least one worker; members: the citizens whose work place it
+ *                                     is (work_building != home_building, not a School) -- the `workers` of
+ *                                     esim_transmission_tree.  Arrays [n_buildings].
+ *                  ESIM_PLACE_ROOM    the school rooms; members: their participants.  Arrays [n_rooms].
+ *                  ESIM_PLACE_SCHOOL  the school buildings; members: the participants of all their rooms together
+ *                                     (room_building).  Arrays [n_buildings].
+ *                  A building or room without a member is no place: counts 0, first_step ESIM_NEVER, not in the tables.
+ *   per place      members[p]: the number of members; cases[p]: the members that are cases; introductions[p]: of those, the index
+ *                  cases and the cases whose setting is not the place's OWN -- ESIM_SETTING_WORKPLACE for ESIM_PLACE_WORK,
+ *                  ESIM_SETTING_SCHOOL for ESIM_PLACE_ROOM and ESIM_PLACE_SCHOOL (a work-side exposure of a member can only have
+ *                  happened in its own work building or room, so the setting alone decides); first_step[p]: the smallest cohort
+ *                  step among its cases.
+ *   bin(x)         x for x < 16, else min(31, 12 + floor(log2 x)): 16..31 -> 16, 32..63 -> 17, ...; exact where rooms and case
+ *                  counts are small, logarithmic where work places are large.
+ * esim_place_outbreaks: the four per place, any may be NULL.
+ * esim_place_sizes: final_size[bin(members) * ESIM_PLACE_BINS + bin(cases)] counts the places, introduced[...] the same with
+ *        bin(introductions) as the second index; either may be NULL.
+ * esim_place_sar (ESIM_PLACE_WORK and ESIM_PLACE_ROOM only; ESIM_PLACE_SCHOOL is ESIM_EINVAL: the infector of a school exposure is
+ *        somebody of the room): a pair is (case j, member m != j of j's place); m is at risk from j iff m is Susceptible after
+ *        step f_j - 1; m is a secondary case of j iff, in addition, infector[m] == j and setting[m] is the place's own.  Counted
+ *        over the cases with cohort step in [first_step, last_step] and f_j <= the steps run; first_step 0 is allowed;
+ *        completeness of a cohort as for esim_household_sar.  secondary <= at_risk cell for cell, by construction.
+ *          where = ESIM_BY_ALL       one cell
+ *          where = ESIM_BY_GROUP     n_groups x n_groups, index g_case * n_groups + g_contact (ESIM_ESTATE without labels)
+ *        The counters are 64 bits wide, on the device too.  Either output may be NULL, not both.
+ * Errors follow the household calls.  ESIM_EINVAL: a null context, an unknown `kind` or `where`, both outputs of esim_place_sar
+ * NULL.  ESIM_ESTATE: before an upload, on a context with more than one rank or a shard, on a history mixed twice, by group
+ * without labels; esim_place_sar also after a rollback under another bus_capacity, as the tree calls are -- the first two calls
+ * need only the settings and return ESIM_OK then.  ESIM_ERANGE: as esim_household_sar.  The audits run: ESIM_ESIM after delivering
+ * everything else; with all outputs NULL the first two calls still run theirs.  A sticky device error comes back as the calls
+ * underneath report it.  All three leave the simulation state, the records, the exposure log, the snapshot, the ensemble
+ * accumulators and the labels as they are.  Temporary device memory, freed when the call returns: that of
+ * esim_exposure_settings (esim_place_sar: of esim_transmission_tree), 16 B per building or room of the kind (ESIM_PLACE_SCHOOL:
+ * per room and per building), 8 KB for the two tables, 16 B per cell.  The work is one pass over the member list; for
+ * esim_place_sar the members of a place are staged once on the chip and its cases run against them there, PER GATHERING,
+ * instead of one walk over the list per case. */
+enum { ESIM_PLACE_WORK = 0, ESIM_PLACE_ROOM = 1, ESIM_PLACE_SCHOOL = 2 };
+#define ESIM_PLACE_BINS 32
+int  esim_place_outbreaks(esim_ctx *ctx, int kind, uint32_t *members, uint32_t *cases, uint32_t *introductions, uint32_t *first_step);
+        /* [n_buildings] or [n_rooms] each, any may be NULL */
+int  esim_place_sizes(esim_ctx *ctx, int kind, uint32_t *final_size, uint32_t *introduced);
+        /* [ESIM_PLACE_BINS * ESIM_PLACE_BINS] each, either may be NULL */
+int  esim_place_sar(esim_ctx *ctx, int kind, int where, uint32_t first_step, uint32_t last_step,
+                    uint64_t *at_risk, uint64_t *secondary);   /* [n_cols * n_cols] each, not both NULL */
 /* Contact-hours at risk: the denominator of the transmissions above, for every setting and not only the household -- how many
  * times a Susceptible citizen took a gathering's draw while a given Infected citizen was a candidate of it.  Derived after the
  * fact like the tree and on top of it; a run that never asks pays nothing.  This is a stated contract, as the tie rule and the
