@@ -24,6 +24,7 @@
 #include "esim_host_settings.h"
 #include "esim_host_tree.h"
 #include "esim_host_ensrows.h"
+#include "esim_host_compare.h"
 #include "esim_host_household.h"
 #include "esim_host_places.h"
 #include "esim_host_contacts.h"

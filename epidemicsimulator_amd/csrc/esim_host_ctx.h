@@ -83,7 +83,9 @@ struct Ensemble {
     // esim_ensemble_begin_settings and esim_ensemble_begin_reproduction (esim_host_ensrows.h) are kinds of the same family:
     // rows.kind tells them apart.  The settings kind keeps hit, sum, sumsq and plane 0 only; the reproduction kind keeps hit,
     // sum and sumsq for the cases, both planes (cases, offspring) and the four accumulators below.
-    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2 };
+    // esim_ensemble_begin_paired (esim_host_compare.h) is the fourth: the reproduction kind's accumulators over the event rows of
+    // the kept baseline (plane 0) and of the run as it stands (plane 1).
+    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2, ROWS_PAIRED = 3 };
     struct Rows {
         uint32_t *hit = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
         unsigned long long *sum = nullptr, *sumsq = nullptr;
@@ -95,6 +97,7 @@ struct Ensemble {
         uint32_t r_num = 0, r_den = 0;            // ROWS_REPRODUCTION: hit where offspring / cases >= r_num / r_den (min: the smallest cohort)
         uint32_t *defined = nullptr;              // ROWS_REPRODUCTION: members with a cohort in the cell
         unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
+        uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
     } rows;
     bool series = false;
 };
@@ -103,6 +106,16 @@ struct Ensemble {
 struct Groups {
     uint16_t *lab = nullptr; uint32_t n = 0;
     uint32_t *size = nullptr, *cnt = nullptr;
+};
+
+// esim_baseline_keep: the exposure step of every citizen of a finished run, one uint32 per citizen on the device (0 for an index
+// case, ESIM_NEVER for a citizen the log did not hold), with the steps run, the parameters then in force and the number of log
+// entries.  The plane is allocated at the first keep and reused; held == false: none is kept (dropped, or never taken).
+struct Baseline {
+    uint32_t *plane = nullptr;
+    bool held = false;
+    uint32_t steps = 0, n_cases = 0;
+    esim_params P;
 };
 
 // esim_snapshot: the state at rest after `step` completed steps, kept on the device, with the parameters then in force; the
@@ -194,6 +207,7 @@ struct esim_ctx_impl {
     Ensemble ens;
     Groups grp;
     Snapshot snap;
+    Baseline base;
     Seam seam;
     DrawSeam draw_seam;               // of the history the context stands on
     DrawSeam snap_draw_seam;          // of the history under the snapshot held (esim_snapshot copies it, esim_rollback starts from it)

@@ -2,7 +2,8 @@
 // esim_setting_series, folded by k_ensemble_fold_rows and read by esim_ensemble_read_series), esim_ensemble_begin_reproduction
 // and esim_ensemble_read_reproduction (the cohort rows of esim_reproduction_series, folded by k_ensemble_fold_ratio), and what
 // esim_ensemble_fold does with one of them in force.  Two more kinds of Ensemble::Rows, beside the series kind of
-// esim_host_outputs.h; the replays are those of esim_host_settings.h and esim_host_tree.h, unchanged.
+// esim_host_outputs.h; the replays are those of esim_host_settings.h and esim_host_tree.h, unchanged.  The paired kind of
+// esim_host_compare.h shares the allocation (ensrows_begin) and the read-out (read_two_planes) of the reproduction kind.
 namespace {
 
 // What both begins refuse alike behind their own argument checks: the state errors of esim_ensemble_begin_series.
@@ -18,7 +19,7 @@ int ensrows_begin_check(esim_ctx_impl *c, const std::string &who, int where)
 // shape in force are kept; any other is allocated before the earlier one goes, so that a refusal leaves everything as it was.
 int ensrows_begin(esim_ctx_impl *c, const std::string &who, int kind, uint32_t n_rows, uint32_t cols)
 {
-    const bool ratio = kind == Ensemble::ROWS_REPRODUCTION;
+    const bool ratio = kind == Ensemble::ROWS_REPRODUCTION || kind == Ensemble::ROWS_PAIRED;   // (two planes, two counters, five sums)
     const size_t cells = (size_t)n_rows * cols;
     Ensemble::Rows &old = c->ens.rows;
     if (!old.hit || old.kind != kind || old.n_rows != n_rows || old.n_cols != cols) {
@@ -91,6 +92,29 @@ int fold_transmission(esim_ctx_impl *c)
     return tree_finish(c, who, &w);
 }
 
+// The read-out of the two kinds with two planes (reproduction, paired): rows [first_row, first_row + n) of the two counters and
+// the five sums, any pointer NULL.
+int read_two_planes(esim_ctx_impl *c, const std::string &who, int kind, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *defined, uint32_t *hit,
+                    uint64_t *sum_0, uint64_t *sum_1, uint64_t *sumsq_0, uint64_t *sumsq_1, uint64_t *sum_cross)
+{
+    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit || c->ens.rows.kind != kind)
+        return fail(c, ESIM_ESTATE, who + ": no population uploaded, or no begin of this kind in force since the upload (or, by group, since esim_set_groups)");
+    const Ensemble::Rows &r = c->ens.rows;
+    if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, who + ": rows outside the accumulators");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for whatever is on the stream)
+    const size_t at = (size_t)first_row * r.n_cols, cells = (size_t)n * r.n_cols;
+    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const std::pair<uint32_t *, const uint32_t *> words[] = { { defined, r.defined }, { hit, r.hit } };
+    for (const auto &w : words)
+        if (w.first && cells) HIP_TRY(c, hipMemcpy(w.first, w.second + at, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
+    const std::pair<uint64_t *, const unsigned long long *> sums[] = { { sum_0, r.sum }, { sum_1, r.sum_o }, { sumsq_0, r.sumsq }, { sumsq_1, r.sumsq_o }, { sum_cross, r.cross } };
+    for (const auto &s : sums)
+        if (s.first && cells) HIP_TRY(c, hipMemcpy(s.first, s.second + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
+    return ctrl_error(c, h);
+}
+
 }  // namespace
 
 extern "C" int esim_ensemble_begin_settings(esim_ctx *ctx, int where, uint32_t setting_mask, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t min_cases)
@@ -130,20 +154,6 @@ extern "C" int esim_ensemble_read_reproduction(esim_ctx *ctx, uint32_t first_row
                                                uint64_t *sum_cases, uint64_t *sum_offspring, uint64_t *sumsq_cases, uint64_t *sumsq_offspring, uint64_t *sum_cross)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit || c->ens.rows.kind != Ensemble::ROWS_REPRODUCTION)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_reproduction: no population uploaded, or no esim_ensemble_begin_reproduction in force since the upload (or, by group, since esim_set_groups)");
-    const Ensemble::Rows &r = c->ens.rows;
-    if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, "esim_ensemble_read_reproduction: rows outside the accumulators");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    Ctrl h; int rc;
-    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for whatever is on the stream)
-    const size_t at = (size_t)first_row * r.n_cols, cells = (size_t)n * r.n_cols;
-    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const std::pair<uint32_t *, const uint32_t *> words[] = { { defined, r.defined }, { hit, r.hit } };
-    for (const auto &w : words)
-        if (w.first && cells) HIP_TRY(c, hipMemcpy(w.first, w.second + at, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
-    const std::pair<uint64_t *, const unsigned long long *> sums[] = { { sum_cases, r.sum }, { sum_offspring, r.sum_o }, { sumsq_cases, r.sumsq }, { sumsq_offspring, r.sumsq_o }, { sum_cross, r.cross } };
-    for (const auto &s : sums)
-        if (s.first && cells) HIP_TRY(c, hipMemcpy(s.first, s.second + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
-    return ctrl_error(c, h);
+    return read_two_planes(c, "esim_ensemble_read_reproduction", Ensemble::ROWS_REPRODUCTION, first_row, n, members, defined, hit,
+                           sum_cases, sum_offspring, sumsq_cases, sumsq_offspring, sum_cross);
 }

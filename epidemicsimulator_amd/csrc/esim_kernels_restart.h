@@ -134,9 +134,23 @@ __device__ __forceinline__ void ratio_pair(const RatioAcc &a, uint64_t j, uint32
     *sc = vsc; *so = vso; *qc = vqc; *qo = vqo; *x = vx;
 }
 
-// The same over the cohort rows (esim_ensemble_begin_reproduction): c[cell] and o[cell] are the cases and the offspring
-// k_tree_rows has just left in the two kept planes.  Per cell: defined += (c >= min_cohort), min_cohort >= 1; hit += 1 where
-// that holds and o / c >= r_num / r_den; the five sums always.  The shape of k_ensemble_fold_rows: a lane owns its cells (plain
+// What decides `defined` and `hit` of one cell of the two-plane fold: the reproduction kind's rule and the paired kind's.  The
+// five sums are the same for both.
+struct RatioRule {                  // esim_ensemble_begin_reproduction: a cohort of at least min_cohort cases; o / c >= r_num / r_den
+    uint32_t min_cohort, r_num, r_den;
+    __device__ __forceinline__ uint32_t defined(uint32_t c) const { return c >= min_cohort; }
+    __device__ __forceinline__ uint32_t hit(uint32_t c, uint32_t o) const { return ratio_hit(c, o, r_num, r_den); }
+};
+struct PairedRule {                 // esim_ensemble_begin_paired: c = the baseline's cases, o = the current run's; b - c >= min_averted as signed
+    uint32_t min_baseline, min_averted;
+    __device__ __forceinline__ uint32_t defined(uint32_t c) const { return c >= min_baseline; }
+    __device__ __forceinline__ uint32_t hit(uint32_t c, uint32_t o) const { return (long long)c - (long long)o >= (long long)min_averted; }
+};
+
+// The same over two row planes (esim_ensemble_begin_reproduction: c[cell] and o[cell] are the cases and the offspring
+// k_tree_rows has just left in the two kept planes; esim_ensemble_begin_paired: the baseline's and the current run's event rows).
+// Per cell: defined += rule.defined(c); hit += 1 where that holds and rule.hit(c, o); the five sums always.  The shape of
+// k_ensemble_fold_rows: a lane owns its cells (plain
 // loads and stores), four cells per lane and trip, 16-byte loads of both planes and of defined and hit, 16-byte loads and stores
 // of the sums, two cells each; a grid capped by the caller strides over the rest, and the up to three cells behind the last
 // whole four are taken by the first lanes of workgroup 0.  Four cells whose c | o is all zero are neither read nor written in the
@@ -144,7 +158,8 @@ __device__ __forceinline__ void ratio_pair(const RatioAcc &a, uint64_t j, uint32
 // zero cells: before the epidemic has arrived a window costs the 8 B per cell of the planes and little else.  A cell with
 // offspring but no cases (a cohort the window's column does not hold) still adds to the sums: nothing here relies on o > 0
 // implying c > 0.
-__global__ __launch_bounds__(TPB) void k_ensemble_fold_ratio(const uint32_t *c, const uint32_t *o, uint64_t cells, uint32_t min_cohort, uint32_t r_num, uint32_t r_den, RatioAcc a)
+template <class Rule>
+__device__ __forceinline__ void fold_two_planes(const uint32_t *c, const uint32_t *o, uint64_t cells, const Rule rule, const RatioAcc &a)
 {
     if (blockIdx.x == 0u && threadIdx.x == 0u) *a.members += 1u;
     const uint4 *c4 = reinterpret_cast<const uint4 *>(c), *o4 = reinterpret_cast<const uint4 *>(o);
@@ -153,13 +168,13 @@ __global__ __launch_bounds__(TPB) void k_ensemble_fold_ratio(const uint32_t *c, 
     for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n4; i += stride) {
         const uint4 vc = c4[i], vo = o4[i];
         if (!(vc.x | vc.y | vc.z | vc.w | vo.x | vo.y | vo.z | vo.w)) continue;
-        const uint32_t dx = vc.x >= min_cohort, dy = vc.y >= min_cohort, dz = vc.z >= min_cohort, dw = vc.w >= min_cohort;
+        const uint32_t dx = rule.defined(vc.x), dy = rule.defined(vc.y), dz = rule.defined(vc.z), dw = rule.defined(vc.w);
         if (dx | dy | dz | dw) {
             uint4 d = d4[i];
             d.x += dx; d.y += dy; d.z += dz; d.w += dw;
             d4[i] = d;
-            const uint32_t hx = dx & ratio_hit(vc.x, vo.x, r_num, r_den), hy = dy & ratio_hit(vc.y, vo.y, r_num, r_den);
-            const uint32_t hz = dz & ratio_hit(vc.z, vo.z, r_num, r_den), hw = dw & ratio_hit(vc.w, vo.w, r_num, r_den);
+            const uint32_t hx = dx & rule.hit(vc.x, vo.x), hy = dy & rule.hit(vc.y, vo.y);
+            const uint32_t hz = dz & rule.hit(vc.z, vo.z), hw = dw & rule.hit(vc.w, vo.w);
             if (hx | hy | hz | hw) {
                 uint4 h = h4[i];
                 h.x += hx; h.y += hy; h.z += hz; h.w += hw;
@@ -172,10 +187,24 @@ __global__ __launch_bounds__(TPB) void k_ensemble_fold_ratio(const uint32_t *c, 
     const uint64_t tail = (n4 << 2) + threadIdx.x;
     if (blockIdx.x == 0u && threadIdx.x < (uint32_t)(cells & 3u)) {
         const uint32_t vc = c[tail], vo = o[tail];
-        if (vc >= min_cohort) { a.defined[tail] += 1u; if (ratio_hit(vc, vo, r_num, r_den)) a.hit[tail] += 1u; }
+        if (rule.defined(vc)) { a.defined[tail] += 1u; if (rule.hit(vc, vo)) a.hit[tail] += 1u; }
         if (vc | vo) {
             a.sum_c[tail] += vc; a.sum_o[tail] += vo;
             a.sq_c[tail] += (unsigned long long)vc * vc; a.sq_o[tail] += (unsigned long long)vo * vo; a.cross[tail] += (unsigned long long)vc * vo;
         }
     }
+}
+
+// The cohort rows: defined += (c >= min_cohort), min_cohort >= 1; hit += 1 where that holds and o / c >= r_num / r_den.
+__global__ __launch_bounds__(TPB) void k_ensemble_fold_ratio(const uint32_t *c, const uint32_t *o, uint64_t cells, uint32_t min_cohort, uint32_t r_num, uint32_t r_den, RatioAcc a)
+{
+    fold_two_planes(c, o, cells, RatioRule{min_cohort, r_num, r_den}, a);
+}
+
+// The paired rows (esim_ensemble_begin_paired): b[cell] and c[cell] are the event rows of the kept baseline and of the run as it
+// stands, as k_compare_rows has just left them.  defined += (b >= min_baseline); hit += 1 where that holds and b - c >=
+// min_averted as signed, min_averted >= 1; the sums are those of b, c, b * b, c * c and b * c.
+__global__ __launch_bounds__(TPB) void k_ensemble_fold_paired(const uint32_t *b, const uint32_t *c, uint64_t cells, uint32_t min_baseline, uint32_t min_averted, RatioAcc a)
+{
+    fold_two_planes(b, c, cells, PairedRule{min_baseline, min_averted}, a);
 }

@@ -98,6 +98,46 @@ def reproduction_summary(acc, first_step=0, stride=24):
             "r": r, "p_r": p_r, "r_se": r_se, "steps": int(first_step) + int(stride) * np.arange(sx.shape[0], dtype=np.int64)}
 
 
+def _spread(m, s, ss):
+    """m * sum x^2 - (sum x)^2 = m * sum (x - mean)^2 per cell, exactly, from integer sums and as float64: in int64 where every
+    term stays below 2^62, in Python integers otherwise."""
+    s, ss = np.asarray(s), np.asarray(ss)
+    top_s, top_ss = (int(np.abs(a).max()) if a.size else 0 for a in (s, ss))
+    kind = np.int64 if max(top_s * top_s, m * top_ss) < 1 << 62 else object
+    s, ss = s.astype(kind), ss.astype(kind)
+    return (m * ss - s * s).astype(np.float64)
+
+
+def paired_summary(acc, first_step=0, stride=24):
+    """From Simulator.ensemble_read_paired(): members, defined, hit; mean_baseline, mean_policy and mean_averted = mean_baseline -
+    mean_policy over the members; p_averted = hit / defined, the share of the members with enough baseline cases in the cell
+    that averted at least min_averted of them, NaN where none had; se_paired, the standard error of mean_averted from the
+    variance of the members' DIFFERENCES -- sum d^2 = sumsq_baseline - 2 sum_cross + sumsq_current, sample variance (ddof = 1) --;
+    se_unpaired = sqrt((var_b + var_c) / members), what two separate ensembles of the same size would quote; both NaN for
+    fewer than two members; and steps, the first step of every row."""
+    m = int(acc["members"])
+    sb, sc = np.asarray(acc["sum_baseline"], np.uint64), np.asarray(acc["sum_current"], np.uint64)
+    sbb, scc, sbc = (np.asarray(acc[k], np.uint64) for k in ("sumsq_baseline", "sumsq_current", "sum_cross"))
+    defined, hit = np.asarray(acc["defined"], np.uint32), np.asarray(acc["hit"], np.uint32)
+    fb, fc = sb.astype(np.float64), sc.astype(np.float64)
+    diff = sb.astype(np.int64) - sc.astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p_averted = np.where(defined > 0, hit.astype(np.float64) / defined.astype(np.float64), np.nan)
+    if m >= 2:
+        wide = max((int(a.max()) if a.size else 0) for a in (sbb, scc, sbc)) >= 1 << 60
+        sq = (lambda a: a.astype(object)) if wide else (lambda a: a.astype(np.int64))
+        sdd = sq(sbb) - 2 * sq(sbc) + sq(scc)                     # sum over members of (b - c)^2, exact
+        scale = float(m) * m * (m - 1.0)                          # _spread / (m (m - 1)) is the sample variance; / m again its mean's
+        se_paired = np.sqrt(np.maximum(_spread(m, diff, sdd), 0.0) / scale)
+        se_unpaired = np.sqrt((np.maximum(_spread(m, sb, sbb), 0.0) + np.maximum(_spread(m, sc, scc), 0.0)) / scale)
+    else:
+        se_paired, se_unpaired = np.full(sb.shape, np.nan), np.full(sb.shape, np.nan)
+    zeros = np.zeros_like(fb)
+    return {"members": m, "defined": defined, "hit": hit, "mean_baseline": fb / m if m else zeros, "mean_policy": fc / m if m else zeros,
+            "mean_averted": diff.astype(np.float64) / m if m else zeros, "p_averted": p_averted, "se_paired": se_paired, "se_unpaired": se_unpaired,
+            "steps": int(first_step) + int(stride) * np.arange(sb.shape[0], dtype=np.int64)}
+
+
 def _json_number(x):
     x = float(x)
     return None if x != x else x          # NaN (an arrival mean nobody contributed to) is written as null
@@ -380,6 +420,50 @@ class EventResult:
         """ensemble_events.npz: sizes and the five [members, top] arrays of the largest events."""
         os.makedirs(directory, exist_ok=True)
         np.savez(os.path.join(directory, "ensemble_events.npz"), sizes=self.sizes, **{k: getattr(self, k) for k in self.KEYS})
+
+
+class CompareResult:
+    """What Ensemble.compare gathers: every member's comparison of its policy run with its own baseline run."""
+
+    KEYS = ("steps", "defined", "hit", "mean_baseline", "mean_policy", "mean_averted", "p_averted", "se_paired", "se_unpaired")
+
+    def __init__(self, members, counts, delay, first_divergence, records_baseline, records_policy, summary=None, where="all", area_codes=None):
+        self.members = list(members)      # the overrides of every member
+        self.counts = np.asarray(counts, np.uint64)                  # uint64 [members, n_cols, 5]: _lib.CMP_BOTH .. CMP_LATER
+        self.delay = np.asarray(delay, np.int64)                     # int64 [members, n_cols]: sum of (step under the policy - step in the baseline) over BOTH
+        self.first_divergence = np.asarray(first_divergence, np.int64)   # int64 [members]: the first step the arms differ at, -1 where they are identical
+        self.records_baseline = records_baseline                     # structured [members, n_steps]
+        self.records_policy = records_policy
+        self.summary = summary            # paired_summary(...) where rows were asked for, else None
+        self.where = where
+        self.area_codes = area_codes
+
+    @classmethod
+    def gathered(cls, members, tables, records_baseline, records_policy, n_cols, n_steps, summary=None, where="all", area_codes=None):
+        """From every member's Simulator.compare() dict and the records of its two arms."""
+        k = len(tables)
+        counts = np.stack([t["counts"] for t in tables]) if k else np.zeros((0, n_cols, _lib.CMP_N), np.uint64)
+        delay = np.stack([t["delay"] for t in tables]) if k else np.zeros((0, n_cols), np.int64)
+        div = [-1 if t["first_divergence"] is None else t["first_divergence"] for t in tables]
+        stack = lambda rows: np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
+        return cls(members, counts, delay, div, stack(records_baseline), stack(records_policy), summary, where, area_codes)
+
+    def averted(self):
+        """int64 [members, n_cols]: the cases the policy averted net of those it added, AVERTED - ADDED."""
+        c = self.counts.astype(np.int64)
+        return c[..., _lib.CMP_AVERTED] - c[..., _lib.CMP_ADDED]
+
+    def dump(self, directory):
+        """ensemble_compare.npz: counts, delay, first_divergence, averted, the class names, and the arrays of the summary (with a
+        summary_ prefix) where rows were asked for; codes where area codes name the columns."""
+        os.makedirs(directory, exist_ok=True)
+        arrays = dict(counts=self.counts, delay=self.delay, first_divergence=self.first_divergence, averted=self.averted(), names=np.asarray(_lib.CMP_NAMES))
+        if self.summary is not None:
+            arrays.update({"summary_" + k: self.summary[k] for k in self.KEYS})
+            arrays["summary_members"] = np.asarray(self.summary["members"], np.uint32)
+        if self.area_codes is not None:
+            arrays["codes"] = np.asarray(self.area_codes)
+        np.savez(os.path.join(directory, "ensemble_compare.npz"), **arrays)
 
 
 _KINDS = ("census", "arrival", "series", "settings", "reproduction")
@@ -702,6 +786,71 @@ class Ensemble:
         summary = self._summary(kind, area)
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
+
+    _FIXED_BY_HISTORY = ("exposed_time", "infected_time", "start_hour", "end_hour")
+
+    def compare(self, baseline, policy, members, n_steps, history_steps=None, where="all", rows=None):
+        """A policy against a baseline, member by member and PAIRED: every member (as for run()) is run for n_steps steps under
+        the base parameters changed by `baseline` and by its own overrides, that run is kept on the device
+        (Simulator.keep_baseline), and the member is run again under `policy` instead of `baseline` with the same seed and the
+        same index cases.  The two runs share their random numbers, so what Simulator.compare(where) then counts -- gathered
+        per member -- is the policy's effect and not noise.  baseline, policy: override dicts on the base parameters.
+        rows: None, or dict(first_step=..., n_rows=..., stride=..., cumulative=..., min_baseline=..., min_averted=...): every
+        member is also folded into the paired accumulators (Simulator.ensemble_begin_paired) and the result carries
+        paired_summary of them.  history_steps: None, or the steps of a shared history that is run once under the base
+        parameters and kept (Simulator.snapshot); both arms of every member are then branches from it (the rules of forecast():
+        no "index_cases" in a member, no other times or working hours in baseline or policy -- ValueError).  Returns a
+        CompareResult."""
+        sim = self.simulator
+        n_steps = int(n_steps)
+        baseline, policy = dict(baseline), dict(policy)
+        members = self._members(members)
+        place = sim._compare_place("Ensemble.compare", where)
+        if "index_cases" in baseline or "index_cases" in policy:
+            raise ValueError("Ensemble.compare: the index cases belong to the member, not to an arm (the pairing needs the same ones in both)")
+        if history_steps is not None:
+            history_steps = int(history_steps)
+            if not 1 <= history_steps <= n_steps:
+                raise ValueError("Ensemble.compare: history_steps must be in 1..n_steps")
+            if any("index_cases" in m for m in members):
+                raise ValueError("Ensemble.compare: a branch cannot change the index cases of the shared history")
+            fixed = sorted(k for k in self._FIXED_BY_HISTORY if k in baseline or k in policy)
+            if fixed:
+                raise ValueError("Ensemble.compare: %s cannot change behind a shared history" % ", ".join(fixed))
+        if rows is not None:
+            unknown = set(rows) - {"first_step", "n_rows", "stride", "cumulative", "min_baseline", "min_averted"}
+            if unknown:
+                raise ValueError("Ensemble.compare: rows takes first_step, n_rows, stride, cumulative, min_baseline and min_averted, got %s" % sorted(unknown))
+            rows = dict(rows)
+            first, n_rows, stride = sim._compare_rows("Ensemble.compare", rows.get("first_step", 0), rows.get("n_rows"), rows.get("stride", 24), n_steps)
+            rows.update(first_step=first, n_rows=n_rows, stride=stride)
+            sim.ensemble_begin_paired(where, **rows)
+        history = np.zeros(0, RECORD_DTYPE)
+        if history_steps is not None:
+            sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
+            self._own_seeds = True
+            history = sim.run(history_steps)
+            sim.snapshot()
+
+        def arm(over, m):
+            if history_steps is None:
+                self._restart_member(dict(over, **m))
+                return sim.run(n_steps)
+            sim.rollback(**dict(over, **m))
+            rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
+            return np.concatenate([history, rec])
+
+        tables, rec_b, rec_p = [], [], []
+        for m in members:
+            rec_b.append(pad_records(arm(baseline, m), n_steps))
+            sim.keep_baseline()
+            rec_p.append(pad_records(arm(policy, m), n_steps))
+            tables.append(sim.compare(where, 0, n_steps))
+            if rows is not None:
+                sim.ensemble_fold()
+        summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
+        codes = self.area_codes if place == _lib.AREA_HOME else None
+        return CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
 
     def close(self):
         self.simulator.close()

@@ -258,6 +258,124 @@ class Simulator:
             self.statistics_recorder = StatisticsRecorder()
             self.statistics_recorder.push_block(self.records_so_far())
 
+    # -- paired policy comparison: a kept baseline run and the run as it stands (esim_baseline_*, esim_compare*) -------
+    @staticmethod
+    def _compare_place(who, where):
+        """`where` of the comparison calls as its code; anything but "all", "home" and "group" raises ValueError."""
+        places = {"all": _lib.BY_ALL, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}
+        if isinstance(where, str):
+            if where not in places:
+                raise ValueError("%s: where must be 'all', 'home' or 'group', got %r" % (who, where))
+            return places[where]
+        if isinstance(where, (bool, float)) or where not in places.values():
+            raise ValueError("%s: where must be 'all', 'home' or 'group', got %r" % (who, where))
+        return int(where)
+
+    def _compare_cols(self, place):
+        return 1 if place == _lib.BY_ALL else max(1, self._n_groups) if place == _lib.BY_GROUP else self.population.n_areas
+
+    @staticmethod
+    def _compare_rows(who, first_step, n_rows, stride, last):
+        """(first_step, n_rows, stride) of event rows that may start at step 0, checked; n_rows=None: up to step `last` (a
+        number, or a function that gives it: asked only once the other arguments stand)."""
+        first, stride = int(first_step), int(stride)
+        if first < 0 or stride < 1:
+            raise ValueError("%s: first_step must be >= 0 and stride >= 1" % who)
+        if n_rows is None:
+            last = int(last() if callable(last) else last)
+            n_rows = (last - first) // stride + 1 if first <= last else 0
+        if int(n_rows) < 1:
+            raise ValueError("%s: no rows (first_step %d lies beyond the last step, or n_rows < 1)" % (who, first))
+        return first, int(n_rows), stride
+
+    def keep_baseline(self):
+        """Keeps the exposure step of every citizen of the run as it stands on the device (esim_baseline_keep): the baseline
+        that compare() and compare_series() set a later run against.  It survives reset, restart, snapshot and rollback."""
+        _lib.check(self.lib.esim_baseline_keep(self._ctx), self._ctx)
+
+    def baseline_info(self):
+        """{"steps", "n_cases", "params"} of the baseline kept (esim_baseline_info): the steps it ran, the entries of its
+        exposure log (index cases included) and the parameters it ran under."""
+        steps, cases, p = C.c_uint32(0), C.c_uint32(0), _lib.Params()
+        _lib.check(self.lib.esim_baseline_info(self._ctx, C.byref(steps), C.byref(cases), C.byref(p)), self._ctx)
+        return {"steps": int(steps.value), "n_cases": int(cases.value), "params": p}
+
+    def drop_baseline(self):
+        """Forgets the baseline kept (esim_baseline_drop)."""
+        _lib.check(self.lib.esim_baseline_drop(self._ctx), self._ctx)
+
+    def _compare_last(self):
+        """The last step both runs have, the window's default end (without a baseline: of this run; the library refuses then)."""
+        steps = C.c_uint32(0)
+        if self.lib.esim_baseline_info(self._ctx, C.byref(steps), None, None) != _lib.OK:
+            return self._steps
+        return min(self._steps, int(steps.value))
+
+    def compare(self, where="all", first_step=0, last_step=None, citizens=False):
+        """The run as it stands against the baseline kept (esim_compare), a dict: counts, uint64 [n_cols, 5] -- per column the
+        citizens that are a case (exposed in steps first_step .. last_step; step 0: the index cases) in both runs, in the
+        baseline only (averted), in this run only (added), and of those in both the ones exposed earlier and later here
+        (_lib.CMP_*); delay, int64 [n_cols]: the sum of (step here - step in the baseline) over the cases of both;
+        first_divergence: the first step at which the two histories differ, None when they are identical; and with
+        citizens=True cls, uint8 [n_citizens]: 0 neither, 1 both, 2 averted, 3 added.  where: "all" (one column), "home" (by
+        the Output Area of the household) or "group".  last_step=None: the last step of the shorter run."""
+        place = self._compare_place("compare", where)
+        first = int(first_step)
+        if first < 0 or (last_step is not None and int(last_step) < first):
+            raise ValueError("compare: steps %d..%s are no window" % (first, last_step))
+        last = self._compare_last() if last_step is None else int(last_step)
+        cols = self._compare_cols(place)
+        counts, delay, div = np.zeros((cols, _lib.CMP_N), np.uint64), np.zeros(cols, np.int64), C.c_uint32(0)
+        cls = np.zeros(self.population.n_citizens, np.uint8) if citizens else None
+        _lib.check(self.lib.esim_compare(self._ctx, place, first, last, counts.ctypes.data_as(C.POINTER(C.c_uint64)), delay.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         C.byref(div), cls.ctypes.data_as(C.POINTER(C.c_uint8)) if citizens else None), self._ctx)
+        out = {"counts": counts, "delay": delay, "first_divergence": None if div.value == _lib.NEVER else int(div.value)}
+        if citizens:
+            out["cls"] = cls
+        return out
+
+    def compare_series(self, where="all", first_step=0, n_rows=None, stride=24, cumulative=False):
+        """(baseline, current), uint32 [n_rows, n_cols] each (esim_compare_series): row i holds the cases of the `stride` steps
+        from first_step + i * stride on in the baseline kept and in the run as it stands (step 0: the index cases); with
+        cumulative=True the cases from first_step up to the row's last step.  baseline - current is the cases averted by row.
+        where as for compare(); n_rows=None: up to the last step of the shorter run."""
+        place = self._compare_place("compare_series", where)
+        first, n_rows, stride = self._compare_rows("compare_series", first_step, n_rows, stride, self._compare_last)
+        cols = self._compare_cols(place)
+        base, cur = np.zeros((n_rows, cols), np.uint32), np.zeros((n_rows, cols), np.uint32)
+        _lib.check(self.lib.esim_compare_series(self._ctx, place, first, n_rows, stride, int(bool(cumulative)), base.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                cur.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return base, cur
+
+    def ensemble_begin_paired(self, where="all", first_step=0, n_rows=None, stride=24, cumulative=False, min_baseline=1, min_averted=1):
+        """Accumulators over the paired rows (esim_ensemble_begin_paired): a member contributes the (baseline, current) rows
+        compare_series(where, first_step, n_rows, stride, cumulative) would return for it.  Per cell ensemble_fold counts the
+        members with at least min_baseline cases in the baseline (defined), those of them with baseline - current >=
+        min_averted (hit), and sums both counts, their squares and their product, in integers on the device.  n_rows=None: up
+        to the last step of the run (params.max_steps); ensemble_read_paired reads them."""
+        place = self._compare_place("ensemble_begin_paired", where)
+        first, n_rows, stride = self._compare_rows("ensemble_begin_paired", first_step, n_rows, stride, int(self.params.max_steps))
+        if int(min_averted) < 1 or int(min_baseline) < 0:
+            raise ValueError("ensemble_begin_paired: min_averted must be >= 1 and min_baseline >= 0")
+        _lib.check(self.lib.esim_ensemble_begin_paired(self._ctx, place, first, n_rows, stride, int(bool(cumulative)), int(min_baseline), int(min_averted)), self._ctx)
+        self._ens_rows = n_rows
+        self._ens_n = self._compare_cols(place)
+
+    PAIRED_KEYS = ("defined", "hit", "sum_baseline", "sum_current", "sumsq_baseline", "sumsq_current", "sum_cross")
+
+    def ensemble_read_paired(self, first_row=0, n_rows=None):
+        """{"members": int, "defined", "hit": uint32 [n, n_cols], "sum_baseline", "sum_current", "sumsq_baseline",
+        "sumsq_current", "sum_cross": uint64 [n, n_cols]}: rows [first_row, first_row + n) of the accumulators begun by
+        ensemble_begin_paired; n_rows=None: all from first_row on."""
+        total = getattr(self, "_ens_rows", 0)
+        n = max(0, total - int(first_row)) if n_rows is None else int(n_rows)
+        cols = getattr(self, "_ens_n", 1)
+        members = C.c_uint32(0)
+        out = {k: np.zeros((n, cols), np.uint32 if i < 2 else np.uint64) for i, k in enumerate(self.PAIRED_KEYS)}
+        ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint32 if i < 2 else C.c_uint64)) for i, k in enumerate(self.PAIRED_KEYS)]
+        _lib.check(self.lib.esim_ensemble_read_paired(self._ctx, int(first_row), n, C.byref(members), *ptrs), self._ctx)
+        return dict(out, members=int(members.value))
+
     def seeds(self):
         """The distinct initially infected citizens in force, in the order of the exposure log (esim_get_seeds)."""
         n = C.c_uint32(0)

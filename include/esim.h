@@ -880,6 +880,75 @@ int  esim_snapshot(esim_ctx *ctx);
 int  esim_rollback(esim_ctx *ctx, const esim_params *p);
 int  esim_snapshot_info(esim_ctx *ctx, uint32_t *step, esim_params *p);
 int  esim_snapshot_drop(esim_ctx *ctx);
+/* Paired policy comparison: cases averted against a kept baseline run.  Every draw is a pure function of (seed, global citizen,
+ * step, slot), so two runs of one population under the same seed and index cases share their random numbers by construction:
+ * a citizen exposed in one run and not in the other is an effect of what differs between them, not noise.  No step kernel is
+ * involved: a run that never asks pays nothing, and every output is an exact integer.
+ * esim_baseline_keep turns the exposure log as it stands into one uint32 per citizen ON THE DEVICE: its exposure step, 0 for an
+ *        index case, ESIM_NEVER for a citizen the log does not hold.  The step comes from the entry's position in the log (the
+ *        citizen word loses it once the citizen is vaccinated).  Kept with it: the steps run, the parameters in force and the
+ *        number of log entries.  4 B per citizen, allocated at the first keep and reused; one baseline per context, a later keep
+ *        replaces it.  Everything runs on the context's stream behind one read of the control block; nothing proportional to the
+ *        population goes to the host.  The baseline is kept through esim_reset, esim_restart, esim_restart_seeded, esim_snapshot,
+ *        esim_rollback and esim_checkpoint_restore, and dropped by a new upload, esim_baseline_drop and esim_destroy.  It is no
+ *        simulation state: no checkpoint holds it.  ESIM_ESTATE before an upload and on a context whose communicator has more
+ *        than one rank or that holds a shard (the rule of esim_restart); ESIM_ENOMEM without device memory; a sticky device-side
+ *        error is reported as the series calls report it.
+ * esim_baseline_info: the steps, the log entries and the parameters of the baseline kept; any pointer may be NULL.  Pure host code.
+ * esim_baseline_drop: forgets it (the plane stays for the next keep).  Both are ESIM_ESTATE without a baseline.
+ * esim_compare: the run as it stands against the baseline.  A citizen is a CASE of a run in the window when its exposure step s
+ *        satisfies first_step <= s <= last_step; first_step 0 takes the index cases in, as esim_reproduction_series does.  With b
+ *        the baseline's step and c the current run's, counts[col * ESIM_CMP_N + class]:
+ *          ESIM_CMP_BOTH     a case in both runs           ESIM_CMP_EARLIER  of BOTH, c < b
+ *          ESIM_CMP_AVERTED  a case in the baseline only   ESIM_CMP_LATER    of BOTH, c > b
+ *          ESIM_CMP_ADDED    a case in the current run only
+ *        delay[col] is the sum of c - b over BOTH, signed.  where = ESIM_BY_ALL (one column), ESIM_AREA_HOME (n_areas columns, by
+ *        the Output Area of the household) or ESIM_BY_GROUP (n_groups columns, ESIM_ESTATE without labels); any other `where` is
+ *        ESIM_EINVAL.  *first_divergence is the smallest step at which the two histories differ: the minimum, over the citizens
+ *        with b != c, of the smaller of the two steps, ESIM_NEVER counting as infinite; ESIM_NEVER for identical histories.  It is
+ *        not restricted to the window.  cls[citizen] is 0 for neither, 1 BOTH, 2 AVERTED, 3 ADDED.  Any output may be NULL; with
+ *        all of them NULL the call still runs and returns its status.  ESIM_ERANGE when last_step < first_step or last_step lies
+ *        beyond the steps of either run; ESIM_ESTATE without a baseline; the other errors are those of esim_baseline_keep.  A
+ *        refused call leaves the outputs untouched.
+ * esim_compare_series: the event rows of both runs from the two planes, baseline[i * n_cols + col] and current[...]: row i holds
+ *        the cases of steps [first_step + i * stride, + stride), the index cases at step 0; with cumulative != 0 it holds the
+ *        steps [first_step, first_step + (i + 1) * stride), a prefix over the rows summed on the device.  `where` as above.
+ *        Either output may be NULL.  ESIM_EINVAL for stride 0 or no rows; ESIM_ERANGE when the last row's first step lies beyond
+ *        the steps of either run (rows are clipped to the steps run, as the incidence rows of esim_area_status_series are; unlike
+ *        them first_step 0 is allowed).  Averted by row is baseline - current, left to the caller: no signed plane exists.
+ * Both calls leave the simulation state, the records, the exposure log, the snapshot, the labels, the ensemble accumulators and
+ * the baseline as they are.  Temporary device memory, freed when the call returns: 4 B per citizen for the current run's plane
+ * (1 B more with cls), and the tables (28 B per column) or the rows (8 B per cell).
+ * Paired ensemble accumulators: one more kind of the accumulators over rows, beside series, settings and reproduction; one kind
+ * is in force at a time.  A member contributes the two row planes of esim_compare_series(where, first_step, n_rows, stride,
+ * cumulative), b = baseline[cell] and c = current[cell].  esim_ensemble_fold with this kind in force adds members += 1 once and
+ * per cell
+ *          if b >= min_baseline:  defined += 1, and hit += 1 iff b - c >= min_averted as signed (min_averted >= 1)
+ *          always:                sum_baseline += b; sum_current += c; sumsq_baseline += b * b; sumsq_current += c * c;
+ *                                 sum_cross += b * c
+ *        in integers, 48 B per cell beside two row planes of 4 B per cell: the mean averted is (sum_baseline - sum_current) /
+ *        members, and the variance of the PAIRED difference, (sumsq_baseline - 2 sum_cross + sumsq_current) / members - mean^2,
+ *        follows from unsigned sums alone.  hit / defined is P(at least min_averted cases averted).  The fold is ESIM_ESTATE
+ *        without a baseline and ESIM_ERANGE when the last row lies beyond either run, with nothing folded; it waits for the
+ *        stream.  The accumulators do not own the baseline: every member keeps its own before its policy run.  ESIM_EINVAL for a
+ *        null context, an unknown `where`, stride 0, no rows, min_averted 0.  Lifetime, shape changes, ESIM_ENOMEM and the other
+ *        ESIM_ESTATE cases are those of esim_ensemble_begin_reproduction.
+ * esim_ensemble_read_paired: rows [first_row, first_row + n) of these accumulators, addressed as esim_ensemble_read_reproduction
+ *        addresses its own; ESIM_ESTATE while another kind is in force -- and the other reads are ESIM_ESTATE while this one is. */
+enum { ESIM_CMP_BOTH = 0, ESIM_CMP_AVERTED, ESIM_CMP_ADDED, ESIM_CMP_EARLIER, ESIM_CMP_LATER, ESIM_CMP_N };
+int  esim_baseline_keep(esim_ctx *ctx);
+int  esim_baseline_info(esim_ctx *ctx, uint32_t *steps, uint32_t *n_cases, esim_params *p);
+int  esim_baseline_drop(esim_ctx *ctx);
+int  esim_compare(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step,
+                  uint64_t *counts /* [n_cols * ESIM_CMP_N] or NULL */, int64_t *delay /* [n_cols] or NULL */,
+                  uint32_t *first_divergence /* or NULL */, uint8_t *cls /* [n_citizens] or NULL */);
+int  esim_compare_series(esim_ctx *ctx, int where, uint32_t first_step, uint32_t n_rows, uint32_t stride, int cumulative,
+                         uint32_t *baseline /* [n_rows * n_cols] or NULL */, uint32_t *current /* same, or NULL */);
+int  esim_ensemble_begin_paired(esim_ctx *ctx, int where, uint32_t first_step, uint32_t n_rows, uint32_t stride, int cumulative,
+                                uint32_t min_baseline, uint32_t min_averted);
+int  esim_ensemble_read_paired(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *defined /* [n * n_cols] */,
+                               uint32_t *hit /* [n * n_cols] */, uint64_t *sum_baseline, uint64_t *sum_current, uint64_t *sumsq_baseline,
+                               uint64_t *sumsq_current, uint64_t *sum_cross /* [n * n_cols] each */);
 
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
