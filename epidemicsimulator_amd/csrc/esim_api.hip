@@ -29,6 +29,7 @@
 #include "esim_host_places.h"
 #include "esim_host_contacts.h"
 #include "esim_host_flows.h"
+#include "esim_host_curves.h"
 #include "esim_host_events.h"
 #include "esim_host_ckpt.h"
 #include "esim_host_snapshot.h"

@@ -85,7 +85,10 @@ struct Ensemble {
     // sum and sumsq for the cases, both planes (cases, offspring) and the four accumulators below.
     // esim_ensemble_begin_paired (esim_host_compare.h) is the fourth: the reproduction kind's accumulators over the event rows of
     // the kept baseline (plane 0) and of the run as it stands (plane 1).
-    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2, ROWS_PAIRED = 3 };
+    // esim_ensemble_begin_peaks (esim_host_curves.h) is the fifth: one row of columns, no kept plane -- a member's summary of its
+    // curves is computed in temporary memory --, two counters and six sums: the peak in sum / sumsq, its step in sum_o / sumsq_o,
+    // the duration in sum_d / sumsq_d.
+    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2, ROWS_PAIRED = 3, ROWS_PEAKS = 4 };
     struct Rows {
         uint32_t *hit = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
         unsigned long long *sum = nullptr, *sumsq = nullptr;
@@ -97,6 +100,8 @@ struct Ensemble {
         uint32_t r_num = 0, r_den = 0;            // ROWS_REPRODUCTION: hit where offspring / cases >= r_num / r_den (min: the smallest cohort)
         uint32_t *defined = nullptr;              // ROWS_REPRODUCTION: members with a cohort in the cell
         unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
+        uint32_t last = 0, threshold = 0;         // ROWS_PEAKS: the window [first, last], the threshold of the duration (mask: the statuses, min: min_peak)
+        unsigned long long *sum_d = nullptr, *sumsq_d = nullptr;   // ... sums of the duration and of its square
         uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
     } rows;
     bool series = false;

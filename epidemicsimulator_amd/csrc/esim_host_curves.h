@@ -1,0 +1,201 @@
+// esim_host_curves.h -- the shape of the epidemic curve per column: esim_curve_summary, and the peaks kind of the ensemble
+// accumulators, esim_ensemble_begin_peaks / esim_ensemble_read_peaks with what esim_ensemble_fold does while it is in force
+// (DESIGN 26).  The kernels: esim_kernels_curves.h around esim_curves.h; the pair engine: esim_host_flows.h; the run's shape and
+// the vaccination replay: esim_host_outputs.h.  Everything a call computes lives in temporary device memory.
+namespace {
+
+// What a summary is taken of.
+struct CurveSpec { int where; uint32_t mask, first, last, threshold; };
+
+// One call's device memory: the replay, the pair engine, the tile aggregates and the per-column tables.
+struct CurveWork {
+    DevTmp<uint32_t> vax, agg, words;           // words: steps, first, last [cols] each
+    DevTmp<unsigned long long> wide;            // best, person [cols] each
+    PairWork p;
+    CurveTabs t;
+    uint32_t cols = 0;
+};
+
+const uint32_t CURVE_MASK_E = 1u << ESIM_EXPOSED, CURVE_MASK_I = 1u << ESIM_INFECTED;
+
+// The arguments both entry points refuse alike; the window's end is checked by whoever knows the steps run.
+int curve_check(esim_ctx_impl *c, const std::string &who, const CurveSpec &s)
+{
+    if (s.where != ESIM_BY_ALL && s.where != ESIM_AREA_HOME && s.where != ESIM_BY_GROUP)
+        return fail(c, ESIM_EINVAL, who + ": `where` must be ESIM_BY_ALL, ESIM_AREA_HOME or ESIM_BY_GROUP (curves by the area stood in are not built)");
+    if (s.mask != CURVE_MASK_E && s.mask != CURVE_MASK_I && s.mask != (CURVE_MASK_E | CURVE_MASK_I))
+        return fail(c, ESIM_EINVAL, who + ": the status mask must be Exposed, Infected or both (the other statuses are monotone)");
+    if (s.threshold == 0u) return fail(c, ESIM_EINVAL, who + ": threshold 0");
+    if (!c->uploaded) return fail(c, ESIM_ESTATE, who + ": no population uploaded");
+    if (c->comm.world > 1 || c->d.n_global != c->d.n)
+        return fail(c, ESIM_ESTATE, who + ": the context has a communicator of several ranks or holds a shard (sharded curves are not built)");
+    if (s.where == ESIM_BY_GROUP && !c->grp.lab) return fail(c, ESIM_ESTATE, who + ": by group without labels (esim_set_groups)");
+    if (s.first == 0u || s.last < s.first) return fail(c, ESIM_ERANGE, who + ": first_step is 1-based, and last_step may not lie before it");
+    return ESIM_OK;
+}
+
+uint32_t curve_cols(const esim_ctx_impl *c, int where) { return where == ESIM_BY_ALL ? 1u : where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; }
+
+// The summary of the run as it stands into w->t, on the context's stream: the change points of every case's interval into the
+// pair table, compacted and sorted by (column, step), scanned per column and reduced.  The stream is waited for twice on the
+// way -- for the control block and the records, and for the number of distinct change points -- and not behind the reduction:
+// the caller waits.  A failure behind the first launch waits for the stream (flows_unwind): the kernels use the work struct's memory.
+int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, CurveWork *w)
+{
+    const uint32_t t_done = c->host_t - 1u;
+    if (s.last > t_done) return fail(c, ESIM_ERANGE, who + ": last_step lies beyond the steps run so far");
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const Dev &d = c->d;
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h)) || (rc = ctrl_error(c, h))) return rc;
+    RunShape shape;
+    if ((rc = run_shape(c, t_done, &shape))) return rc;
+    const bool replay = shape.trigger != 0u;
+    const uint32_t log_len = std::min<uint32_t>(h.log_len, d.n), cols = curve_cols(c, s.where);
+    w->cols = cols;
+    if ((replay && w->vax.alloc(d.n) != hipSuccess) || w->wide.alloc(2 * (size_t)cols) != hipSuccess || w->words.alloc(3 * (size_t)cols) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, ESIM_ENOMEM, who + ": no device memory for the vaccination replay (4 B per citizen) and the tables (28 B per column)");
+    }
+    uint32_t *vax = w->vax.p;
+    w->t.best = w->wide.p; w->t.person = w->wide.p + cols;
+    w->t.steps = w->words.p; w->t.first = w->words.p + cols; w->t.last = w->words.p + 2 * (size_t)cols;
+    if ((rc = pairs_begin(c, who, &w->p, (uint32_t)std::min<uint64_t>(2ull * log_len, 0xFFFFFFFFull)))) return rc;   // (two change points a case; beyond 2^30 it refuses)
+    hipError_t e = hipMemsetAsync(w->wide.p, 0, sizeof(unsigned long long) * 2 * (size_t)cols, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w->words.p, 0, sizeof(uint32_t) * 3 * (size_t)cols, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w->t.first, 0xFF, sizeof(uint32_t) * (size_t)cols, c->stream);
+    if (e == hipSuccess && replay) e = enqueue_vax_replay(c, shape.trigger, t_done, vax);
+    if (e != hipSuccess) return flows_unwind(c, fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)));
+    Series q = Series();
+    q.first = s.first; q.t_done = t_done; q.t_all = shape.t_all; q.vax_of = replay ? vax : nullptr; q.n_cols = cols;
+    q.key = s.where == ESIM_BY_ALL ? CURVE_BY_ALL : s.where == ESIM_BY_GROUP ? (uint32_t)KEY_GROUP : (uint32_t)KEY_HOME;
+    q.grp = s.where == ESIM_BY_GROUP ? c->grp.lab : nullptr;
+    hipLaunchKernelGGL(k_curve_events, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, s.mask, s.last, log_len, w->p.t);
+    if ((rc = pairs_sorted(c, &w->p))) return flows_unwind(c, rc);
+    if (w->p.dropped) {                                                      // (ESIM_PAIR_LOG2 too small: nothing is reduced)
+        (void)hipStreamSynchronize(c->stream);
+        return pairs_end(c, who, &w->p);
+    }
+    const uint32_t n = w->p.n;
+    if (w->agg.alloc(3 * (size_t)curve_tiles(n)) != hipSuccess) {
+        (void)hipGetLastError();
+        return flows_unwind(c, fail(c, ESIM_ENOMEM, who + ": no device memory for the tile aggregates of the scan"));
+    }
+    curve_scan_enqueue(w->p.out_key.p, w->p.out_cnt.p, n, w->agg.p, c->stream);
+    curve_reduce_enqueue(w->p.out_key.p, w->p.out_cnt.p, n, cols, s.last, s.threshold, w->t, c->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return flows_unwind(c, fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)));
+    return ESIM_OK;
+}
+
+}  // namespace
+
+extern "C" int esim_curve_summary(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step, uint32_t threshold,
+                                  uint32_t *peak, uint32_t *peak_step, uint32_t *steps_at_least, uint32_t *first_at_least, uint32_t *last_at_least, uint64_t *person_steps)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_curve_summary";
+    const CurveSpec s = { where, status_mask, first_step, last_step, threshold };
+    if (int rc = curve_check(c, who, s)) return rc;
+    CurveWork w;
+    if (int rc = curve_enqueue(c, who, s, &w)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = pairs_end(c, who, &w.p)) return rc;
+    const size_t cols = w.cols;
+    std::vector<unsigned long long> wide(2 * cols);
+    std::vector<uint32_t> words(3 * cols);
+    HIP_TRY(c, hipMemcpy(wide.data(), w.wide.p, sizeof(unsigned long long) * 2 * cols, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(words.data(), w.words.p, sizeof(uint32_t) * 3 * cols, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < cols; ++k) {
+        const uint32_t top = (uint32_t)(wide[k] >> 32), n_at = words[k];
+        if (peak) peak[k] = top;
+        if (peak_step) peak_step[k] = top ? ~(uint32_t)wide[k] : ESIM_NEVER;
+        if (steps_at_least) steps_at_least[k] = n_at;
+        if (first_at_least) first_at_least[k] = words[cols + k];
+        if (last_at_least) last_at_least[k] = n_at ? words[2 * cols + k] : ESIM_NEVER;
+        if (person_steps) person_steps[k] = wide[cols + k];
+    }
+    return ESIM_OK;
+}
+
+namespace {
+// One member folded into the accumulators of the peaks kind: its summary in temporary memory, the fold kernel, the wait.
+int fold_peaks(esim_ctx_impl *c)
+{
+    Ensemble::Rows &r = c->ens.rows;
+    const std::string who = "esim_ensemble_fold";
+    const CurveSpec s = { c->ens.where, r.mask, r.first, r.last, r.threshold };
+    if (int rc = curve_check(c, who, s)) return rc;
+    if (curve_cols(c, s.where) != r.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
+    CurveWork w;
+    if (int rc = curve_enqueue(c, who, s, &w)) return rc;
+    PeakAcc a;
+    a.defined = r.defined; a.hit = r.hit; a.members = r.members;
+    a.sum_peak = r.sum; a.sq_peak = r.sumsq; a.sum_step = r.sum_o; a.sq_step = r.sumsq_o; a.sum_dur = r.sum_d; a.sq_dur = r.sumsq_d;
+    hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_for(r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, r.min, a);
+    hipError_t e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(c->stream);                   // (the temporary tables go when the call returns)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
+    return pairs_end(c, who, &w.p);
+}
+}  // namespace
+
+extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step, uint32_t threshold, uint32_t min_peak)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_ensemble_begin_peaks";
+    if (min_peak == 0u) return fail(c, ESIM_EINVAL, who + ": min_peak 0");
+    const CurveSpec s = { where, status_mask, first_step, last_step, threshold };
+    if (int rc = curve_check(c, who, s)) return rc;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    const uint32_t cols = curve_cols(c, where);
+    Ensemble::Rows &old = c->ens.rows;
+    if (!old.hit || old.kind != Ensemble::ROWS_PEAKS || old.n_cols != cols) {
+        // another kind or shape: the new one is allocated before the old one goes, so that a refusal leaves everything as it was
+        Ensemble::Rows r;
+        int rc;
+        if ((rc = dev_alloc(c, &r.hit, cols)) || (rc = dev_alloc(c, &r.defined, cols)) || (rc = dev_alloc(c, &r.members, 1)) || (rc = dev_alloc(c, &r.sum, cols)) ||
+            (rc = dev_alloc(c, &r.sumsq, cols)) || (rc = dev_alloc(c, &r.sum_o, cols)) || (rc = dev_alloc(c, &r.sumsq_o, cols)) || (rc = dev_alloc(c, &r.sum_d, cols)) ||
+            (rc = dev_alloc(c, &r.sumsq_d, cols))) {
+            (void)hipGetLastError();
+            rows_free(c, &r);
+            return fail(c, ESIM_ENOMEM, who + ": no device memory for the accumulators (56 B per column)");
+        }
+        if (old.hit) HIP_TRY(c, hipStreamSynchronize(c->stream));    // (a fold on the stream may still be using the old ones)
+        r.vax = old.vax; old.vax = nullptr;                          // (the series kind's 4 B per citizen, whatever the shape)
+        rows_free(c, &old);
+        old = r;
+    }
+    Ensemble::Rows &r = c->ens.rows;
+    r.kind = Ensemble::ROWS_PEAKS; r.n_rows = 1u; r.n_cols = cols; r.two = false;
+    r.mask = status_mask; r.first = first_step; r.last = last_step; r.threshold = threshold; r.min = min_peak;
+    for (uint32_t *p : { r.hit, r.defined }) HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(uint32_t) * std::max<size_t>(1, cols), c->stream));
+    for (unsigned long long *p : { r.sum, r.sumsq, r.sum_o, r.sumsq_o, r.sum_d, r.sumsq_d })
+        HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(unsigned long long) * std::max<size_t>(1, cols), c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
+    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    return ESIM_OK;
+}
+
+extern "C" int esim_ensemble_read_peaks(esim_ctx *ctx, uint32_t *members, uint32_t *defined, uint32_t *hit, uint64_t *sum_peak, uint64_t *sumsq_peak,
+                                        uint64_t *sum_step, uint64_t *sumsq_step, uint64_t *sum_duration, uint64_t *sumsq_duration)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_ensemble_read_peaks";
+    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit || c->ens.rows.kind != Ensemble::ROWS_PEAKS)
+        return fail(c, ESIM_ESTATE, who + ": no population uploaded, or no esim_ensemble_begin_peaks in force since the upload (or, by group, since esim_set_groups)");
+    const Ensemble::Rows &r = c->ens.rows;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    Ctrl h; int rc;
+    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for whatever is on the stream)
+    const size_t cols = r.n_cols;
+    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const std::pair<uint32_t *, const uint32_t *> words[] = { { defined, r.defined }, { hit, r.hit } };
+    for (const auto &p : words)
+        if (p.first && cols) HIP_TRY(c, hipMemcpy(p.first, p.second, sizeof(uint32_t) * cols, hipMemcpyDeviceToHost));
+    const std::pair<uint64_t *, const unsigned long long *> sums[] = { { sum_peak, r.sum }, { sumsq_peak, r.sumsq }, { sum_step, r.sum_o }, { sumsq_step, r.sumsq_o },
+                                                                       { sum_duration, r.sum_d }, { sumsq_duration, r.sumsq_d } };
+    for (const auto &p : sums)
+        if (p.first && cols) HIP_TRY(c, hipMemcpy(p.first, p.second, sizeof(uint64_t) * cols, hipMemcpyDeviceToHost));
+    return ctrl_error(c, h);
+}

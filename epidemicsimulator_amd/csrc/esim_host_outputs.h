@@ -303,7 +303,7 @@ SeriesSpec fold_spec(int where, int what)
 void rows_free(esim_ctx_impl *c, Ensemble::Rows *r)
 {
     for (void *q : { (void *)r->hit, (void *)r->members, (void *)r->p0, (void *)r->p1, (void *)r->occ, (void *)r->vax, (void *)r->sum, (void *)r->sumsq, (void *)r->aw,
-                     (void *)r->defined, (void *)r->sum_o, (void *)r->sumsq_o, (void *)r->cross }) dev_free(c, q);
+                     (void *)r->defined, (void *)r->sum_o, (void *)r->sumsq_o, (void *)r->cross, (void *)r->sum_d, (void *)r->sumsq_d }) dev_free(c, q);
     *r = Ensemble::Rows();
 }
 
@@ -331,6 +331,7 @@ int fold_series(esim_ctx_impl *c)
 
 int fold_transmission(esim_ctx_impl *c);   // (esim_host_ensrows.h: the settings and the reproduction kind)
 int fold_paired(esim_ctx_impl *c);         // (esim_host_compare.h: the paired kind)
+int fold_peaks(esim_ctx_impl *c);          // (esim_host_curves.h: the peaks kind)
 }  // namespace
 
 extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
@@ -387,6 +388,7 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (!c->uploaded || !c->ens.valid || !(c->ens.series ? c->ens.rows.hit : c->ens.hit))
         return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
+    if (c->ens.series && c->ens.rows.kind == Ensemble::ROWS_PEAKS) return fold_peaks(c);
     if (c->ens.series) return c->ens.rows.kind == Ensemble::ROWS_SERIES ? fold_series(c) : c->ens.rows.kind == Ensemble::ROWS_PAIRED ? fold_paired(c) : fold_transmission(c);
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;
@@ -476,6 +478,8 @@ extern "C" int esim_ensemble_read_series(esim_ctx *ctx, uint32_t first_row, uint
         return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_reproduction (read them with esim_ensemble_read_reproduction)");
     if (r.kind == Ensemble::ROWS_PAIRED)
         return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_paired (read them with esim_ensemble_read_paired)");
+    if (r.kind == Ensemble::ROWS_PEAKS)
+        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_peaks (read them with esim_ensemble_read_peaks)");
     if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, "esim_ensemble_read_series: rows outside the accumulators");
     HIP_TRY(c, hipSetDevice(c->P.device));
     Ctrl h; int rc;

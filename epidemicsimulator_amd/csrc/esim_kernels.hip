@@ -43,4 +43,5 @@
 #include "esim_kernels_events.h"
 #include "esim_kernels_restart.h"
 #include "esim_kernels_compare.h"
+#include "esim_kernels_curves.h"
 #include "esim_kernels_snapshot.h"

@@ -3,7 +3,8 @@
 //
 //   insert   pair_insert adds one key to an open-addressing table of `cap` slots (a power of two): a 64-bit finaliser picks the
 //            slot, a linear probe of at most `cap` tries finds the key or an empty slot, a 64-bit atomicCAS claims it and an
-//            atomicAdd counts.  A key that finds no slot bumps *overflow and is dropped: the loop cannot spin.
+//            atomicAdd counts.  A key that finds no slot bumps *overflow and is dropped: the loop cannot spin.  pair_add is the
+//            same with a change other than +1 (esim_curves.h: the net change of a curve at a step).
 //   compact  k_pairs_compact, a lane per slot: the occupied slots of a wavefront are counted with one ballot and reserved with
 //            one atomic, and their (key, count) pairs go to a dense array -- in the order the wavefronts happened to arrive.
 //            k_pairs_compact_min keeps only the slots that count at least min_count.
@@ -40,9 +41,10 @@ __device__ __forceinline__ uint64_t pair_mix(uint64_t k)
     return k ^ (k >> 33);
 }
 
-// Counts `key` (!= PAIR_EMPTY) once.  A slot's key is written once and never changes, so the plain read in front of the CAS
-// can only be stale in one way -- empty where a key stands by now --, and then the CAS returns that key.
-__device__ __forceinline__ void pair_insert(const PairTable &t, uint64_t key)
+// Adds `delta` to the count of `key` (!= PAIR_EMPTY), modulo 2^32: a key may end at a net count of 0 and still holds its slot.
+// A slot's key is written once and never changes, so the plain read in front of the CAS can only be stale in one way -- empty
+// where a key stands by now --, and then the CAS returns that key.
+__device__ __forceinline__ void pair_add(const PairTable &t, uint64_t key, uint32_t delta)
 {
     const uint32_t mask = t.cap - 1u;
     uint32_t slot = (uint32_t)pair_mix(key) & mask;
@@ -52,10 +54,13 @@ __device__ __forceinline__ void pair_insert(const PairTable &t, uint64_t key)
             cur = atomicCAS(&t.key[slot], PAIR_EMPTY, (unsigned long long)key);
             if (cur == PAIR_EMPTY) cur = key;                                   // claimed
         }
-        if (cur == key) { atomicAdd(&t.cnt[slot], 1u); return; }
+        if (cur == key) { atomicAdd(&t.cnt[slot], delta); return; }
     }
     atomicAdd(t.overflow, 1u);
 }
+
+// Counts `key` (!= PAIR_EMPTY) once.
+__device__ __forceinline__ void pair_insert(const PairTable &t, uint64_t key) { pair_add(t, key, 1u); }
 
 // The occupied slots, dense: out_key / out_cnt [*n_out ...), *n_out zeroed by the caller; the arrays hold at least as many pairs
 // as the table can (the callers size them by what can have been inserted).  Every lane of a wavefront makes the same trips.

@@ -138,6 +138,27 @@ def paired_summary(acc, first_step=0, stride=24):
             "steps": int(first_step) + int(stride) * np.arange(sb.shape[0], dtype=np.int64)}
 
 
+def peaks_summary(acc):
+    """From Simulator.ensemble_read_peaks(): members, defined (members with a peak of at least 1), hit, p_peak = hit / members
+    (NaN without members); peak_mean and peak_var, duration_mean and duration_var over all members (a member without a case
+    counts as 0); peak_step_mean and peak_step_var over the defined members, NaN where there is none.  Population variances,
+    from the integer sums."""
+    m = int(acc["members"])
+    defined, hit = np.asarray(acc["defined"], np.uint32), np.asarray(acc["hit"], np.uint32)
+    out = {"members": m, "defined": defined, "hit": hit}
+    d = defined.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["p_peak"] = hit.astype(np.float64) / m if m else np.full(hit.shape, np.nan)
+        for name, key, n in (("peak", "peak", float(m)), ("duration", "duration", float(m)), ("peak_step", "step", d)):
+            s, ss = np.asarray(acc["sum_" + key], np.float64), np.asarray(acc["sumsq_" + key], np.float64)
+            mean = np.where(n > 0, s / n, np.nan)
+            out[name + "_mean"], out[name + "_var"] = mean, np.where(n > 0, np.maximum(ss / n - mean * mean, 0.0), np.nan)
+    return out
+
+
+PEAKS_ARRAYS = ("defined", "hit", "p_peak", "peak_mean", "peak_var", "peak_step_mean", "peak_step_var", "duration_mean", "duration_var")
+
+
 def _json_number(x):
     x = float(x)
     return None if x != x else x          # NaN (an arrival mean nobody contributed to) is written as null
@@ -171,7 +192,8 @@ class EnsembleResult:
         summary's mean and var are null where hit is 0).  A series summary goes to ensemble_area_series.npz instead -- steps,
         hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary; the
         summary of area kind "settings" goes to ensemble_area_settings.npz the same way, that of kind "reproduction" to
-        ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes.  The members' exposures by setting, where they
+        ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes; that of
+        kind "peaks" to ensemble_area_peaks.npz: the arrays of peaks_summary, members, and codes.  The members' exposures by setting, where they
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
         ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names."""
         os.makedirs(directory, exist_ok=True)
@@ -182,7 +204,13 @@ class EnsembleResult:
         with open(os.path.join(directory, "ensemble_stats.json"), "w") as fh:
             json.dump(stats, fh)
         doc = None
-        if self.area is not None and "steps" in self.area:     # a summary over rows: arrays by (row, column), too many for JSON
+        if self.area is not None and self.area_kind == "peaks":      # arrays by column: nine of them, too many for the JSON's three
+            arrays = {k: self.area[k] for k in PEAKS_ARRAYS}
+            arrays["members"] = np.asarray(self.area["members"], np.uint32)
+            if self.area_codes is not None:
+                arrays["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_peaks.npz"), **arrays)
+        elif self.area is not None and "steps" in self.area:     # a summary over rows: arrays by (row, column), too many for JSON
             a = self.area
             ratio = "r" in a
             arrays = {k: a[k] for k in (("steps", "defined", "hit", "cases_mean", "offspring_mean", "r", "p_r", "r_se") if ratio else ("steps", "hit", "mean", "var"))}
@@ -466,8 +494,8 @@ class CompareResult:
         np.savez(os.path.join(directory, "ensemble_compare.npz"), **arrays)
 
 
-_KINDS = ("census", "arrival", "series", "settings", "reproduction")
-_ROW_KINDS = ("series", "settings", "reproduction")      # a member that stopped early has no rows behind its last step
+_KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks")
+_ROW_KINDS = ("series", "settings", "reproduction", "peaks")      # a member that stopped early has no rows behind its last step
 
 
 class Ensemble:
@@ -492,13 +520,15 @@ class Ensemble:
         area = dict(area)
         kind = area.pop("kind", "census")
         if kind not in _KINDS:
-            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings' or 'reproduction', got %r" % (who, kind))
+            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction' or 'peaks', got %r" % (who, kind))
         if kind in _ROW_KINDS and stop_when_done:
             raise ValueError("Ensemble.%s: area kind %r cannot go with stop_when_done=True (a member that stopped early has no "
                              "rows behind its last step, and the library refuses the fold)" % (who, kind))
         if kind == "settings" and area.get("n_rows") is None:
             first, stride = int(area.get("first_step", 1)), int(area.get("stride", 1))
             area["n_rows"] = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
+        if kind == "peaks" and area.get("last_step") is None:
+            area["last_step"] = int(n_steps)
         if kind == "reproduction":
             complete = area.pop("complete", True)
             if area.get("n_rows") is None:
@@ -519,12 +549,14 @@ class Ensemble:
         sim = self.simulator
         if kind is not None:
             getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
-                          "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction"}[kind])(**area)
+                          "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks"}[kind])(**area)
 
     def _summary(self, kind, area):
         sim = self.simulator
         if kind is None:
             return None
+        if kind == "peaks":
+            return peaks_summary(sim.ensemble_read_peaks())
         if kind == "reproduction":
             return reproduction_summary(sim.ensemble_read_reproduction(), area.get("first_step", 0), area.get("stride", 24))
         if kind in ("series", "settings"):
@@ -716,7 +748,9 @@ class Ensemble:
         settings=..., first_step=..., n_rows=..., stride=..., min_cases=...) for the exposures by setting per Output Area or
         group (Simulator.ensemble_begin_settings; a series_summary again); or dict(kind="reproduction", where=..., first_step=...,
         n_rows=..., stride=..., min_cohort=..., r=(num, den), complete=True) for the cohort rows (Simulator.
-        ensemble_begin_reproduction; the summary is a reproduction_summary).  With complete=True and n_rows=None only complete
+        ensemble_begin_reproduction; the summary is a reproduction_summary); or dict(kind="peaks", where=..., status=...,
+        first_step=..., last_step=..., threshold=..., min_peak=...) for the shape of every member's curve per column
+        (Simulator.ensemble_begin_peaks; last_step=None: n_steps; the summary is a peaks_summary).  With complete=True and n_rows=None only complete
         cohort rows are taken -- an incomplete cohort biases R down -- and ValueError is raised when there is none.  Neither goes
         with stop_when_done=True.
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting

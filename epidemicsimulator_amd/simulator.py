@@ -487,6 +487,55 @@ class Simulator:
         _lib.check(self.lib.esim_ensemble_read_reproduction(self._ctx, int(first_row), n, C.byref(members), *ptrs), self._ctx)
         return dict(out, members=int(members.value))
 
+    # -- the shape of the epidemic curve per column (esim_curve_summary, esim_ensemble_begin_peaks) -------
+    CURVE_STATUS = {"exposed": 1 << _lib.EXPOSED, "infected": 1 << _lib.INFECTED, "active": (1 << _lib.EXPOSED) | (1 << _lib.INFECTED)}
+    CURVE_KEYS = ("peak", "peak_step", "steps_at_least", "first_at_least", "last_at_least", "person_steps")
+    PEAKS_KEYS = ("defined", "hit", "sum_peak", "sumsq_peak", "sum_step", "sumsq_step", "sum_duration", "sumsq_duration")
+
+    def _curve_args(self, who, where, status):
+        """(`where` code, status mask, columns) of the curve calls; a bad `status` is refused here, before any library call."""
+        if status not in self.CURVE_STATUS:
+            raise ValueError("Simulator.%s: status must be 'exposed', 'infected' or 'active', got %r" % (who, status))
+        place = {"all": _lib.BY_ALL, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        n_cols = 1 if place == _lib.BY_ALL else max(1, self._n_groups) if place == _lib.BY_GROUP else self.population.n_areas
+        return int(place), self.CURVE_STATUS[status], n_cols
+
+    def curve_summary(self, where="home", status="infected", first_step=1, last_step=None, threshold=1):
+        """The shape of the epidemic curve per column (esim_curve_summary), a dict of [n_cols] arrays over the steps first_step ..
+        last_step (None: the last step run) of x_s = the citizens of the column whose status after step s is `status`
+        ("exposed", "infected", or "active": either): peak = max x_s; peak_step = the first step that attains it (_lib.NEVER
+        where the peak is 0); steps_at_least = the steps with x_s >= threshold, first_at_least and last_at_least the first and
+        the last of them (_lib.NEVER without one); person_steps = the sum of x_s (uint64).  where: "all" (one column), "home"
+        (by the Output Area of the household) or "group".  Computed on the device from the exposure log; no rows are built."""
+        place, mask, n_cols = self._curve_args("curve_summary", where, status)
+        last = self._steps if last_step is None else int(last_step)
+        out = {k: np.zeros(n_cols, np.uint64 if k == "person_steps" else np.uint32) for k in self.CURVE_KEYS}
+        ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint64 if k == "person_steps" else C.c_uint32)) for k in self.CURVE_KEYS]
+        _lib.check(self.lib.esim_curve_summary(self._ctx, place, mask, int(first_step), last, int(threshold), *ptrs), self._ctx)
+        return out
+
+    def ensemble_begin_peaks(self, where="home", status="infected", first_step=1, last_step=None, threshold=1, min_peak=1):
+        """Accumulators over the curve summaries (esim_ensemble_begin_peaks): ensemble_fold computes the member's
+        curve_summary(where, status, first_step, last_step, threshold) on the device and adds per column defined += (peak >= 1),
+        hit += (peak >= min_peak), the sums of the peak, of steps_at_least and of their squares over all members, and those of
+        peak_step over the defined ones.  last_step=None: the last step of the run (params.max_steps).  ensemble_read_peaks
+        reads them."""
+        place, mask, n_cols = self._curve_args("ensemble_begin_peaks", where, status)
+        last = int(self.params.max_steps) if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_ensemble_begin_peaks(self._ctx, place, mask, int(first_step), last, int(threshold), int(min_peak)), self._ctx)
+        self._ens_rows = 1
+        self._ens_n = n_cols
+
+    def ensemble_read_peaks(self):
+        """{"members": int, "defined", "hit": uint32 [n_cols], "sum_peak", "sumsq_peak", "sum_step", "sumsq_step", "sum_duration",
+        "sumsq_duration": uint64 [n_cols]}: the accumulators begun by ensemble_begin_peaks."""
+        cols = getattr(self, "_ens_n", self.population.n_areas)
+        members = C.c_uint32(0)
+        out = {k: np.zeros(cols, np.uint32 if i < 2 else np.uint64) for i, k in enumerate(self.PEAKS_KEYS)}
+        ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint32 if i < 2 else C.c_uint64)) for i, k in enumerate(self.PEAKS_KEYS)]
+        _lib.check(self.lib.esim_ensemble_read_peaks(self._ctx, C.byref(members), *ptrs), self._ctx)
+        return dict(out, members=int(members.value))
+
     def download_state(self):
         n = self.population.n_citizens
         out = {"status": np.zeros(n, np.uint8), "timer": np.zeros(n, np.uint16),
@@ -971,7 +1020,7 @@ class Simulator:
         return self._pairs(self.lib.esim_lineage_areas, ())
 
     def pair_stats(self):
-        """What the pair engine did in the last area_flows() / lineage_areas() call (esim_pair_stats): a dict of insert_ms,
+        """What the pair engine did in the last area_flows(), lineage_areas() or curve_summary() call, or peaks fold (esim_pair_stats): a dict of insert_ms,
         compact_ms, sort_ms (device time, HIP events), distinct, capacity and dropped."""
         ms, counts = (C.c_double * 3)(), (C.c_uint32 * 3)()
         _lib.check(self.lib.esim_pair_stats(self._ctx, ms, counts), self._ctx)

@@ -950,6 +950,55 @@ int  esim_ensemble_read_paired(esim_ctx *ctx, uint32_t first_row, uint32_t n, ui
                                uint32_t *hit /* [n * n_cols] */, uint64_t *sum_baseline, uint64_t *sum_current, uint64_t *sumsq_baseline,
                                uint64_t *sumsq_current, uint64_t *sum_cross /* [n * n_cols] each */);
 
+/* The shape of the epidemic curve per column.  x_s[col] is the number of citizens of column `col` whose status after
+ * step s is in status_mask -- the state after that step's vaccinations, the convention of every area and group table.  Three masks
+ * are allowed: 1 << ESIM_EXPOSED, 1 << ESIM_INFECTED, and both together ("active"): together the two statuses are one interval
+ * per case.  Every other mask is ESIM_EINVAL (the other statuses are monotone: the census and the arrival map describe them).
+ *          where = ESIM_BY_ALL       one column
+ *          where = ESIM_AREA_HOME    n_areas columns, by the Output Area of the household
+ *          where = ESIM_BY_GROUP     n_groups columns, by the labels of esim_set_groups (ESIM_ESTATE without labels)
+ *        ESIM_AREA_CURRENT and anything else is ESIM_EINVAL.  Cell for cell x_s is the row of step s of
+ *        esim_area_status_series(ESIM_AREA_HOME, what) or esim_group_series(what) at stride 1, for the mask of both the sum of the
+ *        two rows; the index cases are Infected after steps 0 .. infected_time.
+ * esim_curve_summary: over the steps s in [first_step, last_step],
+ *          peak[col]            max x_s
+ *          peak_step[col]       the smallest s that attains it; ESIM_NEVER where the peak is 0
+ *          steps_at_least[col]  the number of steps with x_s >= threshold
+ *          first_at_least[col], last_at_least[col]   the smallest and the largest such s; ESIM_NEVER without one
+ *          person_steps[col]    the sum of x_s
+ *        Any output may be NULL; with all of them NULL the call still runs and returns its status.  ESIM_EINVAL also for threshold
+ *        0; ESIM_ESTATE before an upload and on a context with more than one rank or that holds a shard; ESIM_ERANGE for
+ *        first_step 0, last_step < first_step, or last_step beyond the steps run; ESIM_ENOMEM without device memory (or with a
+ *        pair table, ESIM_PAIR_LOG2, too small for the change points); a sticky device-side error is reported as the series calls
+ *        report it.  A refused call leaves the outputs untouched.  The call leaves the simulation state, the records, the exposure
+ *        log, the snapshot, the baseline, the labels and the ensemble accumulators as they are and keeps nothing between calls;
+ *        after an esim_rollback under another seed or vaccination rate the vaccinations are replayed across the seam, as the
+ *        series calls replay them.  Nothing proportional to steps x columns is built: every case adds +1 at the first step of its
+ *        interval and -1 behind the last one to a sparse table keyed by (column, step), the distinct keys are sorted, a segmented
+ *        scan turns the changes into counts and a reduction per column takes the summary.  Temporary device memory, freed when the
+ *        call returns: 4 B per citizen for the vaccination replay once a programme has run; the pair table (12 B per slot, the
+ *        smallest power of two >= 4 x the log's entries) and the dense array (12 B per pair, 2 x the log's entries rounded up to a
+ *        power of two); 28 B per column for the tables and 12 B per 2048 pairs for the scan.  esim_pair_stats reports this call.
+ * Peaks ensemble accumulators: one more kind of the accumulators over rows, beside series, settings, reproduction and paired; one
+ * kind is in force at a time.  esim_ensemble_fold with this kind in force computes the member's esim_curve_summary(where,
+ * status_mask, first_step, last_step, threshold) on the device, adds members += 1 once and per column
+ *          defined += (peak >= 1);  hit += (peak >= min_peak)
+ *          sum_peak += peak; sumsq_peak += peak^2; sum_duration += steps_at_least; sumsq_duration += steps_at_least^2   (every member)
+ *          sum_step += peak_step; sumsq_step += peak_step^2                                                           (defined members)
+ *        in integers, 56 B per column; nothing per column goes to the host.  The fold is ESIM_ERANGE, with nothing folded, when
+ *        last_step lies beyond the member's steps; it waits for the stream.  ESIM_EINVAL and ESIM_ERANGE as esim_curve_summary, and
+ *        ESIM_EINVAL for min_peak 0.  Lifetime, replacement of the kind in force, ESIM_ENOMEM, the ESIM_ESTATE cases and the
+ *        invalidation by esim_set_groups are those of esim_ensemble_begin_reproduction.
+ * esim_ensemble_read_peaks: the accumulators, [n_cols] each, any pointer NULL; ESIM_ESTATE while another kind is in force -- and
+ *        the other reads are ESIM_ESTATE while this one is. */
+int  esim_curve_summary(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step, uint32_t threshold,
+                        uint32_t *peak, uint32_t *peak_step, uint32_t *steps_at_least, uint32_t *first_at_least, uint32_t *last_at_least,
+                        uint64_t *person_steps /* [n_cols] each, any may be NULL */);
+int  esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step,
+                               uint32_t threshold, uint32_t min_peak);
+int  esim_ensemble_read_peaks(esim_ctx *ctx, uint32_t *members, uint32_t *defined, uint32_t *hit, uint64_t *sum_peak, uint64_t *sumsq_peak,
+                              uint64_t *sum_step, uint64_t *sumsq_step, uint64_t *sum_duration, uint64_t *sumsq_duration);
+
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
  *   out[0] "Generate Exposures", out[1] "Apply Exposures", out[2] "Apply Interventions", out[3] total.
