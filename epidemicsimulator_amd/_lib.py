@@ -91,7 +91,7 @@ SYMBOLS = [
     "esim_comm_unique_id", "esim_comm_init_rccl", "esim_comm_init_callback", "esim_comm_set_timeout", "esim_debug_inject_error", "esim_comm_stats", "esim_run_sharded", "esim_shard_stats",
     "esim_read_records", "esim_synchronize",
     "esim_download_state", "esim_download_exposure_log", "esim_area_census", "esim_area_arrival", "esim_area_series", "esim_area_status_series", "esim_set_groups", "esim_group_census", "esim_group_series", "esim_exposure_settings", "esim_setting_series", "esim_building_exposures", "esim_transmission_tree", "esim_offspring", "esim_reproduction_series", "esim_mixing_matrix", "esim_transmission_chains", "esim_outbreaks", "esim_transmission_ages", "esim_household_outbreaks", "esim_household_final_sizes", "esim_household_sar", "esim_place_outbreaks", "esim_place_sizes", "esim_place_sar", "esim_contact_hours", "esim_area_flows", "esim_area_imports", "esim_area_invasion", "esim_lineage_areas", "esim_pair_stats", "esim_transmission_events", "esim_routes", "esim_ensemble_begin", "esim_ensemble_begin_arrival", "esim_ensemble_fold", "esim_ensemble_read", "esim_ensemble_begin_series", "esim_ensemble_read_series", "esim_ensemble_begin_settings", "esim_ensemble_begin_reproduction", "esim_ensemble_read_reproduction", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_snapshot", "esim_rollback", "esim_snapshot_info", "esim_snapshot_drop", "esim_baseline_keep", "esim_baseline_info", "esim_baseline_drop", "esim_compare", "esim_compare_series", "esim_ensemble_begin_paired", "esim_ensemble_read_paired", "esim_curve_summary", "esim_ensemble_begin_peaks", "esim_ensemble_read_peaks", "esim_enable_phase_timing", "esim_phase_timings",
-    "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters",
+    "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters", "esim_debug_launches",
     "esim_last_error", "esim_destroy",
     "esim_threshold_lut", "esim_synth_preset", "esim_synth_create", "esim_synth_create_shard", "esim_synth_free",
     "esim_shard_population", "esim_shard_cuts",
@@ -205,6 +205,7 @@ def load():
         "esim_enable_kernel_timing": (C.c_int, [vp, C.c_int]),
         "esim_kernel_timings": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
         "esim_debug_counters": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "esim_debug_launches": (C.c_int, [vp, C.c_char_p, _u32p, C.c_uint32, _u32p, C.c_int]),
         "esim_set_small_step_limit": (C.c_int, [vp, C.c_uint32]),
         "esim_set_tiny_chunk_limit": (C.c_int, [vp, C.c_uint32]),
         "esim_small_kernel_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -256,6 +257,8 @@ CMP_NAMES = ("both", "averted", "added", "earlier", "later")
 ENSEMBLE_SERIES_EVENTS = 5            # esim_ensemble_begin_series `what`, beside the five status codes: incidence / exposures
 DEBUG_COUNTERS = ("t", "chunk_ok", "chunk_parallel", "chunk_pairs", "n_items", "items_per_wave", "n_units", "chunk_bus",
                   "n_route_pairs_big", "n_newexp", "log_len", "n_susceptible", "lockdown", "mask", "at_work", "bus_dir")   # esim_debug_counters
+LAUNCH_SITE_CHARS = 48                # ESIM_LAUNCH_SITE_CHARS: a site's name in esim_debug_launches
+LAUNCH_SITES_MAX = 128                # the sites esim_debug_launches can hold
 CHUNK_KERNELS = ("marks", "fold", "draw", "units", "count", "books", "scatter", "vax", "vax_adj", "vax_final", "decide", "future", "map_clear", "tiny", "vax_repair")   # ESIM_CK_* (vax_adj, map_clear: always 0)
 PHASE_OF_KERNEL = {"marks": "Generate Exposures", "fold": "Generate Exposures", "draw": "Apply Exposures", "units": "Apply Exposures"}   # the rest: "Apply Interventions"
 TINY_PHASE_SHARES = {"Generate Exposures": 0.10, "Apply Exposures": 0.40, "Apply Interventions": 0.50}   # k_chunk_tiny: all three in one launch

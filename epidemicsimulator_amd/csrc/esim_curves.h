@@ -187,11 +187,12 @@ static inline void curve_scan_enqueue(const unsigned long long *key, uint32_t *c
     hipLaunchKernelGGL(k_curve_scan, dim3(tiles), dim3(CURVE_TPB), 0, stream, key, cnt, n, carry, cnt);
 }
 
-// The launch that reduces the n scanned pairs into the tables on `stream`.
+// The launch that reduces the n scanned pairs into the tables on `stream`, with at most max_blocks workgroups (the kernel loops).
+const uint32_t CURVE_REDUCE_GRID = 4096u;
 static inline void curve_reduce_enqueue(const unsigned long long *key, const uint32_t *val, uint32_t n, uint32_t n_cols, uint32_t last_step, uint32_t threshold,
-                                        const CurveTabs &t, hipStream_t stream)
+                                        const CurveTabs &t, hipStream_t stream, uint32_t max_blocks = CURVE_REDUCE_GRID)
 {
     if (!n) return;
     const uint32_t blocks = (uint32_t)(((uint64_t)n + 255u) / 256u);
-    hipLaunchKernelGGL(k_curve_reduce, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, stream, key, val, n, n_cols, last_step, threshold, t);
+    hipLaunchKernelGGL(k_curve_reduce, dim3(blocks < max_blocks ? blocks : max_blocks), dim3(256), 0, stream, key, val, n, n_cols, last_step, threshold, t);
 }

@@ -35,7 +35,7 @@ hipError_t enqueue_plane(esim_ctx_impl *c, uint32_t log_len, uint32_t *plane)
 {
     const hipError_t e = hipMemsetAsync(plane, 0xFF, sizeof(uint32_t) * std::max<size_t>(1, c->d.n), c->stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_compare_plane, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, c->host_t - 1u, log_len, plane);
+    hipLaunchKernelGGL(k_compare_plane, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, c->host_t - 1u, log_len, plane);
     return hipGetLastError();
 }
 
@@ -50,7 +50,7 @@ hipError_t enqueue_compare_rows(esim_ctx_impl *c, int where, uint32_t first_step
     CompareRows r;
     r.base = c->base.plane; r.cur = cur; r.where = (uint32_t)where; r.first = first_step; r.n_rows = n_rows; r.stride = stride; r.n_cols = cols;
     r.grp = where == ESIM_BY_GROUP ? c->grp.lab : nullptr; r.rows_b = rows_b; r.rows_c = rows_c;
-    hipLaunchKernelGGL(k_compare_rows, dim3(grid_for(((size_t)c->d.n + 3u) / 4u, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, r);
+    hipLaunchKernelGGL(k_compare_rows, dim3(grid_capped(c, ((size_t)c->d.n + 3u) / 4u, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, r);
     if (cumulative) hipLaunchKernelGGL(k_compare_prefix, dim3(grid_for(cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, rows_b, rows_c, n_rows, cols);
     return hipGetLastError();
 }
@@ -83,7 +83,7 @@ int fold_paired(esim_ctx_impl *c)
         RatioAcc a;
         a.defined = r.defined; a.hit = r.hit; a.members = r.members; a.sum_c = r.sum; a.sum_o = r.sum_o; a.sq_c = r.sumsq; a.sq_o = r.sumsq_o; a.cross = r.cross;
         const uint64_t cells = (uint64_t)r.n_rows * r.n_cols;
-        hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(grid_for((size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.min_averted, a);
+        hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.min_averted, a);
         e = hipGetLastError();
     }
     const hipError_t es = hipStreamSynchronize(c->stream);           // (the temporary plane goes when the call returns)

@@ -61,13 +61,13 @@ extern "C" int esim_contact_hours(esim_ctx *ctx, int where, uint32_t setting_mas
     if (hours || per_case) {
         const int mode = where == ESIM_BY_ALL ? CT_ONE_CELL : lds <= CONTACT_LDS_BYTES ? CT_LDS : CT_GLOBAL;
         if ((setting_mask >> ESIM_SETTING_HOUSEHOLD) & 1u) {
-            const dim3 grid(grid_for(log_len, TPB, 4096));
+            const dim3 grid(grid_capped(c, log_len, TPB, 4096));
             if (mode == CT_ONE_CELL) hipLaunchKernelGGL(k_contact_home<CT_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
-            else if (mode == CT_LDS) hipLaunchKernelGGL(k_contact_home<CT_LDS>, dim3(grid_for(log_len, TPB * HH_SAR_PER_LANE, 4096)), dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
+            else if (mode == CT_LDS) hipLaunchKernelGGL(k_contact_home<CT_LDS>, dim3(grid_capped(c, log_len, TPB * HH_SAR_PER_LANE, 4096, TPB)), dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
             else hipLaunchKernelGGL(k_contact_home<CT_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
         }
         if (setting_mask & ~(1u << ESIM_SETTING_HOUSEHOLD)) {
-            const dim3 grid(grid_for(log_len, TPB / 64u, 4096));
+            const dim3 grid(grid_capped(c, log_len, TPB / 64u, 4096));
             if (mode == CT_ONE_CELL) hipLaunchKernelGGL(k_contact_wide<CT_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
             else if (mode == CT_LDS) hipLaunchKernelGGL(k_contact_wide<CT_LDS>, grid, dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
             else hipLaunchKernelGGL(k_contact_wide<CT_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
@@ -77,7 +77,9 @@ extern "C" int esim_contact_hours(esim_ctx *ctx, int where, uint32_t setting_mas
         // the bus steps of the window in stretches whose (step, route) bit set fits CONTACT_BITS_MAX
         const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_bus, CONTACT_BITS_MAX / d.n_routes));
         const size_t n_words = (size_t)(((uint64_t)per * d.n_routes + 31u) / 32u);
-        const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(CONTACT_ROUTE_GRID, (256ull << 20) / (8ull * d.max_route)));
+        // (a workgroup takes 64 words of the bit set a trip; tmp below is sized by the grid as clamped)
+        const uint32_t route_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(CONTACT_ROUTE_GRID, (256ull << 20) / (8ull * d.max_route)));
+        const uint32_t grid = grid_clamp(c, n_words, 64u, route_grid, __builtin_FILE(), __builtin_LINE());
         if (n_words > 0xFFFFFFFFull || bus_steps.alloc(n_bus) != hipSuccess || bits.alloc(n_words) != hipSuccess || tmp.alloc((size_t)grid * 2u * d.max_route) != hipSuccess)
             return leave(ESIM_ENOMEM, "no device memory for the routes longer than a bus (a bit per route and bus step of the window, 64 MB at most, and 8 B per rider of the longest route per workgroup)");
         k.bus_steps = bus_steps.p;
@@ -86,12 +88,12 @@ extern "C" int esim_contact_hours(esim_ctx *ctx, int where, uint32_t setting_mas
             const uint32_t hi = std::min(n_bus, lo + per);
             e = hipMemsetAsync(bits.p, 0, sizeof(uint32_t) * n_words, c->stream);
             if (e != hipSuccess) break;
-            hipLaunchKernelGGL(k_contact_route_mark, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w.s.q, k, log_len, lo, hi, bits.p);
+            hipLaunchKernelGGL(k_contact_route_mark, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w.s.q, k, log_len, lo, hi, bits.p);
             hipLaunchKernelGGL(k_contact_route, dim3(grid), dim3(64), 0, c->stream, d, w.s.q, k, lo, bits.p, (uint32_t)n_words, tmp.p);
         }
         if (e != hipSuccess) return leave(ESIM_ENODEVICE, hipGetErrorString(e));
     }
-    if (transmissions) hipLaunchKernelGGL(k_contact_trans, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w.s.q, w.t, k, log_len);
+    if (transmissions) hipLaunchKernelGGL(k_contact_trans, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w.s.q, w.t, k, log_len);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (hours) HIP_TRY(c, hipMemcpy(hours, k.hours, sizeof(uint64_t) * plane, hipMemcpyDeviceToHost));

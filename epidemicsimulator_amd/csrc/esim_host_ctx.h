@@ -166,6 +166,16 @@ struct Tuning {
     uint32_t draw_mult = 4, units_mult = 4;     // k_chunk_draw / k_chunk_units run this many times the marks grid: more, shorter wavefronts than the chip holds at once
     uint32_t small_max = 128;                   // infected-slice length up to which the persistent single-workgroup kernel runs a step
     uint32_t pair_log2 = 0;                     // ESIM_PAIR_LOG2: the pair table of esim_area_flows / esim_lineage_areas has 1 << this many slots (0: sized by the log)
+    uint32_t grid_cap = 0;                      // ESIM_GRID_CAP: the grids of the output kernels hold at most this many workgroups (0: unset, as in production)
+};
+
+// What grid_capped sized while ESIM_GRID_CAP is set, per launch site (esim_debug_launches): a fixed table, a site more than it
+// holds is an error of the call that reads it.
+const uint32_t LAUNCH_SITES_MAX = 128;
+struct LaunchLog {
+    struct Site { const char *file; uint32_t line, launches, clipped, max_trips; } site[LAUNCH_SITES_MAX];
+    uint32_t n = 0;
+    bool overflow = false;
 };
 
 // What the pair engine (esim_host_flows.h) did in the last call that used it: esim_pair_stats.
@@ -217,6 +227,7 @@ struct esim_ctx_impl {
     DrawSeam draw_seam;               // of the history the context stands on
     DrawSeam snap_draw_seam;          // of the history under the snapshot held (esim_snapshot copies it, esim_rollback starts from it)
     Tuning tune;
+    LaunchLog launches;
 };
 
 #define CTX(c) (reinterpret_cast<esim_ctx_impl *>(c))
@@ -299,6 +310,39 @@ uint32_t grid_for(size_t items, uint32_t per_block, uint32_t cap)
 {
     size_t g = (items + per_block - 1) / per_block;
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(g, cap));
+}
+
+// The grid of an output launch: `grid` as the launch site sized it, or ESIM_GRID_CAP workgroups where that is fewer -- the
+// kernels loop with a grid stride, so a test reaches the second and later trips with a small world.  With the knob unset
+// (production) this returns `grid` and touches nothing.  With it set, the site's record counts the launch, whether it was
+// clipped, and the trips of its longest loop.
+uint32_t grid_clamp(esim_ctx_impl *c, size_t items, uint32_t per_block, uint32_t grid, const char *file, uint32_t line)
+{
+    const uint32_t knob = c->tune.grid_cap;
+    if (!knob) return grid;
+    const uint32_t g = std::min(grid, knob);
+    LaunchLog &l = c->launches;
+    uint32_t i = 0;
+    while (i < l.n && !(l.site[i].line == line && std::strcmp(l.site[i].file, file) == 0)) ++i;
+    if (i == l.n) {
+        if (l.n == LAUNCH_SITES_MAX) { l.overflow = true; return g; }
+        l.site[l.n++] = LaunchLog::Site{ file, line, 0u, 0u, 0u };
+    }
+    LaunchLog::Site &s = l.site[i];
+    const size_t per_trip = (size_t)g * per_block;
+    s.launches += 1u;
+    s.clipped += g < grid ? 1u : 0u;
+    s.max_trips = std::max(s.max_trips, (uint32_t)std::min<size_t>(0xFFFFFFFFu, (items + per_trip - 1) / per_trip));
+    return g;
+}
+
+// grid_for for a launch whose kernel loops over its items: every such launch of the output families is sized here.
+// per_trip: the items a workgroup takes per trip of its loop where that is not per_block -- a site that sizes its grid for
+// several trips a lane (per_block = TPB * 32 with a loop that strides by TPB) -- so that the record counts the trips made.
+uint32_t grid_capped(esim_ctx_impl *c, size_t items, uint32_t per_block, uint32_t cap, uint32_t per_trip = 0, const char *file = __builtin_FILE(),
+                     uint32_t line = __builtin_LINE())
+{
+    return grid_clamp(c, items, per_trip ? per_trip : per_block, grid_for(items, per_block, cap), file, line);
 }
 
 static inline void ht_mark(esim_ctx_impl *c, const char *what)

@@ -70,7 +70,7 @@ int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, 
     q.first = s.first; q.t_done = t_done; q.t_all = shape.t_all; q.vax_of = replay ? vax : nullptr; q.n_cols = cols;
     q.key = s.where == ESIM_BY_ALL ? CURVE_BY_ALL : s.where == ESIM_BY_GROUP ? (uint32_t)KEY_GROUP : (uint32_t)KEY_HOME;
     q.grp = s.where == ESIM_BY_GROUP ? c->grp.lab : nullptr;
-    hipLaunchKernelGGL(k_curve_events, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, s.mask, s.last, log_len, w->p.t);
+    hipLaunchKernelGGL(k_curve_events, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, s.mask, s.last, log_len, w->p.t);
     if ((rc = pairs_sorted(c, &w->p))) return flows_unwind(c, rc);
     if (w->p.dropped) {                                                      // (ESIM_PAIR_LOG2 too small: nothing is reduced)
         (void)hipStreamSynchronize(c->stream);
@@ -82,7 +82,7 @@ int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, 
         return flows_unwind(c, fail(c, ESIM_ENOMEM, who + ": no device memory for the tile aggregates of the scan"));
     }
     curve_scan_enqueue(w->p.out_key.p, w->p.out_cnt.p, n, w->agg.p, c->stream);
-    curve_reduce_enqueue(w->p.out_key.p, w->p.out_cnt.p, n, cols, s.last, s.threshold, w->t, c->stream);
+    if (n) curve_reduce_enqueue(w->p.out_key.p, w->p.out_cnt.p, n, cols, s.last, s.threshold, w->t, c->stream, grid_capped(c, n, 256u, CURVE_REDUCE_GRID));
     if ((e = hipGetLastError()) != hipSuccess) return flows_unwind(c, fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)));
     return ESIM_OK;
 }
@@ -131,7 +131,7 @@ int fold_peaks(esim_ctx_impl *c)
     PeakAcc a;
     a.defined = r.defined; a.hit = r.hit; a.members = r.members;
     a.sum_peak = r.sum; a.sq_peak = r.sumsq; a.sum_step = r.sum_o; a.sq_step = r.sumsq_o; a.sum_dur = r.sum_d; a.sq_dur = r.sumsq_d;
-    hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_for(r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, r.min, a);
+    hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_capped(c, r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, r.min, a);
     hipError_t e = hipGetLastError();
     const hipError_t es = hipStreamSynchronize(c->stream);                   // (the temporary tables go when the call returns)
     if (e == hipSuccess) e = es;

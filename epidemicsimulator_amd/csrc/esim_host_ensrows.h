@@ -67,7 +67,7 @@ int fold_transmission(esim_ctx_impl *c)
         return fail(c, ESIM_ERANGE, who + ": rows outside the steps run so far");
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint64_t cells = (uint64_t)r.n_rows * r.n_cols;
-    const uint32_t fold_grid = grid_for((size_t)(cells >> 2), TPB, 2048);
+    const uint32_t fold_grid = grid_capped(c, (size_t)(cells >> 2), TPB, 2048);
     HIP_TRY(c, hipMemsetAsync(r.p0, 0, sizeof(uint32_t) * std::max<size_t>(1, (size_t)cells), c->stream));
     if (!ratio) {
         SettingRows q;
@@ -75,7 +75,7 @@ int fold_transmission(esim_ctx_impl *c)
         q.grp = by_group ? c->grp.lab : nullptr; q.rows = r.p0;
         SettingWork w;
         if (int rc = settings_enqueue(c, who, &w)) return rc;
-        hipLaunchKernelGGL(k_setting_rows, dim3(grid_for(w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, q, w.log_len);
+        hipLaunchKernelGGL(k_setting_rows, dim3(grid_capped(c, w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, q, w.log_len);
         hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
         return settings_finish(c, who, &w);
     }
@@ -87,7 +87,7 @@ int fold_transmission(esim_ctx_impl *c)
     a.defined = r.defined; a.hit = r.hit; a.members = r.members; a.sum_c = r.sum; a.sum_o = r.sum_o; a.sq_c = r.sumsq; a.sq_o = r.sumsq_o; a.cross = r.cross;
     TreeWork w;
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
-    hipLaunchKernelGGL(k_tree_rows, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, q, w.s.log_len);
+    hipLaunchKernelGGL(k_tree_rows, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, q, w.s.log_len);
     hipLaunchKernelGGL(k_ensemble_fold_ratio, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.r_num, r.r_den, a);
     return tree_finish(c, who, &w);
 }

@@ -25,12 +25,12 @@ extern "C" int esim_transmission_events(esim_ctx *ctx, uint32_t setting_mask, ui
     if (int rc = tree_enqueue(c, who, &w, false, true)) return rc;
     const uint32_t log_len = w.s.log_len;
     if (int rc = pairs_begin(c, who, &p, log_len)) return flows_unwind(c, rc);
-    hipLaunchKernelGGL(k_event_keys, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, log_len, p.t);
+    hipLaunchKernelGGL(k_event_keys, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, log_len, p.t);
     if (sizes) {
         const hipError_t e = hipMemsetAsync(hist.p, 0, sizeof(uint32_t) * bins, c->stream);
         if (e != hipSuccess) return flows_unwind(c, fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)));
         // (a workgroup walks 8 slots per lane at least before it hands over its 1024 counters)
-        hipLaunchKernelGGL(k_event_hist, dim3(grid_for(p.t.cap, PAIR_TPB * 8u, 1024)), dim3(PAIR_TPB), 0, c->stream, p.t, hist.p);
+        hipLaunchKernelGGL(k_event_hist, dim3(grid_capped(c, p.t.cap, PAIR_TPB * 8u, 1024, PAIR_TPB)), dim3(PAIR_TPB), 0, c->stream, p.t, hist.p);
     }
     if (int rc = pairs_compacted(c, &p, min_size)) return flows_unwind(c, rc);
     // the events to deliver: by key all of them or none, by size the first `cap`
@@ -43,13 +43,13 @@ extern "C" int esim_transmission_events(esim_ctx *ctx, uint32_t setting_mask, ui
         }
         pairs_sort_enqueue(p.out_key.p, p.out_cnt.p, n_sort, c->stream);
         if (by_size) {
-            hipLaunchKernelGGL(k_event_rekey, dim3(grid_for(n_sort, PAIR_TPB, 4096)), dim3(PAIR_TPB), 0, c->stream, p.out_cnt.p, n, n_sort, by_key.p, by_cnt.p);
+            hipLaunchKernelGGL(k_event_rekey, dim3(grid_capped(c, n_sort, PAIR_TPB, 4096)), dim3(PAIR_TPB), 0, c->stream, p.out_cnt.p, n, n_sort, by_key.p, by_cnt.p);
             pairs_sort_enqueue(by_key.p, by_cnt.p, n_sort, c->stream);
         }
         EventOut o;
         o.step = step ? out.p : nullptr; o.place = place ? out.p + m : nullptr; o.bus = bus ? out.p + 2 * (size_t)m : nullptr; o.size = size ? out.p + 3 * (size_t)m : nullptr;
         o.setting = setting ? out_set.p : nullptr;
-        hipLaunchKernelGGL(k_event_split, dim3(grid_for(m, PAIR_TPB, 4096)), dim3(PAIR_TPB), 0, c->stream, c->d, p.out_key.p, p.out_cnt.p, n, by_size ? by_key.p : nullptr, m, o);
+        hipLaunchKernelGGL(k_event_split, dim3(grid_capped(c, m, PAIR_TPB, 4096)), dim3(PAIR_TPB), 0, c->stream, c->d, p.out_key.p, p.out_cnt.p, n, by_size ? by_key.p : nullptr, m, o);
     }
     {
         const hipError_t e = hipEventRecord(p.ev[3], c->stream);

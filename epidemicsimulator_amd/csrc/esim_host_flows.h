@@ -45,7 +45,7 @@ int pairs_begin(esim_ctx_impl *c, const std::string &who, PairWork *w, uint32_t 
 int pairs_compacted(esim_ctx_impl *c, PairWork *w, uint32_t min_count)
 {
     HIP_TRY(c, hipEventRecord(w->ev[1], c->stream));
-    const dim3 grid(grid_for(w->t.cap, PAIR_TPB, 4096)), block(PAIR_TPB);
+    const dim3 grid(grid_capped(c, w->t.cap, PAIR_TPB, 4096)), block(PAIR_TPB);
     if (min_count > 1u) hipLaunchKernelGGL(k_pairs_compact_min, grid, block, 0, c->stream, w->t, min_count, w->out_key.p, w->out_cnt.p, w->dense, w->counters.p);
     else hipLaunchKernelGGL(k_pairs_compact, grid, block, 0, c->stream, w->t, w->out_key.p, w->out_cnt.p, w->dense, w->counters.p);
     HIP_TRY(c, hipEventRecord(w->ev[2], c->stream));
@@ -126,7 +126,7 @@ extern "C" int esim_area_flows(esim_ctx *ctx, uint32_t setting_mask, uint32_t fi
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     const uint32_t log_len = w.s.log_len;
     if (int rc = pairs_begin(c, who, &p, log_len)) return flows_unwind(c, rc);
-    hipLaunchKernelGGL(k_flow_pairs, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, log_len, p.t);
+    hipLaunchKernelGGL(k_flow_pairs, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, log_len, p.t);
     if (int rc = pairs_sorted(c, &p)) return flows_unwind(c, rc);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
@@ -150,7 +150,7 @@ extern "C" int esim_area_imports(esim_ctx *ctx, uint32_t setting_mask, uint32_t 
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(uint32_t) * std::max<size_t>(1, 3 * na), c->stream));
     if (local || imported || exported)
-        hipLaunchKernelGGL(k_flow_imports, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, w.s.log_len,
+        hipLaunchKernelGGL(k_flow_imports, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step, w.s.log_len,
                            local ? tab.p : nullptr, imported ? tab.p + na : nullptr, exported ? tab.p + 2 * na : nullptr);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
@@ -178,8 +178,8 @@ extern "C" int esim_area_invasion(esim_ctx *ctx, uint32_t *first_case, uint32_t 
     TreeWork w;
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     HIP_TRY(c, hipMemsetAsync(best.p, 0xFF, sizeof(unsigned long long) * std::max<size_t>(1, na), c->stream));
-    hipLaunchKernelGGL(k_flow_first, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.s.log_len, best.p);
-    hipLaunchKernelGGL(k_flow_resolve, dim3(grid_for(na, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, best.p, tab.p, tab.p + na, tab.p + 2 * na, set.p);
+    hipLaunchKernelGGL(k_flow_first, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.s.log_len, best.p);
+    hipLaunchKernelGGL(k_flow_resolve, dim3(grid_capped(c, na, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, best.p, tab.p, tab.p + na, tab.p + 2 * na, set.p);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     const size_t bytes = sizeof(uint32_t) * na;
@@ -202,7 +202,7 @@ extern "C" int esim_lineage_areas(esim_ctx *ctx, uint32_t *lineage, uint32_t *ar
     if (int rc = chains_enqueue(c, who, &w, CHAIN_UP, 0u, 0u)) return rc;
     const uint32_t log_len = w.t.s.log_len;
     if (int rc = pairs_begin(c, who, &p, log_len)) return flows_unwind(c, rc);
-    hipLaunchKernelGGL(k_flow_lineages, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.ch, log_len, p.t);
+    hipLaunchKernelGGL(k_flow_lineages, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.ch, log_len, p.t);
     if (int rc = pairs_sorted(c, &p)) return flows_unwind(c, rc);
     const int rc = chains_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;

@@ -25,9 +25,9 @@ int household_enqueue(esim_ctx_impl *c, const std::string &who, HouseholdWork *w
     if (e == hipSuccess) e = hipMemsetAsync(h.first, 0xFF, sizeof(uint32_t) * std::max<size_t>(1, nb), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h.final_size, 0, sizeof(uint32_t) * 2 * HH_CELLS, c->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }   // (the settings' kernels still read the host vectors of w->s)
-    hipLaunchKernelGGL(k_hh_residents, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, h);
+    hipLaunchKernelGGL(k_hh_residents, dim3(grid_capped(c, d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, h);
     // (a workgroup of k_hh_tables bins 32 buildings per lane at least before it hands over its table of 8192 counters at most)
-    if (tables) hipLaunchKernelGGL(k_hh_tables, dim3(grid_for(nb, TPB * 32u, 1024)), dim3(TPB), 0, c->stream, d, h);
+    if (tables) hipLaunchKernelGGL(k_hh_tables, dim3(grid_capped(c, nb, TPB * 32u, 1024, TPB)), dim3(TPB), 0, c->stream, d, h);
     return ESIM_OK;
 }
 
@@ -90,11 +90,11 @@ extern "C" int esim_household_sar(esim_ctx *ctx, int where, uint32_t first_step,
     HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(unsigned long long) * std::max<size_t>(1, 2 * cells), c->stream));
     const uint32_t log_len = w.s.log_len;
     if (where == ESIM_BY_ALL)
-        hipLaunchKernelGGL(k_hh_sar<HH_ONE_CELL>, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, s, log_len);
+        hipLaunchKernelGGL(k_hh_sar<HH_ONE_CELL>, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, s, log_len);
     else if (lds <= HH_LDS_BYTES)
-        hipLaunchKernelGGL(k_hh_sar<HH_LDS>, dim3(grid_for(log_len, TPB * HH_SAR_PER_LANE, 4096)), dim3(TPB), lds, c->stream, c->d, w.s.q, w.t, s, log_len);
+        hipLaunchKernelGGL(k_hh_sar<HH_LDS>, dim3(grid_capped(c, log_len, TPB * HH_SAR_PER_LANE, 4096, TPB)), dim3(TPB), lds, c->stream, c->d, w.s.q, w.t, s, log_len);
     else
-        hipLaunchKernelGGL(k_hh_sar<HH_GLOBAL>, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, s, log_len);
+        hipLaunchKernelGGL(k_hh_sar<HH_GLOBAL>, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, s, log_len);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (at_risk) HIP_TRY(c, hipMemcpy(at_risk, s.at_risk, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));

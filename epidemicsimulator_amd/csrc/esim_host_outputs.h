@@ -26,7 +26,7 @@ extern "C" int esim_download_state(esim_ctx *ctx, uint8_t *status, uint16_t *tim
     DevTmp<uint8_t> d_status, d_bus, d_elig; DevTmp<uint16_t> d_timer; DevTmp<uint32_t> d_cur;
     if ((status && d_status.alloc(N) != hipSuccess) || (on_bus && d_bus.alloc(N) != hipSuccess) || (eligible && d_elig.alloc(N) != hipSuccess) ||
         (timer && d_timer.alloc(N) != hipSuccess) || (current_building && d_cur.alloc(N) != hipSuccess)) return fail(c, ESIM_ENOMEM, "esim_download_state: hipMalloc");
-    hipLaunchKernelGGL(k_decode_state, dim3(c->tune.grid_citizens), dim3(TPB), 0, c->stream, c->d, d_status.p, d_timer.p, d_cur.p, d_bus.p, d_elig.p);
+    hipLaunchKernelGGL(k_decode_state, dim3(grid_clamp(c, N, TPB, c->tune.grid_citizens, __builtin_FILE(), __builtin_LINE())), dim3(TPB), 0, c->stream, c->d, d_status.p, d_timer.p, d_cur.p, d_bus.p, d_elig.p);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess && status) e = hipMemcpy(status, d_status.p, N, hipMemcpyDeviceToHost);
     if (e == hipSuccess && on_bus) e = hipMemcpy(on_bus, d_bus.p, N, hipMemcpyDeviceToHost);
@@ -56,7 +56,7 @@ extern "C" int esim_download_exposure_log(esim_ctx *ctx, uint32_t *citizen, uint
     if (n == 0) return ESIM_OK;
     DevTmp<uint32_t> d_c; DevTmp<uint8_t> d_b;
     if (d_c.alloc(n) != hipSuccess || d_b.alloc(n) != hipSuccess) return fail(c, ESIM_ENOMEM, "esim_download_exposure_log: hipMalloc");
-    hipLaunchKernelGGL(k_export_log, dim3(grid_for(n, TPB, 2048)), dim3(TPB), 0, c->stream, c->d, first, n, d_c.p, d_b.p);
+    hipLaunchKernelGGL(k_export_log, dim3(grid_capped(c, n, TPB, 2048)), dim3(TPB), 0, c->stream, c->d, first, n, d_c.p, d_b.p);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(citizen, d_c.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(on_bus, d_b.p, n, hipMemcpyDeviceToHost);
@@ -87,7 +87,7 @@ int enqueue_group_census(esim_ctx_impl *c)
 {
     const Dev &d = c->d;
     HIP_TRY(c, hipMemsetAsync(c->grp.cnt, 0, sizeof(uint32_t) * (size_t)c->grp.n * 5u, c->stream));
-    hipLaunchKernelGGL(k_group_census, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 1024)), dim3(TPB), 0, c->stream, d, c->grp.lab, c->grp.n, c->grp.cnt);
+    hipLaunchKernelGGL(k_group_census, dim3(grid_capped(c, ((size_t)d.n + 3u) / 4u, TPB, 1024)), dim3(TPB), 0, c->stream, d, c->grp.lab, c->grp.n, c->grp.cnt);
     hipLaunchKernelGGL(k_group_finish, dim3(grid_for(c->grp.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, c->grp.size, c->grp.n, c->grp.cnt);
     return ESIM_OK;
 }
@@ -103,7 +103,7 @@ int enqueue_arrival(esim_ctx_impl *c, int where)
     const bool by_group = where == ESIM_BY_GROUP;
     const uint32_t n_keys = by_group ? c->grp.n : d.n_areas;
     HIP_TRY(c, hipMemsetAsync(c->arrival, 0xFF, sizeof(uint32_t) * std::max<size_t>(1, n_keys), c->stream));
-    hipLaunchKernelGGL(k_area_arrival, dim3(grid_for(d.n, TPB, 1024)), dim3(TPB), 0, c->stream, d, by_group ? c->grp.lab : nullptr, n_keys,
+    hipLaunchKernelGGL(k_area_arrival, dim3(grid_capped(c, d.n, TPB, 1024)), dim3(TPB), 0, c->stream, d, by_group ? c->grp.lab : nullptr, n_keys,
                        c->host_t - 1u, c->arrival);
     return ESIM_OK;
 }
@@ -259,10 +259,10 @@ hipError_t series_enqueue(esim_ctx_impl *c, const SeriesSpec &s, uint32_t first_
     q.n_tog = s.pieces ? (uint32_t)shape.tog.size() : 0u; q.tog = s.pieces ? b.tog : nullptr;
     const uint32_t *occ0 = !p.sus ? nullptr : p.by_group ? c->grp.size : b.occ, *occ1 = p.sus && p.two ? b.occ + p.cols : nullptr;
     if (s.what != ESIM_VACCINATED)
-        hipLaunchKernelGGL(k_series_log, dim3(grid_for(p.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, p.log_len);
+        hipLaunchKernelGGL(k_series_log, dim3(grid_capped(c, p.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, p.log_len);
     if (p.replay && (s.what == ESIM_VACCINATED || p.sus))         // (nobody is Vaccinated before a programme has run)
-        hipLaunchKernelGGL(k_series_vax, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
-    if (p.count_occ) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, b.occ, p.two ? b.occ + p.cols : nullptr);
+        hipLaunchKernelGGL(k_series_vax, dim3(grid_capped(c, d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
+    if (p.count_occ) hipLaunchKernelGGL(k_area_occupancy, dim3(grid_capped(c, d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, b.occ, p.two ? b.occ + p.cols : nullptr);
     if (!p.events)
         hipLaunchKernelGGL(k_series_prefix, dim3(grid_for(p.cols, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, q, occ0, occ1);
     return hipSuccess;
@@ -323,7 +323,7 @@ int fold_series(esim_ctx_impl *c)
     const hipError_t e = series_enqueue(c, s, r.first, r.n_rows, r.stride, p, b);
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_ensemble_fold: ") + hipGetErrorString(e));
     const uint64_t cells = (uint64_t)p.words;
-    hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(grid_for((size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream,
+    hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream,
                        r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;

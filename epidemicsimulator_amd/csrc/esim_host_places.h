@@ -30,11 +30,11 @@ int place_enqueue(esim_ctx_impl *c, const std::string &who, int kind, const Sett
     if (e == hipSuccess && n_list) e = hipMemsetAsync(w->list.first, 0xFF, sizeof(uint32_t) * n_list, c->stream);   // (a population without a room has no row)
     if (e == hipSuccess && kind == ESIM_PLACE_SCHOOL && n_out) e = hipMemsetAsync(w->out.first, 0xFF, sizeof(uint32_t) * n_out, c->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
-    if (kind == ESIM_PLACE_WORK) hipLaunchKernelGGL(k_place_members<false>, dim3(grid_for(d.n_wrk_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
-    else hipLaunchKernelGGL(k_place_members<true>, dim3(grid_for(d.n_room_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
-    if (kind == ESIM_PLACE_SCHOOL) hipLaunchKernelGGL(k_place_schools, dim3(grid_for(d.n_room, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->list, w->out);
+    if (kind == ESIM_PLACE_WORK) hipLaunchKernelGGL(k_place_members<false>, dim3(grid_capped(c, d.n_wrk_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
+    else hipLaunchKernelGGL(k_place_members<true>, dim3(grid_capped(c, d.n_room_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
+    if (kind == ESIM_PLACE_SCHOOL) hipLaunchKernelGGL(k_place_schools, dim3(grid_capped(c, d.n_room, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->list, w->out);
     // (a workgroup of k_place_tables bins 32 places per lane at least before it hands over its table of 2048 counters at most)
-    if (tables) hipLaunchKernelGGL(k_place_tables, dim3(grid_for(n_out, TPB * 32u, 1024)), dim3(TPB), 0, c->stream, w->out);
+    if (tables) hipLaunchKernelGGL(k_place_tables, dim3(grid_capped(c, n_out, TPB * 32u, 1024, TPB)), dim3(TPB), 0, c->stream, w->out);
     return ESIM_OK;
 }
 
@@ -108,11 +108,11 @@ extern "C" int esim_place_sar(esim_ctx *ctx, int kind, int where, uint32_t first
     const bool rooms = kind == ESIM_PLACE_ROOM;
 #ifndef PLACE_SAR_PER_CASE
     // a workgroup scans TPB places at a time; the grid stays wide, the long places lie where they lie
-    const dim3 grid(grid_for(pw.list.n_places, TPB, 16384));
+    const dim3 grid(grid_capped(c, pw.list.n_places, TPB, 16384));
 #define PLACE_SAR_LAUNCH(MODE, ROOMS, LDS) hipLaunchKernelGGL((k_place_sar<MODE, ROOMS>), grid, dim3(TPB), LDS, c->stream, c->d, w.s.q, w.t, pw.list, s)
 #else
     const uint32_t log_len = w.s.log_len;
-    const dim3 grid(grid_for(log_len, TPB / 64u, 4096));
+    const dim3 grid(grid_capped(c, log_len, TPB / 64u, 4096));
 #define PLACE_SAR_LAUNCH(MODE, ROOMS, LDS) hipLaunchKernelGGL((k_place_sar<MODE, ROOMS>), grid, dim3(TPB), LDS, c->stream, c->d, w.s.q, w.t, pw.list, s, log_len)
 #endif
     if (where == ESIM_BY_ALL) { if (rooms) PLACE_SAR_LAUNCH(PLACE_ONE_CELL, true, 0); else PLACE_SAR_LAUNCH(PLACE_ONE_CELL, false, 0); }

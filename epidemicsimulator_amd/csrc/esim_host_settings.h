@@ -79,8 +79,8 @@ int settings_enqueue(esim_ctx_impl *c, const std::string &who, SettingWork *w)
     }
     if (e == hipSuccess && replay) e = enqueue_vax_replay(c, w->shape.trigger, t_done, w->vax.p);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
-    hipLaunchKernelGGL(k_setting_scatter, dim3(grid_for(w->log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->log_len);
-    hipLaunchKernelGGL(k_setting_attr, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
+    hipLaunchKernelGGL(k_setting_scatter, dim3(grid_capped(c, w->log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->log_len);
+    hipLaunchKernelGGL(k_setting_attr, dim3(grid_capped(c, d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, q);
     return ESIM_OK;
 }
 
@@ -108,7 +108,7 @@ extern "C" int esim_exposure_settings(esim_ctx *ctx, uint8_t *setting, uint32_t 
     SettingWork w;
     if (int rc = settings_enqueue(c, who, &w)) return rc;
     const size_t n = c->d.n;
-    if (building) hipLaunchKernelGGL(k_setting_building, dim3(grid_for(n, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q);
+    if (building) hipLaunchKernelGGL(k_setting_building, dim3(grid_capped(c, n, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q);
     const int rc = settings_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (setting && n) HIP_TRY(c, hipMemcpy(setting, w.set.p, n, hipMemcpyDeviceToHost));
@@ -139,7 +139,7 @@ extern "C" int esim_setting_series(esim_ctx *ctx, int where, uint32_t setting_ma
     SettingWork w;
     if (int rc = settings_enqueue(c, who, &w)) return rc;
     HIP_TRY(c, hipMemsetAsync(rows.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream));
-    hipLaunchKernelGGL(k_setting_rows, dim3(grid_for(w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, r, w.log_len);
+    hipLaunchKernelGGL(k_setting_rows, dim3(grid_capped(c, w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, r, w.log_len);
     const int rc = settings_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (words) HIP_TRY(c, hipMemcpy(out, rows.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
@@ -161,7 +161,7 @@ extern "C" int esim_building_exposures(esim_ctx *ctx, uint32_t first_step, uint3
     SettingWork w;
     if (int rc = settings_enqueue(c, who, &w)) return rc;
     HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(uint32_t) * std::max<size_t>(1, nb), c->stream));
-    hipLaunchKernelGGL(k_setting_tally, dim3(grid_for(w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, first_step, last_step, w.log_len, tab.p);
+    hipLaunchKernelGGL(k_setting_tally, dim3(grid_capped(c, w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, first_step, last_step, w.log_len, tab.p);
     const int rc = settings_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (nb) HIP_TRY(c, hipMemcpy(counts, tab.p, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));

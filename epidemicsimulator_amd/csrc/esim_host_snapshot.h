@@ -49,7 +49,7 @@ int snapshot_room(esim_ctx_impl *c, uint32_t log_len)
 
 void launch_words(esim_ctx_impl *c, uint32_t *dst, const uint32_t *src)
 {
-    if (c->d.n) hipLaunchKernelGGL(k_snapshot_words, dim3(grid_for(((size_t)c->d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, dst, src, c->d.n);
+    if (c->d.n) hipLaunchKernelGGL(k_snapshot_words, dim3(grid_capped(c, ((size_t)c->d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, dst, src, c->d.n);
 }
 
 // bytes of the prefixes a state at rest with host_t as its next step has written (what esim_checkpoint_save pulls)

@@ -72,6 +72,28 @@ extern "C" int esim_debug_counters(esim_ctx *ctx, uint32_t out[16])
     return ESIM_OK;
 }
 
+extern "C" int esim_debug_launches(esim_ctx *ctx, char *sites, uint32_t *counts, uint32_t cap, uint32_t *out_n, int reset)
+{
+    esim_ctx_impl *c = CTX(ctx);
+    if (!c || !out_n) return ESIM_EINVAL;
+    LaunchLog &l = c->launches;
+    if (l.overflow)
+        return fail(c, ESIM_ERANGE, "esim_debug_launches: more than " + std::to_string(LAUNCH_SITES_MAX) + " launch sites were sized under ESIM_GRID_CAP (LAUNCH_SITES_MAX): records were lost");
+    *out_n = l.n;
+    if (cap < l.n || (l.n && (!sites || !counts))) {
+        if (cap < l.n) return fail(c, ESIM_ERANGE, "esim_debug_launches: " + std::to_string(l.n) + " sites are recorded, cap is smaller");
+        return ESIM_EINVAL;
+    }
+    for (uint32_t i = 0; i < l.n; ++i) {
+        const LaunchLog::Site &s = l.site[i];
+        const char *base = std::strrchr(s.file, '/');
+        std::snprintf(sites + (size_t)i * ESIM_LAUNCH_SITE_CHARS, ESIM_LAUNCH_SITE_CHARS, "%s:%u", base ? base + 1 : s.file, s.line);
+        counts[3 * i] = s.launches; counts[3 * i + 1] = s.clipped; counts[3 * i + 2] = s.max_trips;
+    }
+    if (reset) l = LaunchLog();
+    return ESIM_OK;
+}
+
 #ifdef ESIM_COUNT_WORK
 // counting build only (not in include/esim.h): what the chunk pass worked on since the last call (WK_* in esim_kernels_common.h)
 extern "C" int esim_work_counters(esim_ctx *ctx, unsigned long long *out, uint32_t n)

@@ -40,12 +40,12 @@ int tree_enqueue(esim_ctx_impl *c, const std::string &who, TreeWork *w, bool gen
     hipError_t e = hipMemsetAsync(w->counters.p, 0, 3 * sizeof(uint32_t), c->stream);
     if (e == hipSuccess && buses) e = hipMemsetAsync(w->bus.p, 0, sizeof(uint32_t) * std::max<size_t>(1, d.n), c->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
-    hipLaunchKernelGGL(k_tree_home, dim3(grid_for(d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);
-    hipLaunchKernelGGL(k_tree_wide, dim3(grid_for(log_len, TPB / 64u, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);
-    if (d.max_route > d.bus_capacity) hipLaunchKernelGGL(k_tree_route, dim3(grid_for(log_len, 1, 8192)), dim3(64), 0, c->stream, d, w->s.q, t);
+    hipLaunchKernelGGL(k_tree_home, dim3(grid_capped(c, d.n, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);
+    hipLaunchKernelGGL(k_tree_wide, dim3(grid_capped(c, log_len, TPB / 64u, 4096)), dim3(TPB), 0, c->stream, d, w->s.q, t);
+    if (d.max_route > d.bus_capacity) hipLaunchKernelGGL(k_tree_route, dim3(grid_capped(c, log_len, 1, 8192)), dim3(64), 0, c->stream, d, w->s.q, t);
     if (generations && t_done) {
         const uint32_t span = d.exposed_time + 1u, n_win = (t_done + span - 1u) / span;
-        const uint32_t grid = grid_for((size_t)log_len / n_win * 2u + 1u, TPB, 1024);
+        const uint32_t grid = grid_capped(c, (size_t)log_len / n_win * 2u + 1u, TPB, 1024);
         for (uint32_t lo = 1u; lo <= t_done; lo += span)
             hipLaunchKernelGGL(k_tree_gen, dim3(grid), dim3(TPB), 0, c->stream, d, w->s.q, t, lo, std::min(t_done, lo + span - 1u), log_len);
     }
@@ -99,7 +99,7 @@ extern "C" int esim_offspring(esim_ctx *ctx, uint32_t first_step, uint32_t last_
     TreeWork w;
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(uint32_t) * std::max<size_t>(1, n), c->stream));
-    hipLaunchKernelGGL(k_tree_offspring, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, first_step, last_step, w.s.log_len, tab.p);
+    hipLaunchKernelGGL(k_tree_offspring, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, first_step, last_step, w.s.log_len, tab.p);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (n) HIP_TRY(c, hipMemcpy(counts, tab.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
@@ -128,7 +128,7 @@ extern "C" int esim_reproduction_series(esim_ctx *ctx, int where, uint32_t first
     TreeWork w;
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     HIP_TRY(c, hipMemsetAsync(rows.p, 0, sizeof(uint32_t) * std::max<size_t>(1, 2 * words), c->stream));
-    hipLaunchKernelGGL(k_tree_rows, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, r, w.s.log_len);
+    hipLaunchKernelGGL(k_tree_rows, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, r, w.s.log_len);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
     if (cases && words) HIP_TRY(c, hipMemcpy(cases, rows.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
@@ -153,7 +153,7 @@ extern "C" int esim_mixing_matrix(esim_ctx *ctx, uint32_t setting_mask, uint32_t
     TreeWork w;
     if (int rc = tree_enqueue(c, who, &w, false)) return rc;
     HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(uint32_t) * std::max<size_t>(1, words), c->stream));
-    hipLaunchKernelGGL(k_tree_matrix, dim3(grid_for(w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step,
+    hipLaunchKernelGGL(k_tree_matrix, dim3(grid_capped(c, w.s.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.s.q, w.t, setting_mask, first_step, last_step,
                        (const uint16_t *)c->grp.lab, c->grp.n, w.s.log_len, tab.p);
     const int rc = tree_finish(c, who, &w);
     if (rc && rc != ESIM_ESIM) return rc;
@@ -197,7 +197,7 @@ int chains_enqueue(esim_ctx_impl *c, const std::string &who, ChainWork *w, unsig
     if (up) hipLaunchKernelGGL(k_chain_roots, dim3(grid_for(ch.n_seeds, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream, d, ch);
     if ((up || down) && t_done) {
         const uint32_t span = d.exposed_time + 1u, n_win = (t_done + span - 1u) / span;
-        const uint32_t grid = grid_for((size_t)log_len / n_win * 2u + 1u, TPB, 1024);
+        const uint32_t grid = grid_capped(c, (size_t)log_len / n_win * 2u + 1u, TPB, 1024);
         if (up)
             for (uint32_t lo = 1u; lo <= t_done; lo += span)
                 hipLaunchKernelGGL(k_chain_up, dim3(grid), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, lo, std::min(t_done, lo + span - 1u), log_len);
@@ -207,9 +207,9 @@ int chains_enqueue(esim_ctx_impl *c, const std::string &who, ChainWork *w, unsig
                 hipLaunchKernelGGL(k_chain_down, dim3(grid), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, lo, std::min(t_done, lo + span - 1u), log_len);
             }
     }
-    if (what & CHAIN_TABLE) hipLaunchKernelGGL(k_chain_outbreaks, dim3(grid_for(log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, log_len);
+    if (what & CHAIN_TABLE) hipLaunchKernelGGL(k_chain_outbreaks, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, log_len);
     // (a workgroup of k_chain_ages walks 32 entries per lane at least before it hands over its table of 2048 counters at most)
-    if (what & CHAIN_AGE) hipLaunchKernelGGL(k_chain_ages, dim3(grid_for(log_len, TPB * 32u, 1024)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, first, last, log_len);
+    if (what & CHAIN_AGE) hipLaunchKernelGGL(k_chain_ages, dim3(grid_capped(c, log_len, TPB * 32u, 1024, TPB)), dim3(TPB), 0, c->stream, d, w->t.s.q, w->t.t, ch, first, last, log_len);
     return ESIM_OK;
 }
 

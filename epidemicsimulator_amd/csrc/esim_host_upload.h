@@ -381,6 +381,9 @@ void upload_tuning(esim_ctx_impl *c, const UploadHost &u)
     if (const char *e = std::getenv("ESIM_GRID_EXPOSE")) t.grid_expose = (uint32_t)std::max(1, std::atoi(e));
     t.pair_log2 = 0u;
     if (const char *e = std::getenv("ESIM_PAIR_LOG2")) t.pair_log2 = (uint32_t)std::min(31, std::max(6, std::atoi(e)));     // (at least 64 slots)
+    t.grid_cap = 0u;
+    if (const char *e = std::getenv("ESIM_GRID_CAP")) t.grid_cap = (uint32_t)std::max(1, std::atoi(e));                     // (tests only: the output kernels' grids)
+    c->launches = LaunchLog();
 }
 
 }  // namespace
@@ -534,7 +537,7 @@ int restart_enqueue(esim_ctx_impl *c, const esim_params *p, bool replace, const 
     if (replace && n_seeds_now) HIP_TRY(c, hipMemcpyAsync(c->rs.seeds_dev, c->rs.seeds_stage, sizeof(uint32_t) * n_seeds_now, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->rs.ev, c->stream));
     c->rs.ev_used = true;
-    if (d.n) hipLaunchKernelGGL(k_restart_words, dim3(grid_for(((size_t)d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, d.cit, d.n);
+    if (d.n) hipLaunchKernelGGL(k_restart_words, dim3(grid_capped(c, ((size_t)d.n + 3u) / 4u, TPB, 2048)), dim3(TPB), 0, c->stream, d.cit, d.n);
     HIP_TRY(c, hipMemsetAsync(c->cnt_base, 0, c->cnt_bytes, c->stream));
     HIP_TRY(c, hipMemsetAsync(d.exp_step, 0, sizeof(uint32_t) * 2 * ((size_t)c->cap_steps + 2), c->stream));
     HIP_TRY(c, hipMemsetAsync(d.records, 0, sizeof(esim_step_result) * ((size_t)c->cap_steps + 1), c->stream));

@@ -1121,6 +1121,21 @@ class Simulator:
         _lib.check(self.lib.esim_debug_counters(self._ctx, out), self._ctx)
         return dict(zip(_lib.DEBUG_COUNTERS, (int(x) for x in out)))
 
+    def debug_launches(self, reset=False):
+        """What the output launches were sized to while ESIM_GRID_CAP is set (esim_debug_launches): {site: {"launches",
+        "clipped", "max_trips"}}, a site being "<file>:<line>" of the host code.  Empty when the knob is unset.  reset: the
+        records start anew after this read."""
+        cap = _lib.LAUNCH_SITES_MAX
+        names = C.create_string_buffer(cap * _lib.LAUNCH_SITE_CHARS)
+        counts = (C.c_uint32 * (3 * cap))()
+        n = C.c_uint32(0)
+        _lib.check(self.lib.esim_debug_launches(self._ctx, names, counts, cap, C.byref(n), 1 if reset else 0), self._ctx)
+        out = {}
+        for i in range(n.value):
+            raw = names.raw[i * _lib.LAUNCH_SITE_CHARS:(i + 1) * _lib.LAUNCH_SITE_CHARS]
+            out[raw.split(b"\0", 1)[0].decode()] = {"launches": int(counts[3 * i]), "clipped": int(counts[3 * i + 1]), "max_trips": int(counts[3 * i + 2])}
+        return out
+
     def vax_chunk_stats(self):
         """Steps run as chunks under a vaccination programme and how many of those chunks were cut short."""
         ns, nc = C.c_uint64(0), C.c_uint64(0)

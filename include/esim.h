@@ -1033,6 +1033,19 @@ int  esim_pipeline_timing(esim_ctx *ctx, double *mean_step_ms, uint64_t *steps_t
  * whose books ran; 0 after one of the one-workgroup form, which does not count them), n_newexp, log_len, n_susceptible, lockdown, mask,
  * at_work, bus_dir). */
 int  esim_debug_counters(esim_ctx *ctx, uint32_t out[16]);
+/* Diagnostics of the tests: ESIM_GRID_CAP=<workgroups> in the environment (read at esim_upload_population, at least 1, kept per
+ * context) caps the grid of every output kernel that loops over its items with a grid stride, so that a small world reaches
+ * the second and later trips of those loops.  Production never sets it: unset, every grid is what its launch site asks for
+ * and nothing is recorded.  While it is set, every such launch site keeps a record, which this call reads: sites[i] is the
+ * site's name, "<file>:<line>" of the host code that sized the grid, NUL-terminated in ESIM_LAUNCH_SITE_CHARS bytes;
+ * counts[3 * i + 0 .. 2] are the launches it sized, how many of them the cap clipped, and the largest
+ * trips = ceil(items / (grid * items a workgroup takes per trip of its loop)) among them.  *out_n: the number of sites recorded; cap: the room of
+ * sites and counts, in sites (ESIM_ERANGE when smaller than *out_n, which is set; cap = 0 with NULL arrays asks for the
+ * number alone while nothing is recorded).  reset != 0 empties the records after reading them.  The records live in a fixed
+ * table of 128 sites: a launch site beyond it makes this call fail with ESIM_ERANGE rather than drop the record silently.
+ * The call waits for nothing and touches no device. */
+#define ESIM_LAUNCH_SITE_CHARS 48
+int  esim_debug_launches(esim_ctx *ctx, char *sites, uint32_t *counts, uint32_t cap, uint32_t *out_n, int reset);
 
 const char *esim_last_error(const esim_ctx *ctx);   /* ctx may be NULL: last esim_create error */
 void esim_destroy(esim_ctx *ctx);

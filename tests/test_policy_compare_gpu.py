@@ -63,6 +63,12 @@ def groups_of(pop, g):
 @pytest.mark.parametrize("world,pair", cr.WORLD_PAIRS)
 def test_worlds_against_the_reference(world, pair, level):
     sim, pop, n, b, c, arm_b, arm_c = both_arms(world, pair, level)
+    check_world(sim, pop, n, b, c, arm_b, arm_c, world, pair)
+    sim.close()
+
+
+def check_world(sim, pop, n, b, c, arm_b, arm_c, world, pair):
+    """Every comparison of a world with both arms run and the baseline kept (both_arms) against the reference."""
     for got, want in (arm_b, arm_c):                                  # (the runs themselves are the oracle's)
         assert len(got) == n and all((got[f] == want[f]).all() for f in ("susceptible", "exposures_building", "exposures_bus", "vaccinated"))
     info = sim.baseline_info()
@@ -104,7 +110,6 @@ def test_worlds_against_the_reference(world, pair, level):
     cum_b, cum_c = sim.compare_series("home", 0, None, 24, True)
     t = sim.compare("home", 0, n)["counts"]
     assert (cum_b[-1] == t[:, B] + t[:, AV]).all() and (cum_c[-1] == t[:, B] + t[:, AD]).all()
-    sim.close()
 
 
 def test_each_output_alone_and_none():
