@@ -90,7 +90,8 @@ SYMBOLS = [
     "esim_run", "esim_set_pipeline", "esim_chunk_timing", "esim_enable_chunk_kernel_timing", "esim_chunk_kernel_timings", "esim_vax_chunk_stats", "esim_vax_repair_stats", "esim_pipeline_timing",
     "esim_comm_unique_id", "esim_comm_init_rccl", "esim_comm_init_callback", "esim_comm_set_timeout", "esim_debug_inject_error", "esim_comm_stats", "esim_run_sharded", "esim_shard_stats",
     "esim_read_records", "esim_synchronize",
-    "esim_download_state", "esim_download_exposure_log", "esim_area_census", "esim_area_arrival", "esim_area_series", "esim_area_status_series", "esim_set_groups", "esim_group_census", "esim_group_series", "esim_exposure_settings", "esim_setting_series", "esim_building_exposures", "esim_transmission_tree", "esim_offspring", "esim_reproduction_series", "esim_mixing_matrix", "esim_transmission_chains", "esim_outbreaks", "esim_transmission_ages", "esim_household_outbreaks", "esim_household_final_sizes", "esim_household_sar", "esim_place_outbreaks", "esim_place_sizes", "esim_place_sar", "esim_contact_hours", "esim_area_flows", "esim_area_imports", "esim_area_invasion", "esim_lineage_areas", "esim_pair_stats", "esim_transmission_events", "esim_routes", "esim_ensemble_begin", "esim_ensemble_begin_arrival", "esim_ensemble_fold", "esim_ensemble_read", "esim_ensemble_begin_series", "esim_ensemble_read_series", "esim_ensemble_begin_settings", "esim_ensemble_begin_reproduction", "esim_ensemble_read_reproduction", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_snapshot", "esim_rollback", "esim_snapshot_info", "esim_snapshot_drop", "esim_baseline_keep", "esim_baseline_info", "esim_baseline_drop", "esim_compare", "esim_compare_series", "esim_ensemble_begin_paired", "esim_ensemble_read_paired", "esim_curve_summary", "esim_ensemble_begin_peaks", "esim_ensemble_read_peaks", "esim_enable_phase_timing", "esim_phase_timings",
+    "esim_download_state", "esim_download_exposure_log", "esim_area_census", "esim_area_arrival", "esim_area_series", "esim_area_status_series", "esim_set_groups", "esim_group_census", "esim_group_series", "esim_exposure_settings", "esim_setting_series", "esim_building_exposures", "esim_transmission_tree", "esim_offspring", "esim_reproduction_series", "esim_mixing_matrix", "esim_transmission_chains", "esim_outbreaks", "esim_transmission_ages", "esim_household_outbreaks", "esim_household_final_sizes", "esim_household_sar", "esim_place_outbreaks", "esim_place_sizes", "esim_place_sar", "esim_contact_hours", "esim_area_flows", "esim_area_imports", "esim_area_invasion", "esim_lineage_areas", "esim_pair_stats", "esim_transmission_events", "esim_routes", "esim_ensemble_begin", "esim_ensemble_begin_arrival", "esim_ensemble_fold", "esim_ensemble_read", "esim_ensemble_begin_series", "esim_ensemble_read_series", "esim_ensemble_begin_settings", "esim_ensemble_begin_reproduction", "esim_ensemble_read_reproduction", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_snapshot", "esim_rollback", "esim_snapshot_info", "esim_snapshot_drop", "esim_baseline_keep", "esim_baseline_info", "esim_baseline_drop", "esim_compare", "esim_compare_series", "esim_ensemble_begin_paired", "esim_ensemble_read_paired", "esim_curve_summary", "esim_ensemble_begin_peaks", "esim_ensemble_read_peaks",
+    "esim_ensemble_keep_members", "esim_ensemble_members_info", "esim_ensemble_read_members", "esim_ensemble_quantiles", "esim_ensemble_exceedance", "esim_enable_phase_timing", "esim_phase_timings",
     "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters", "esim_debug_launches",
     "esim_last_error", "esim_destroy",
     "esim_threshold_lut", "esim_synth_preset", "esim_synth_create", "esim_synth_create_shard", "esim_synth_free",
@@ -200,6 +201,11 @@ def load():
         "esim_curve_summary": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint64)]),
         "esim_ensemble_begin_peaks": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "esim_ensemble_read_peaks": (C.c_int, [vp, _u32p, _u32p, _u32p] + [C.POINTER(C.c_uint64)] * 6),
+        "esim_ensemble_keep_members": (C.c_int, [vp, C.c_uint32, C.c_int]),
+        "esim_ensemble_members_info": (C.c_int, [vp, _u32p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "esim_ensemble_read_members": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),
+        "esim_ensemble_quantiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]),
+        "esim_ensemble_exceedance": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.c_uint32, _u32p]),
         "esim_enable_phase_timing": (C.c_int, [vp, C.c_int]),
         "esim_phase_timings": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "esim_enable_kernel_timing": (C.c_int, [vp, C.c_int]),
@@ -243,7 +249,9 @@ BY_SETTING = 3                        # esim_setting_series `where`, beside AREA
 NO_INFECTOR = 0xFFFFFFFF              # ESIM_NO_INFECTOR: esim_transmission_tree's entry for an index case, a citizen never exposed, an unexplained entry
 BY_ALL = 4                            # esim_reproduction_series `where`, beside AREA_HOME and BY_GROUP: one column
 NO_LINEAGE = 0xFFFFFFFF               # ESIM_NO_LINEAGE: esim_transmission_chains' entry for a citizen whose chain reaches no index case
-AGE_BINS = 512                        # ESIM_AGE_BINS: the infectious ages esim_transmission_ages counts per setting
+MEMBERS_MAX, RANKS_MAX = 256, 16      # ESIM_MEMBERS_MAX, ESIM_RANKS_MAX: esim_ensemble_keep_members' capacity, ranks or thresholds a call
+KEEP_VALUE, KEEP_PEAK_STEP, KEEP_DURATION = range(3)   # ESIM_KEEP_*: `what` of esim_ensemble_keep_members
+AGE_BINS = 512                     # ESIM_AGE_BINS: the infectious ages esim_transmission_ages counts per setting
 HH_BINS = 64                          # ESIM_HH_BINS: household sizes and case counts of esim_household_final_sizes, the last bin open-ended
 PLACE_WORK, PLACE_ROOM, PLACE_SCHOOL = range(3)   # ESIM_PLACE_*: the `kind` of esim_place_outbreaks, esim_place_sizes, esim_place_sar
 PLACE_NAMES = ("work", "room", "school")

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "esim_host_ctx.h"
+#include "esim_host_members.h"
 #include "esim_host_upload.h"
 #include "esim_host_run.h"
 #include "esim_host_shard.h"

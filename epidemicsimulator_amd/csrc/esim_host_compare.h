@@ -84,7 +84,8 @@ int fold_paired(esim_ctx_impl *c)
         a.defined = r.defined; a.hit = r.hit; a.members = r.members; a.sum_c = r.sum; a.sum_o = r.sum_o; a.sq_c = r.sumsq; a.sq_o = r.sumsq_o; a.cross = r.cross;
         const uint64_t cells = (uint64_t)r.n_rows * r.n_cols;
         hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.min_averted, a);
-        e = hipGetLastError();
+        e = members_keep(c);
+        if (e == hipSuccess) e = hipGetLastError();
     }
     const hipError_t es = hipStreamSynchronize(c->stream);           // (the temporary plane goes when the call returns)
     if (e == hipSuccess) e = es;
@@ -229,6 +230,7 @@ extern "C" int esim_ensemble_begin_paired(esim_ctx *ctx, int where, uint32_t fir
     Ensemble::Rows &r = c->ens.rows;
     r.first = first_step; r.stride = stride; r.min = min_baseline; r.min_averted = min_averted; r.cumulative = cumulative != 0;
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 

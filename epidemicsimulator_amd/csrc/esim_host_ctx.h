@@ -105,6 +105,16 @@ struct Ensemble {
         uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
     } rows;
     bool series = false;
+    // esim_ensemble_keep_members (esim_host_members.h): the members' values beside the accumulators in force, [capacity][n_rows *
+    // n_cols] keys (signed values with the top bit flipped), `kept` slots filled in the order of the folds.  planes == nullptr: no
+    // store.  folds: the members folded since the begin, kept or not (a store may only be opened in front of the first).
+    struct Store {
+        uint32_t *planes = nullptr;
+        uint32_t capacity = 0, kept = 0, n_rows = 0, n_cols = 0;
+        int what = 0;
+        bool is_signed = false, has_never = false;
+    } store;
+    uint32_t folds = 0;
 };
 
 // esim_set_groups: a label per citizen, the groups' sizes and the count table of esim_group_census [n * 5] (nullptr: no labels).
@@ -282,6 +292,7 @@ void free_device(esim_ctx_impl *c)
 {
     for (void *p : c->allocs) (void)hipFree(p);
     c->allocs.clear();
+    c->ens.store = Ensemble::Store();           // (the members kept were one of them)
     c->uploaded = false;
 }
 

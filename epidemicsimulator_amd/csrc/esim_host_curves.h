@@ -132,7 +132,8 @@ int fold_peaks(esim_ctx_impl *c)
     a.defined = r.defined; a.hit = r.hit; a.members = r.members;
     a.sum_peak = r.sum; a.sq_peak = r.sumsq; a.sum_step = r.sum_o; a.sq_step = r.sumsq_o; a.sum_dur = r.sum_d; a.sq_dur = r.sumsq_d;
     hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_capped(c, r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, r.min, a);
-    hipError_t e = hipGetLastError();
+    hipError_t e = members_keep(c, &w.t);
+    if (e == hipSuccess) e = hipGetLastError();
     const hipError_t es = hipStreamSynchronize(c->stream);                   // (the temporary tables go when the call returns)
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
@@ -174,6 +175,7 @@ extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t stat
         HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(unsigned long long) * std::max<size_t>(1, cols), c->stream));
     HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 

@@ -77,7 +77,9 @@ int fold_transmission(esim_ctx_impl *c)
         if (int rc = settings_enqueue(c, who, &w)) return rc;
         hipLaunchKernelGGL(k_setting_rows, dim3(grid_capped(c, w.log_len, TPB, 4096)), dim3(TPB), 0, c->stream, c->d, w.q, q, w.log_len);
         hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
-        return settings_finish(c, who, &w);
+        const hipError_t kept = members_keep(c);
+        const int rc = settings_finish(c, who, &w);
+        return kept != hipSuccess ? fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(kept)) : rc;
     }
     HIP_TRY(c, hipMemsetAsync(r.p1, 0, sizeof(uint32_t) * std::max<size_t>(1, (size_t)cells), c->stream));
     TreeRows q;
@@ -131,6 +133,7 @@ extern "C" int esim_ensemble_begin_settings(esim_ctx *ctx, int where, uint32_t s
     Ensemble::Rows &r = c->ens.rows;
     r.mask = setting_mask; r.first = first_step; r.stride = stride; r.min = min_cases;
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 
@@ -147,6 +150,7 @@ extern "C" int esim_ensemble_begin_reproduction(esim_ctx *ctx, int where, uint32
     Ensemble::Rows &r = c->ens.rows;
     r.first = first_step; r.stride = stride; r.min = min_cohort; r.r_num = r_num; r.r_den = r_den;
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 

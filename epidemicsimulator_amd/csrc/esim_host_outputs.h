@@ -325,6 +325,7 @@ int fold_series(esim_ctx_impl *c)
     const uint64_t cells = (uint64_t)p.words;
     hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream,
                        r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
+    HIP_TRY(c, members_keep(c));
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
@@ -369,6 +370,7 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
     if (int rc = ensemble_zero(c)) return rc;
     c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases; c->ens.arrival = false; c->ens.series = false;
     c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 
@@ -380,6 +382,7 @@ extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t ho
     if (int rc = ensemble_zero(c)) return rc;
     c->ens.where = where; c->ens.arrival = true; c->ens.series = false; c->ens.horizon = horizon;
     c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 
@@ -388,6 +391,7 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (!c->uploaded || !c->ens.valid || !(c->ens.series ? c->ens.rows.hit : c->ens.hit))
         return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
+    if (int rc = members_full(c)) return rc;
     if (c->ens.series && c->ens.rows.kind == Ensemble::ROWS_PEAKS) return fold_peaks(c);
     if (c->ens.series) return c->ens.rows.kind == Ensemble::ROWS_SERIES ? fold_series(c) : c->ens.rows.kind == Ensemble::ROWS_PAIRED ? fold_paired(c) : fold_transmission(c);
     HIP_TRY(c, hipSetDevice(c->P.device));
@@ -397,12 +401,14 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
         if ((rc = enqueue_arrival(c, c->ens.where))) return rc;
         hipLaunchKernelGGL(k_ensemble_fold_arrival, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
                            c->arrival, c->ens.n, c->ens.horizon, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
+        HIP_TRY(c, members_keep(c));
         HIP_TRY(c, hipGetLastError());
         return ESIM_OK;
     }
     if ((rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, c->ens.where))) return rc;
     hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
                        by_group ? c->grp.cnt : c->area_cnt, c->ens.n, c->ens.mask, c->ens.min, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
+    HIP_TRY(c, members_keep(c));
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
@@ -465,6 +471,7 @@ extern "C" int esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, ui
     HIP_TRY(c, hipMemsetAsync(r.sumsq, 0, sizeof(unsigned long long) * cells, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
+    members_end(c);
     return ESIM_OK;
 }
 

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .simulator import RECORD_DTYPE, Simulator
+from .simulator import RECORD_DTYPE, Simulator, check_probs
 
 QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)           # the rows of ensemble_stats.json
 STAT_FIELDS = ("susceptible", "exposed", "infected", "recovered", "vaccinated", "exposures_building", "exposures_bus", "vaccinated_now")
@@ -195,7 +195,9 @@ class EnsembleResult:
         ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes; that of
         kind "peaks" to ensemble_area_peaks.npz: the arrays of peaks_summary, members, and codes.  The members' exposures by setting, where they
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
-        ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names."""
+        ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names.  The quantile maps, where the area dict
+        asked for them, go to ensemble_area_quantiles.npz: probs, quantiles, thresholds, exceed, steps for a summary over rows, and
+        codes; every other file is what it is without them."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -227,6 +229,13 @@ class EnsembleResult:
                    "areas": {key(i): {"hit": int(a["hit"][i]), "mean": _json_number(a["mean"][i]), "var": _json_number(a["var"][i])} for i in range(len(a["hit"]))}}
         with open(os.path.join(directory, "ensemble_areas.json"), "w") as fh:
             json.dump(doc, fh)
+        if self.area is not None and "probs" in self.area:           # the quantile maps: a file of their own, the others are what they are without
+            extra = {k: self.area[k] for k in ("probs", "quantiles", "thresholds", "exceed") if self.area[k] is not None}
+            if "steps" in self.area:
+                extra["steps"] = self.area["steps"]
+            if self.area_codes is not None:
+                extra["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_quantiles.npz"), **extra)
         if self.settings is not None:
             np.savez(os.path.join(directory, "ensemble_settings.npz"), settings=self.settings, names=np.asarray(_lib.SETTING_NAMES))
         if self.reproduction is not None:
@@ -465,6 +474,8 @@ class CompareResult:
         self.summary = summary            # paired_summary(...) where rows were asked for, else None
         self.where = where
         self.area_codes = area_codes
+        self.quantile_probs = None        # float64 [n_q], and
+        self.averted_quantiles = None     # [n_q, n_rows, n_cols]: quantiles over the members of baseline - policy per cell, where compare(quantiles=...) asked
 
     @classmethod
     def gathered(cls, members, tables, records_baseline, records_policy, n_cols, n_steps, summary=None, where="all", area_codes=None):
@@ -492,6 +503,32 @@ class CompareResult:
         if self.area_codes is not None:
             arrays["codes"] = np.asarray(self.area_codes)
         np.savez(os.path.join(directory, "ensemble_compare.npz"), **arrays)
+        if self.averted_quantiles is not None:       # a file of its own: ensemble_compare.npz is what it is without them
+            extra = dict(probs=self.quantile_probs, quantiles=self.averted_quantiles)
+            if self.area_codes is not None:
+                extra["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_quantiles.npz"), **extra)
+
+
+def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep")):
+    """The keys of the quantile maps popped from `area` and checked before any library call: None where none is given, else
+    dict(probs, method, thresholds, what).  ValueError for the reproduction kind (a ratio per cell is not kept), a probability
+    outside [0, 1], an unknown method, `keep` on another kind than peaks, or more members than the store takes."""
+    given = {k: area.pop(k) for k in keys if k in area}
+    if not given:
+        return None
+    if kind == "reproduction":
+        raise ValueError("%s: the reproduction kind keeps no members (a ratio per cell is out of scope): no %s" % (who, ", ".join(sorted(given))))
+    probs = check_probs(who, given.get("quantiles") or ())
+    method = given.get("quantile_method", "nearest")
+    if method not in ("nearest", "linear"):
+        raise ValueError("%s: quantile_method must be 'nearest' or 'linear', got %r" % (who, method))
+    what = given.get("keep", "value")
+    if what not in Simulator.KEEP_WHAT or (what != "value" and kind != "peaks"):
+        raise ValueError("%s: keep must be 'value', or for the peaks kind 'peak_step' or 'duration', got %r" % (who, what))
+    if n_members is not None and int(n_members) > _lib.MEMBERS_MAX:
+        raise ValueError("%s: %d members, the store of the quantile maps takes %d (ESIM_MEMBERS_MAX)" % (who, int(n_members), _lib.MEMBERS_MAX))
+    return dict(probs=probs, method=method, thresholds=[int(t) for t in (given.get("exceed") or ())], what=what)
 
 
 _KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks")
@@ -511,16 +548,20 @@ class Ensemble:
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
         self._own_seeds = True            # the seeds in force are the uploaded population's
 
-    def _area_kind(self, who, area, n_steps, stop_when_done=False):
+    def _area_kind(self, who, area, n_steps, stop_when_done=False, n_members=None):
         """area of run() / forecast() checked, before anything runs: (kind, the area dict without its kind), or (None, None).
         For the reproduction kind `complete` is resolved here: with complete=True (the default) and n_rows=None only the rows
-        are taken whose cohort has had its whole infectious period by step n_steps."""
+        are taken whose cohort has had its whole infectious period by step n_steps.  The keys of the quantile maps -- quantiles,
+        quantile_method, exceed, keep -- are checked and taken out of the dict here (self._keep_spec holds them, None without
+        one): the begin call never sees them."""
+        self._keep_spec = None
         if area is None:
             return None, None
         area = dict(area)
         kind = area.pop("kind", "census")
         if kind not in _KINDS:
             raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction' or 'peaks', got %r" % (who, kind))
+        self._keep_spec = _keep_spec("Ensemble." + who, kind, area, n_members)
         if kind in _ROW_KINDS and stop_when_done:
             raise ValueError("Ensemble.%s: area kind %r cannot go with stop_when_done=True (a member that stopped early has no "
                              "rows behind its last step, and the library refuses the fold)" % (who, kind))
@@ -550,6 +591,24 @@ class Ensemble:
         if kind is not None:
             getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
                           "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks"}[kind])(**area)
+
+    def _keep_begin(self, n_members):
+        """Behind the begin: the store of the quantile maps, where the area dict asked for them."""
+        if self._keep_spec is not None and n_members:
+            self.simulator.ensemble_keep_members(n_members, self._keep_spec["what"])
+
+    def _keep_summary(self, summary, kind, n_members):
+        """The summary with probs, quantiles, thresholds and exceed added: [n_q, n_rows, n_cols], [n_q, n_cols] for the kinds
+        without rows (census, arrival, peaks)."""
+        spec = self._keep_spec
+        if spec is None or summary is None or not n_members:
+            return summary
+        sim = self.simulator
+        flat = (lambda a: a[:, 0]) if kind in ("census", "arrival", "peaks") else (lambda a: a)
+        out = dict(summary, probs=np.asarray(spec["probs"], np.float64), thresholds=np.asarray(spec["thresholds"], np.int64))
+        out["quantiles"] = flat(sim.ensemble_quantiles(spec["probs"], spec["method"])) if spec["probs"] else None
+        out["exceed"] = flat(sim.ensemble_exceedance(spec["thresholds"])) if spec["thresholds"] else None
+        return out
 
     def _summary(self, kind, area):
         sim = self.simulator
@@ -753,18 +812,23 @@ class Ensemble:
         (Simulator.ensemble_begin_peaks; last_step=None: n_steps; the summary is a peaks_summary).  With complete=True and n_rows=None only complete
         cohort rows are taken -- an incomplete cohort biases R down -- and ValueError is raised when there is none.  Neither goes
         with stop_when_done=True.
+        Every kind but reproduction also takes quantiles=(0.05, 0.5, 0.95), quantile_method="nearest" or "linear", exceed=(1, 5)
+        and, for peaks, keep="value", "peak_step" or "duration": the members' values per cell are then kept on the device
+        (Simulator.ensemble_keep_members) and the summary gains probs, quantiles [n_q, n_rows, n_cols] ([n_q, n_cols] for the
+        kinds without rows), thresholds and exceed -- the members at or above each threshold.  At most 256 members.
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
         (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
         with stop_when_done=True either.
         reproduction: None, or dict(first_step=..., n_rows=..., stride=...): every member's cohort rows
         (Simulator.reproduction_series("all")) gathered as EnsembleResult.reproduction, [members, n_rows, 2] = (cases,
         offspring); not with stop_when_done=True either.  Returns an EnsembleResult."""
-        kind, area = self._area_kind("run", area, n_steps, stop_when_done)
+        members = self._members(members)
+        kind, area = self._area_kind("run", area, n_steps, stop_when_done, len(members))
         spec = self._settings_rows("run", settings, n_steps, stop_when_done)
         r_spec = self._reproduction_rows("run", reproduction, n_steps, stop_when_done)
         sim = self.simulator
-        members = self._members(members)
         self._begin(kind, area)
+        self._keep_begin(len(members))
         rows, n_done, by_setting, by_cohort = [], [], [], []
         for m in members:
             self._restart_member(m)
@@ -778,7 +842,7 @@ class Ensemble:
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
-        summary = self._summary(kind, area)
+        summary = self._keep_summary(self._summary(kind, area), kind, len(members))
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
 
@@ -789,17 +853,18 @@ class Ensemble:
         for run(), without "index_cases" (the seeds belong to the shared history) and without other times or working hours (the
         library refuses them).  area, settings and reproduction: as for run(), folded / gathered once per member.  Returns an EnsembleResult whose records are
         [members, n_steps], the shared history repeated in every row."""
-        kind, area = self._area_kind("forecast", area, n_steps)
+        members = [dict(m) for m in members]
+        kind, area = self._area_kind("forecast", area, n_steps, False, len(members))
         spec = self._settings_rows("forecast", settings, n_steps)
         r_spec = self._reproduction_rows("forecast", reproduction, n_steps)
         sim = self.simulator
         history_steps, n_steps = int(history_steps), int(n_steps)
         if not 1 <= history_steps <= n_steps:
             raise ValueError("Ensemble.forecast: history_steps must be in 1..n_steps")
-        members = [dict(m) for m in members]
         if any("index_cases" in m for m in members):
             raise ValueError("Ensemble.forecast: a branch cannot change the index cases of the shared history")
         self._begin(kind, area)
+        self._keep_begin(len(members))
         sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
         self._own_seeds = True
         history = sim.run(history_steps)
@@ -817,13 +882,13 @@ class Ensemble:
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
-        summary = self._summary(kind, area)
+        summary = self._keep_summary(self._summary(kind, area), kind, len(members))
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
 
     _FIXED_BY_HISTORY = ("exposed_time", "infected_time", "start_hour", "end_hour")
 
-    def compare(self, baseline, policy, members, n_steps, history_steps=None, where="all", rows=None):
+    def compare(self, baseline, policy, members, n_steps, history_steps=None, where="all", rows=None, quantiles=None, quantile_method="nearest"):
         """A policy against a baseline, member by member and PAIRED: every member (as for run()) is run for n_steps steps under
         the base parameters changed by `baseline` and by its own overrides, that run is kept on the device
         (Simulator.keep_baseline), and the member is run again under `policy` instead of `baseline` with the same seed and the
@@ -833,8 +898,10 @@ class Ensemble:
         member is also folded into the paired accumulators (Simulator.ensemble_begin_paired) and the result carries
         paired_summary of them.  history_steps: None, or the steps of a shared history that is run once under the base
         parameters and kept (Simulator.snapshot); both arms of every member are then branches from it (the rules of forecast():
-        no "index_cases" in a member, no other times or working hours in baseline or policy -- ValueError).  Returns a
-        CompareResult."""
+        no "index_cases" in a member, no other times or working hours in baseline or policy -- ValueError).
+        quantiles: None, or probabilities (with rows): the members' baseline - current per cell are kept on the device
+        (Simulator.ensemble_keep_members) and CompareResult.averted_quantiles holds their quantiles, [n_q, n_rows, n_cols] --
+        int32 for quantile_method="nearest", float64 for "linear".  Returns a CompareResult."""
         sim = self.simulator
         n_steps = int(n_steps)
         baseline, policy = dict(baseline), dict(policy)
@@ -851,6 +918,9 @@ class Ensemble:
             fixed = sorted(k for k in self._FIXED_BY_HISTORY if k in baseline or k in policy)
             if fixed:
                 raise ValueError("Ensemble.compare: %s cannot change behind a shared history" % ", ".join(fixed))
+        keep = _keep_spec("Ensemble.compare", "paired", dict(quantiles=quantiles, quantile_method=quantile_method), len(members)) if quantiles is not None else None
+        if keep is not None and rows is None:
+            raise ValueError("Ensemble.compare: quantiles are taken of the paired rows: give rows= too")
         if rows is not None:
             unknown = set(rows) - {"first_step", "n_rows", "stride", "cumulative", "min_baseline", "min_averted"}
             if unknown:
@@ -859,6 +929,8 @@ class Ensemble:
             first, n_rows, stride = sim._compare_rows("Ensemble.compare", rows.get("first_step", 0), rows.get("n_rows"), rows.get("stride", 24), n_steps)
             rows.update(first_step=first, n_rows=n_rows, stride=stride)
             sim.ensemble_begin_paired(where, **rows)
+            if keep is not None and members:
+                sim.ensemble_keep_members(len(members))
         history = np.zeros(0, RECORD_DTYPE)
         if history_steps is not None:
             sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
@@ -884,7 +956,11 @@ class Ensemble:
                 sim.ensemble_fold()
         summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
         codes = self.area_codes if place == _lib.AREA_HOME else None
-        return CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
+        out = CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
+        if keep is not None and members and keep["probs"]:
+            out.quantile_probs = np.asarray(keep["probs"], np.float64)
+            out.averted_quantiles = sim.ensemble_quantiles(keep["probs"], keep["method"])
+        return out
 
     def close(self):
         self.simulator.close()

@@ -8,7 +8,9 @@ Same names, argument meaning and side effects as the reference API that `run` an
 The compute is the HIP library; this file only marshals.
 """
 import ctypes as C
+import fractions
 import json
+import math
 import os
 import time
 
@@ -77,6 +79,41 @@ def _memory_usage():
         return "%.2f GB" % (pages * os.sysconf("SC_PAGE_SIZE") / 1024 / 1024 / 1024.0)
     except OSError:
         return "0.00 GB"
+
+
+# -- the rank rules of the ensemble quantile maps (Simulator.ensemble_quantiles, Ensemble) -------
+def check_probs(who, probs):
+    """The probabilities as a list of floats; ValueError for one outside [0, 1] (NaN included)."""
+    out = [float(p) for p in probs]
+    for p in out:
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("%s: a probability must lie in [0, 1], got %r" % (who, p))
+    return out
+
+
+def nearest_rank(p, m):
+    """The 0-based rank of the inverted CDF among m members: the smallest value v with at least p * m members <= v, that is
+    max(0, ceil(p * m) - 1).  p is taken as the decimal it was written as (0.05 is 1/20, not the binary number next to it), so
+    that p * m is exact and 5 % of 20 members is the first of them."""
+    x = fractions.Fraction(repr(float(p))) * int(m)
+    return max(0, -((-x.numerator) // x.denominator) - 1)
+
+
+def linear_ranks(p, m):
+    """(lo, hi, frac): the neighbouring 0-based ranks of h = p * (m - 1) and the weight of the upper one, numpy's default
+    ("linear") definition; hi == lo where h is a whole number."""
+    h = float(p) * (int(m) - 1)
+    lo = min(int(math.floor(h)), int(m) - 1)
+    return lo, min(int(math.ceil(h)), int(m) - 1), h - lo
+
+
+def interpolate_linear(lo, hi, frac):
+    """float64: lo + (hi - lo) * frac per cell, NaN where either neighbour of an unsigned kind is _lib.NEVER."""
+    a, b = np.asarray(lo).astype(np.float64), np.asarray(hi).astype(np.float64)
+    out = a + (b - a) * float(frac)
+    if np.asarray(lo).dtype == np.uint32:
+        out[(np.asarray(lo) == _lib.NEVER) | (np.asarray(hi) == _lib.NEVER)] = np.nan
+    return out
 
 
 class Simulator:
@@ -391,6 +428,7 @@ class Simulator:
     def ensemble_begin(self, where="home", status_mask=(1 << _lib.EXPOSED) | (1 << _lib.INFECTED) | (1 << _lib.RECOVERED), min_cases=1):
         code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)
         self._ens_n = self._n_groups if code == _lib.BY_GROUP else self.population.n_areas
+        self._ens_rows = 1
         _lib.check(self.lib.esim_ensemble_begin(self._ctx, int(code), int(status_mask), int(min_cases)), self._ctx)
 
     def ensemble_begin_arrival(self, where="home", horizon=None):
@@ -398,6 +436,7 @@ class Simulator:
         reached the area (where="home") or group (where="group") by step `horizon`; None: within whatever steps it ran."""
         code = {"current": _lib.AREA_CURRENT, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP}.get(where, where)   # ("current": refused by the library)
         self._ens_n = self._n_groups if code == _lib.BY_GROUP else self.population.n_areas
+        self._ens_rows = 1
         _lib.check(self.lib.esim_ensemble_begin_arrival(self._ctx, int(code), _lib.NEVER if horizon is None else int(horizon)), self._ctx)
 
     def ensemble_fold(self):
@@ -535,6 +574,92 @@ class Simulator:
         ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint32 if i < 2 else C.c_uint64)) for i, k in enumerate(self.PEAKS_KEYS)]
         _lib.check(self.lib.esim_ensemble_read_peaks(self._ctx, C.byref(members), *ptrs), self._ctx)
         return dict(out, members=int(members.value))
+
+    # -- ensemble quantile maps: the members kept on the device, order statistics per cell (esim_ensemble_keep_members) -------
+    KEEP_WHAT = {"value": _lib.KEEP_VALUE, "peak_step": _lib.KEEP_PEAK_STEP, "duration": _lib.KEEP_DURATION}
+
+    def ensemble_keep_members(self, capacity, what="value"):
+        """Keeps every member folded from here on the device, beside the accumulators of the begin in force (any kind but
+        reproduction; call it behind the begin and in front of the first fold): capacity x rows x columns x 4 B.  A member's
+        value per cell: the census count, the arrival step (_lib.NEVER: not reached by the horizon), the cell of the series or
+        settings rows, baseline - current for the paired kind (signed), and for the peaks kind what="value" (the peak),
+        "peak_step" (_lib.NEVER without a peak) or "duration" (steps_at_least).  With the store full, ensemble_fold refuses."""
+        code = self.KEEP_WHAT.get(what, what)
+        if not isinstance(code, int):
+            raise ValueError("Simulator.ensemble_keep_members: what must be 'value', 'peak_step' or 'duration', got %r" % (what,))
+        _lib.check(self.lib.esim_ensemble_keep_members(self._ctx, int(capacity), code), self._ctx)
+
+    def ensemble_members_info(self):
+        """{"capacity", "kept", "what", "signed"} of the store (esim_ensemble_members_info)."""
+        cap, kept, what, signed = C.c_uint32(0), C.c_uint32(0), C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.esim_ensemble_members_info(self._ctx, C.byref(cap), C.byref(kept), C.byref(what), C.byref(signed)), self._ctx)
+        names = {v: k for k, v in self.KEEP_WHAT.items()}
+        return {"capacity": int(cap.value), "kept": int(kept.value), "what": names[int(what.value)], "signed": bool(signed.value)}
+
+    def _members_rows(self, first_row, n_rows):
+        total = max(1, int(getattr(self, "_ens_rows", 1)))
+        return int(first_row), (total - int(first_row) if n_rows is None else int(n_rows)), int(getattr(self, "_ens_n", self.population.n_areas))
+
+    def ensemble_members(self, first_member=0, n_members=None, first_row=0, n_rows=None):
+        """[members, rows, cols]: the values kept, members in the order of their folds; int32 for the paired kind, uint32
+        otherwise (esim_ensemble_read_members).  n_members=None: all from first_member on; n_rows=None: all from first_row on."""
+        info = self.ensemble_members_info()
+        first_row, n, cols = self._members_rows(first_row, n_rows)
+        m = info["kept"] - int(first_member) if n_members is None else int(n_members)
+        out = np.zeros((max(0, m), max(0, n), cols), np.uint32)
+        _lib.check(self.lib.esim_ensemble_read_members(self._ctx, int(first_member), max(0, m), first_row, max(0, n), out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out.view(np.int32) if info["signed"] else out
+
+    def _members_ranks(self, ranks, first_row, n_rows, signed):
+        first_row, n, cols = self._members_rows(first_row, n_rows)
+        ranks = np.ascontiguousarray(ranks, np.uint32).reshape(-1)
+        out = np.zeros((ranks.size, max(0, n), cols), np.uint32)
+        _lib.check(self.lib.esim_ensemble_quantiles(self._ctx, first_row, max(0, n), ranks.ctypes.data_as(C.POINTER(C.c_uint32)), ranks.size,
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out.view(np.int32) if signed else out
+
+    def ensemble_quantiles(self, probs=(0.05, 0.5, 0.95), method="nearest", first_row=0, n_rows=None, ranks=None):
+        """[len(probs), rows, cols]: quantiles per cell over the members kept, selected on the device (esim_ensemble_quantiles).
+        method="nearest": the inverted CDF, the smallest value v with at least p * M members <= v -- rank max(0, ceil(p * M) - 1),
+        an exact integer array (int32 for the paired kind, uint32 otherwise; _lib.NEVER sorts last).  method="linear": numpy's
+        default, the two neighbouring ranks of p * (M - 1) interpolated in float64, NaN where either is _lib.NEVER.  ranks=
+        (0-based, any order, at most 16 a call here too) bypasses both and returns those order statistics."""
+        info = self.ensemble_members_info()
+        kept, signed = info["kept"], info["signed"]
+        if ranks is not None:
+            return self._members_ranks(ranks, first_row, n_rows, signed)
+        if method not in ("nearest", "linear"):
+            raise ValueError("Simulator.ensemble_quantiles: method must be 'nearest' or 'linear', got %r" % (method,))
+        probs = check_probs("Simulator.ensemble_quantiles", probs)
+        if kept == 0 or not probs:
+            return self._members_ranks(np.zeros(len(probs), np.uint32), first_row, n_rows, signed)     # (the library's refusal)
+        if method == "nearest":
+            want = [nearest_rank(p, kept) for p in probs]
+        else:
+            pairs = [linear_ranks(p, kept) for p in probs]
+            want = [r for lo, hi, _ in pairs for r in (lo, hi)]
+        distinct = sorted(set(want))
+        got = {}
+        for i in range(0, len(distinct), _lib.RANKS_MAX):
+            part = distinct[i:i + _lib.RANKS_MAX]
+            for r, plane in zip(part, self._members_ranks(part, first_row, n_rows, signed)):
+                got[r] = plane
+        if method == "nearest":
+            return np.stack([got[r] for r in want])
+        return np.stack([interpolate_linear(got[lo], got[hi], frac) for lo, hi, frac in pairs])
+
+    def ensemble_exceedance(self, thresholds, first_row=0, n_rows=None):
+        """uint32 [len(thresholds), rows, cols]: the members kept whose value is >= each threshold, chosen after the folds
+        (esim_ensemble_exceedance; at most 16 thresholds a call of the library, more are split here).  Signed comparison for the
+        paired kind; where _lib.NEVER occurs (arrival, peak_step) a member at it counts as >= every threshold."""
+        first_row, n, cols = self._members_rows(first_row, n_rows)
+        thr = np.ascontiguousarray(thresholds, np.int64).reshape(-1)
+        out = np.zeros((thr.size, max(0, n), cols), np.uint32)
+        for i in range(0, max(1, thr.size), _lib.RANKS_MAX):                       # (out[i:i + k] is contiguous: the library writes into it)
+            k = min(_lib.RANKS_MAX, thr.size - i)
+            _lib.check(self.lib.esim_ensemble_exceedance(self._ctx, first_row, max(0, n), thr[i:].ctypes.data_as(C.POINTER(C.c_int64)), k,
+                                                         out[i:].ctypes.data_as(C.POINTER(C.c_uint32))), self._ctx)
+        return out
 
     def download_state(self):
         n = self.population.n_citizens

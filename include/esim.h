@@ -999,6 +999,46 @@ int  esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t status_mask, u
 int  esim_ensemble_read_peaks(esim_ctx *ctx, uint32_t *members, uint32_t *defined, uint32_t *hit, uint64_t *sum_peak, uint64_t *sumsq_peak,
                               uint64_t *sum_step, uint64_t *sumsq_step, uint64_t *sum_duration, uint64_t *sumsq_duration);
 
+/* Ensemble quantile maps: the members of an ensemble kept on the device, one value x per cell and member, and order
+ * statistics and exceedance counts per cell taken there -- for the distributions whose mean and variance mislead (an area
+ * reached in 3 members of 32), and for thresholds chosen after the folds.
+ * keep:  esim_ensemble_keep_members comes after a begin of any kind but the reproduction kind and before that begin's first fold.
+ *        It allocates capacity * n_rows * n_cols * 4 B (n_rows = 1 for the kinds without rows); from then on every fold that
+ *        raises the member counter also writes the member's x into the next slot, one more launch or device-to-device copy on
+ *        the context's stream and no wait.  x per kind: the census kind, the count the fold adds to sum; arrival, the arrival
+ *        step, ESIM_NEVER where the entry was not reached by the horizon; series and settings, the cell of the member's rows;
+ *        paired, baseline - current as a signed number (is_signed = 1); peaks, by `what`: the peak (ESIM_KEEP_VALUE), its step
+ *        (ESIM_KEEP_PEAK_STEP, ESIM_NEVER without a peak) or steps_at_least (ESIM_KEEP_DURATION).  Every other kind takes
+ *        ESIM_KEEP_VALUE only.  ESIM_EINVAL: capacity 0 or above ESIM_MEMBERS_MAX, an unknown `what`, or one the kind does not
+ *        have; ESIM_ESTATE: no population, no valid begin in force, the reproduction kind, or a member folded since the begin;
+ *        ESIM_ENOMEM: the store does not fit.  A refusal leaves the accumulators and an earlier store as they were.  With the
+ *        store full, the fold is ESIM_ERANGE with nothing folded and nothing enqueued.  A fold that returns an error with
+ *        nothing folded keeps nothing; one that returns an audit's ESIM_ESIM with the member folded keeps the member.
+ * info:  capacity, members kept, `what` and whether x is signed, any pointer NULL; ESIM_ESTATE without a store.
+ * read:  out[(m * n_rows + r) * n_cols + col] = x of member first_member + m (in the order of the folds) in row first_row + r;
+ *        signed kinds as int32 bit patterns.
+ * quantiles:  out[(q * n_rows + r) * n_cols + col] = the ranks[q]-th smallest (0-based) x of the cell over the members kept;
+ *        the order is signed for the paired kind and unsigned otherwise, so that ESIM_NEVER sorts last: a quantile of
+ *        ESIM_NEVER says that the entry was not reached in at least that share of the members.  Ranks need be neither sorted
+ *        nor distinct.
+ * exceedance:  out[(t * n_rows + r) * n_cols + col] = the members kept with x >= thresholds[t], compared as signed numbers for
+ *        the paired kind and as unsigned ones otherwise; for the kinds in which ESIM_NEVER occurs (arrival, the step of the
+ *        peak) a member at ESIM_NEVER is >= every threshold.
+ *        The three are ESIM_ESTATE without a store or with nothing kept; ESIM_ERANGE for rows or members outside the store or a
+ *        rank >= the members kept; ESIM_EINVAL for a null output, no ranks or thresholds, or more than ESIM_RANKS_MAX.  They
+ *        wait for the stream and leave everything as it is.
+ * The store lives as long as the accumulators beside it: kept through esim_reset, esim_restart, esim_restart_seeded,
+ * esim_snapshot and esim_rollback; ended by a begin of any kind, a new upload, esim_destroy, and esim_set_groups when begun by
+ * group; not part of a checkpoint. */
+#define ESIM_MEMBERS_MAX 256
+#define ESIM_RANKS_MAX   16
+enum { ESIM_KEEP_VALUE = 0, ESIM_KEEP_PEAK_STEP = 1, ESIM_KEEP_DURATION = 2 };
+int  esim_ensemble_keep_members(esim_ctx *ctx, uint32_t capacity, int what);
+int  esim_ensemble_members_info(esim_ctx *ctx, uint32_t *capacity, uint32_t *kept, int *what, int *is_signed);
+int  esim_ensemble_read_members(esim_ctx *ctx, uint32_t first_member, uint32_t n_members, uint32_t first_row, uint32_t n_rows, uint32_t *out);
+int  esim_ensemble_quantiles(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const uint32_t *ranks, uint32_t n_ranks, uint32_t *out);
+int  esim_ensemble_exceedance(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const int64_t *thresholds, uint32_t n_thresholds, uint32_t *out);
+
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
  *   out[0] "Generate Exposures", out[1] "Apply Exposures", out[2] "Apply Interventions", out[3] total.
