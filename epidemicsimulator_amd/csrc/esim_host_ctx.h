@@ -198,6 +198,7 @@ struct esim_ctx_impl {
     esim_params P;
     Dev d;
     bool uploaded = false;
+    bool household_work = false;          // the uploaded population has a Household that is the work place of a citizen who does not live in it: the replays refuse it (settings_check)
     hipStream_t stream = nullptr;
     std::string err;
     // host copies needed for reset

@@ -28,6 +28,8 @@ int settings_check(esim_ctx_impl *c, const std::string &who)
     if (!c->uploaded) return fail(c, ESIM_ESTATE, who + ": no population uploaded");
     if (c->comm.world > 1 || c->d.n_global != c->d.n)
         return fail(c, ESIM_ESTATE, who + ": the context has a communicator of several ranks, or holds a shard (a household draw is replayed from the whole population's log)");
+    if (c->household_work)
+        return fail(c, ESIM_ESTATE, who + ": the population has a household that is the work place of a citizen who does not live in it; the replay counts only the residents among the Infected of a household and would credit exposures to the wrong setting");
     if (c->draw_seam.twice)
         return fail(c, ESIM_ESTATE, who + ": the run was branched from a snapshot that itself lay on a branch under another seed, exposure_chance or mask_effectiveness; a history mixed twice is not built");
     return ESIM_OK;

@@ -13,6 +13,7 @@ struct UploadHost {
     bool any_big = false;
     std::vector<uint32_t> res_off, res_idx, wrk_off, wrk_idx, room_off, room_idx;
     bool home_sorted = true;
+    bool household_work = false;                 // a Household is the work place of a citizen who does not live in it
 };
 
 // ---- validate the population contract and derive the static flags
@@ -49,6 +50,7 @@ int upload_validate(esim_ctx_impl *c, UploadHost &u)
                     return fail(c, ESIM_EINVAL, "esim_upload_population: school member without a room of that school");
                 u.room_fixed[i] = pop->room[i];
             }
+            else if (pop->building_type[wb] == ESIM_HOUSEHOLD) u.household_work = true;
         }
         u.fl[i] = f;
     }
@@ -414,6 +416,7 @@ extern "C" int esim_upload_population(esim_ctx *ctx, const esim_population *pop)
     if ((rc = upload_shard_tables(c, u))) return rc;
     if ((rc = upload_pinned(c, u))) return rc;
     upload_tuning(c, u);
+    c->household_work = u.household_work;
     c->uploaded = true;
     return esim_reset(ctx);
 }

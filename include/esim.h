@@ -443,7 +443,13 @@ int  esim_group_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_
  * esim_building_exposures: counts[b] = the exposures of steps [first_step, last_step] credited to building b, the hot-spot map;
  *        public transport is not counted.  ESIM_ERANGE: first_step == 0, last_step < first_step or beyond the steps run.
  * All three: ESIM_EINVAL for a null context or output and unknown arguments; ESIM_ESTATE before an upload and on a context
- * whose communicator has more than one rank (the rule of esim_restart) or that holds a shard; ESIM_ERANGE / ESIM_ENOMEM as
+ * whose communicator has more than one rank (the rule of esim_restart) or that holds a shard; ESIM_ESTATE, too, on a
+ * population in which a Household is the work_building of a citizen who does not live in it (found once, at the upload): rule 2
+ * counts the residents only, the workers standing in such a household would be missing from n_home, and exposures would be
+ * credited to the wrong setting, most of them without becoming unexplained.  esim_run, the records, the exposure log and every
+ * output that replays no draw (the census, the series, the arrival times, esim_curve_summary) take such a population as any
+ * other; every call below that builds on the settings -- the tree, the chains, the household and place outbreaks, the flows,
+ * the events, the contact-hours, the ensemble kinds that fold them -- refuses it in the same way.  ESIM_ERANGE / ESIM_ENOMEM as
  * the series calls give them; a sticky device-side error is reported as the series calls report it.  They leave the
  * simulation state, the records, the snapshot, the ensemble accumulators and the labels as they are.  Temporary device memory,
  * freed when the call returns: 4 B per citizen for the exposure steps, 1 B per citizen for the setting, 1 B per step for each
@@ -483,8 +489,8 @@ int  esim_building_exposures(esim_ctx *ctx, uint32_t first_step, uint32_t last_s
  * Generation: 0 for an index case, the infector's + 1 otherwise, ESIM_NEVER for a citizen never exposed or unexplained.
  * After an esim_rollback under another seed the bus keys and the pick of the entries up to the snapshot's step use the
  * snapshot's seed, as the household replay does.  After a rollback that changed bus_capacity these calls are ESIM_ESTATE (a bus
- * replay under two capacities is not built) until an esim_restart, esim_reset or upload; on a sharded context and on a history
- * mixed twice they are ESIM_ESTATE as the calls above.
+ * replay under two capacities is not built) until an esim_restart, esim_reset or upload; on a sharded context, on a history
+ * mixed twice and on a population with a household that is somebody else's work place they are ESIM_ESTATE as the calls above.
  * esim_transmission_tree: infector[c], n_candidates[c] (the k of c's exposure, 0 where there is none) and generation[c] per
  *        citizen.  Any pointer may be NULL; with all three NULL the audit still runs and its result is returned.
  * esim_offspring: counts[j] = the citizens exposed in steps [first_step, last_step] whose infector is j.  ESIM_ERANGE as
