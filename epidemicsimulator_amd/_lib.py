@@ -69,6 +69,14 @@ class StepResult(C.Structure):
 RECORD_FIELDS = [n for n, _ in StepResult._fields_]
 
 
+class BurdenParams(C.Structure):
+    _fields_ = [
+        ("n_groups", C.c_uint32), ("admit_thr", _u32p), ("death_thr", _u32p),
+        ("delay_unit", C.c_uint32), ("n_delay", C.c_uint32), ("delay_cdf", _u32p),
+        ("stay_unit", C.c_uint32), ("n_stay", C.c_uint32), ("stay_cdf", _u32p),
+    ]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [
         ("n_citizens", C.c_uint32), ("n_areas", C.c_uint32), ("citizens_per_school", C.c_uint32),
@@ -91,6 +99,7 @@ SYMBOLS = [
     "esim_comm_unique_id", "esim_comm_init_rccl", "esim_comm_init_callback", "esim_comm_set_timeout", "esim_debug_inject_error", "esim_comm_stats", "esim_run_sharded", "esim_shard_stats",
     "esim_read_records", "esim_synchronize",
     "esim_download_state", "esim_download_exposure_log", "esim_area_census", "esim_area_arrival", "esim_area_series", "esim_area_status_series", "esim_set_groups", "esim_group_census", "esim_group_series", "esim_exposure_settings", "esim_setting_series", "esim_building_exposures", "esim_transmission_tree", "esim_offspring", "esim_reproduction_series", "esim_mixing_matrix", "esim_transmission_chains", "esim_outbreaks", "esim_transmission_ages", "esim_household_outbreaks", "esim_household_final_sizes", "esim_household_sar", "esim_place_outbreaks", "esim_place_sizes", "esim_place_sar", "esim_contact_hours", "esim_area_flows", "esim_area_imports", "esim_area_invasion", "esim_lineage_areas", "esim_pair_stats", "esim_transmission_events", "esim_routes", "esim_ensemble_begin", "esim_ensemble_begin_arrival", "esim_ensemble_fold", "esim_ensemble_read", "esim_ensemble_begin_series", "esim_ensemble_read_series", "esim_ensemble_begin_settings", "esim_ensemble_begin_reproduction", "esim_ensemble_read_reproduction", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_snapshot", "esim_rollback", "esim_snapshot_info", "esim_snapshot_drop", "esim_baseline_keep", "esim_baseline_info", "esim_baseline_drop", "esim_compare", "esim_compare_series", "esim_ensemble_begin_paired", "esim_ensemble_read_paired", "esim_curve_summary", "esim_ensemble_begin_peaks", "esim_ensemble_read_peaks",
+    "esim_burden_set", "esim_burden_drop", "esim_burden_get", "esim_burden_outcomes", "esim_burden_series", "esim_burden_summary", "esim_ensemble_begin_burden_peaks",
     "esim_ensemble_keep_members", "esim_ensemble_members_info", "esim_ensemble_read_members", "esim_ensemble_quantiles", "esim_ensemble_exceedance", "esim_enable_phase_timing", "esim_phase_timings",
     "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters", "esim_debug_launches",
     "esim_last_error", "esim_destroy",
@@ -201,6 +210,13 @@ def load():
         "esim_curve_summary": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint64)]),
         "esim_ensemble_begin_peaks": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "esim_ensemble_read_peaks": (C.c_int, [vp, _u32p, _u32p, _u32p] + [C.POINTER(C.c_uint64)] * 6),
+        "esim_burden_set": (C.c_int, [vp, C.POINTER(BurdenParams)]),
+        "esim_burden_drop": (C.c_int, [vp]),
+        "esim_burden_get": (C.c_int, [vp] + [_u32p] * 9),
+        "esim_burden_outcomes": (C.c_int, [vp, _u32p, _u32p, _u8p]),
+        "esim_burden_series": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),
+        "esim_burden_summary": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint64), _u32p, _u32p]),
+        "esim_ensemble_begin_burden_peaks": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "esim_ensemble_keep_members": (C.c_int, [vp, C.c_uint32, C.c_int]),
         "esim_ensemble_members_info": (C.c_int, [vp, _u32p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "esim_ensemble_read_members": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),
@@ -251,6 +267,9 @@ BY_ALL = 4                            # esim_reproduction_series `where`, beside
 NO_LINEAGE = 0xFFFFFFFF               # ESIM_NO_LINEAGE: esim_transmission_chains' entry for a citizen whose chain reaches no index case
 MEMBERS_MAX, RANKS_MAX = 256, 16      # ESIM_MEMBERS_MAX, ESIM_RANKS_MAX: esim_ensemble_keep_members' capacity, ranks or thresholds a call
 KEEP_VALUE, KEEP_PEAK_STEP, KEEP_DURATION = range(3)   # ESIM_KEEP_*: `what` of esim_ensemble_keep_members
+BURDEN_BINS = 64                      # ESIM_BURDEN_BINS: the most entries of a delay or stay CDF of esim_burden_set
+BURDEN_ADMISSIONS, BURDEN_OCCUPANCY, BURDEN_DEATHS = range(3)   # ESIM_BURDEN_*: `what` of esim_burden_series
+BURDEN_NAMES = ("admissions", "occupancy", "deaths")
 AGE_BINS = 512                     # ESIM_AGE_BINS: the infectious ages esim_transmission_ages counts per setting
 HH_BINS = 64                          # ESIM_HH_BINS: household sizes and case counts of esim_household_final_sizes, the last bin open-ended
 PLACE_WORK, PLACE_ROOM, PLACE_SCHOOL = range(3)   # ESIM_PLACE_*: the `kind` of esim_place_outbreaks, esim_place_sizes, esim_place_sar
@@ -286,3 +305,38 @@ def default_params(**overrides):
             raise AttributeError("esim_params has no field %r" % k)
         setattr(p, k, v)
     return p
+
+
+def _burden_words(who, x):
+    """A table as uint32 words: integers as they are, probabilities p as min(int(p * 2**32), 0xFFFFFFFF)."""
+    import numpy as np
+    a = np.atleast_1d(np.asarray(x))
+    if a.ndim != 1:
+        raise ValueError("burden_tables: %s must be one-dimensional" % who)
+    if a.dtype.kind in "ui":
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("burden_tables: %s holds an integer outside uint32" % who)
+        return a.astype(np.uint32)
+    if a.size and not ((a >= 0.0) & (a <= 1.0)).all():
+        raise ValueError("burden_tables: %s holds a probability outside [0, 1]" % who)
+    return np.array([min(int(float(p) * 2 ** 32), 0xFFFFFFFF) for p in a], np.uint32)
+
+
+def burden_tables(p_admit, p_death, delay_pmf, stay_pmf, delay_unit=24, stay_unit=24):
+    """The severity tables of esim_burden_set as a dict of uint32 arrays and the two units.  p_admit, p_death: one entry per
+    group, probabilities (thresholds by min(int(p * 2**32), 0xFFFFFFFF)) or integer thresholds, taken as they are.  delay_pmf:
+    the probabilities of a delay of 0, 1, 2, ... units between onset and admission; stay_pmf: those of a stay of 1, 2, 3, ...
+    units.  Their cumulative sums become the CDFs the same way: n entries give n + 1 outcomes, the last one with the
+    probability that is left (a pmf given in full ends in a CDF entry that only the largest draw reaches).  Integer arrays are
+    taken as the CDFs themselves."""
+    import numpy as np
+
+    def cdf(who, pmf):
+        a = np.atleast_1d(np.asarray(pmf))
+        return _burden_words(who, a if a.dtype.kind in "ui" else np.minimum(np.cumsum(a.astype(np.float64)), 1.0))
+
+    out = dict(admit_thr=_burden_words("p_admit", p_admit), death_thr=_burden_words("p_death", p_death), delay_cdf=cdf("delay_pmf", delay_pmf),
+               stay_cdf=cdf("stay_pmf", stay_pmf), delay_unit=int(delay_unit), stay_unit=int(stay_unit))
+    if out["admit_thr"].shape != out["death_thr"].shape:
+        raise ValueError("burden_tables: p_admit and p_death must have one entry per group each")
+    return out

@@ -31,6 +31,7 @@
 #include "esim_host_contacts.h"
 #include "esim_host_flows.h"
 #include "esim_host_curves.h"
+#include "esim_host_burden.h"
 #include "esim_host_events.h"
 #include "esim_host_ckpt.h"
 #include "esim_host_snapshot.h"

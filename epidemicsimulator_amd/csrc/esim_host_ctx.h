@@ -102,6 +102,7 @@ struct Ensemble {
         unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
         uint32_t last = 0, threshold = 0;         // ROWS_PEAKS: the window [first, last], the threshold of the duration (mask: the statuses, min: min_peak)
         unsigned long long *sum_d = nullptr, *sumsq_d = nullptr;   // ... sums of the duration and of its square
+        bool burden = false;                      // ... the curve a fold summarises: bed occupancy (esim_ensemble_begin_burden_peaks) instead of a status
         uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
     } rows;
     bool series = false;
@@ -121,6 +122,16 @@ struct Ensemble {
 struct Groups {
     uint16_t *lab = nullptr; uint32_t n = 0;
     uint32_t *size = nullptr, *cnt = nullptr;
+};
+
+// esim_burden_set: the severity tables in force, on the host as they were given and on the device as the kernels
+// read them: admit_thr [n_groups], death_thr [n_groups], delay_cdf [ESIM_BURDEN_BINS], stay_cdf [ESIM_BURDEN_BINS] in one
+// allocation.  set == false: none.
+struct BurdenState {
+    bool set = false;
+    uint32_t n_groups = 0, n_delay = 0, n_stay = 0, delay_unit = 0, stay_unit = 0;
+    std::vector<uint32_t> host;
+    uint32_t *tab = nullptr;
 };
 
 // esim_baseline_keep: the exposure step of every citizen of a finished run, one uint32 per citizen on the device (0 for an index
@@ -234,6 +245,7 @@ struct esim_ctx_impl {
     Groups grp;
     Snapshot snap;
     Baseline base;
+    BurdenState burden;
     Seam seam;
     DrawSeam draw_seam;               // of the history the context stands on
     DrawSeam snap_draw_seam;          // of the history under the snapshot held (esim_snapshot copies it, esim_rollback starts from it)

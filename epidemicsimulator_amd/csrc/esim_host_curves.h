@@ -34,13 +34,17 @@ int curve_check(esim_ctx_impl *c, const std::string &who, const CurveSpec &s)
     return ESIM_OK;
 }
 
+// What puts a curve's change points into the pair table between pairs_begin and pairs_sorted: nullptr for the status curves of
+// k_curve_events, or another family's enqueuer with its own launch (esim_host_burden.h).  q: as k_curve_events reads it.
+typedef void (*CurveEvents)(esim_ctx_impl *c, const Series &q, uint32_t last, uint32_t log_len, const PairTable &t, void *user);
+
 uint32_t curve_cols(const esim_ctx_impl *c, int where) { return where == ESIM_BY_ALL ? 1u : where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; }
 
 // The summary of the run as it stands into w->t, on the context's stream: the change points of every case's interval into the
 // pair table, compacted and sorted by (column, step), scanned per column and reduced.  The stream is waited for twice on the
 // way -- for the control block and the records, and for the number of distinct change points -- and not behind the reduction:
 // the caller waits.  A failure behind the first launch waits for the stream (flows_unwind): the kernels use the work struct's memory.
-int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, CurveWork *w)
+int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, CurveWork *w, CurveEvents events = nullptr, void *user = nullptr)
 {
     const uint32_t t_done = c->host_t - 1u;
     if (s.last > t_done) return fail(c, ESIM_ERANGE, who + ": last_step lies beyond the steps run so far");
@@ -70,7 +74,8 @@ int curve_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, 
     q.first = s.first; q.t_done = t_done; q.t_all = shape.t_all; q.vax_of = replay ? vax : nullptr; q.n_cols = cols;
     q.key = s.where == ESIM_BY_ALL ? CURVE_BY_ALL : s.where == ESIM_BY_GROUP ? (uint32_t)KEY_GROUP : (uint32_t)KEY_HOME;
     q.grp = s.where == ESIM_BY_GROUP ? c->grp.lab : nullptr;
-    hipLaunchKernelGGL(k_curve_events, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, s.mask, s.last, log_len, w->p.t);
+    if (events) events(c, q, s.last, log_len, w->p.t, user);
+    else hipLaunchKernelGGL(k_curve_events, dim3(grid_capped(c, log_len, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, s.mask, s.last, log_len, w->p.t);
     if ((rc = pairs_sorted(c, &w->p))) return flows_unwind(c, rc);
     if (w->p.dropped) {                                                      // (ESIM_PAIR_LOG2 too small: nothing is reduced)
         (void)hipStreamSynchronize(c->stream);
@@ -118,16 +123,12 @@ extern "C" int esim_curve_summary(esim_ctx *ctx, int where, uint32_t status_mask
 }
 
 namespace {
-// One member folded into the accumulators of the peaks kind: its summary in temporary memory, the fold kernel, the wait.
-int fold_peaks(esim_ctx_impl *c)
+int fold_burden_peaks(esim_ctx_impl *c);   // (esim_host_burden.h: a member's occupancy curve, where Rows::burden says so)
+
+// Behind curve_enqueue: the member's tables in w folded into the accumulators, kept where members are kept, and the wait.
+int fold_peaks_tables(esim_ctx_impl *c, const std::string &who, CurveWork &w)
 {
     Ensemble::Rows &r = c->ens.rows;
-    const std::string who = "esim_ensemble_fold";
-    const CurveSpec s = { c->ens.where, r.mask, r.first, r.last, r.threshold };
-    if (int rc = curve_check(c, who, s)) return rc;
-    if (curve_cols(c, s.where) != r.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
-    CurveWork w;
-    if (int rc = curve_enqueue(c, who, s, &w)) return rc;
     PeakAcc a;
     a.defined = r.defined; a.hit = r.hit; a.members = r.members;
     a.sum_peak = r.sum; a.sq_peak = r.sumsq; a.sum_step = r.sum_o; a.sq_step = r.sumsq_o; a.sum_dur = r.sum_d; a.sq_dur = r.sumsq_d;
@@ -139,15 +140,26 @@ int fold_peaks(esim_ctx_impl *c)
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e));
     return pairs_end(c, who, &w.p);
 }
-}  // namespace
 
-extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step, uint32_t threshold, uint32_t min_peak)
+// One member folded into the accumulators of the peaks kind: its summary in temporary memory, the fold kernel, the wait.
+int fold_peaks(esim_ctx_impl *c)
 {
-    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    const std::string who = "esim_ensemble_begin_peaks";
-    if (min_peak == 0u) return fail(c, ESIM_EINVAL, who + ": min_peak 0");
-    const CurveSpec s = { where, status_mask, first_step, last_step, threshold };
+    Ensemble::Rows &r = c->ens.rows;
+    if (r.burden) return fold_burden_peaks(c);
+    const std::string who = "esim_ensemble_fold";
+    const CurveSpec s = { c->ens.where, r.mask, r.first, r.last, r.threshold };
     if (int rc = curve_check(c, who, s)) return rc;
+    if (curve_cols(c, s.where) != r.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
+    CurveWork w;
+    if (int rc = curve_enqueue(c, who, s, &w)) return rc;
+    return fold_peaks_tables(c, who, w);
+}
+
+// The begin of the peaks kind behind its caller's checks: the accumulators allocated or reused and zeroed.  burden: a fold
+// summarises the occupancy curve of esim_burden_summary instead of the status curve of the mask.
+int peaks_begin(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, uint32_t min_peak, bool burden)
+{
+    const int where = s.where;
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint32_t cols = curve_cols(c, where);
     Ensemble::Rows &old = c->ens.rows;
@@ -169,7 +181,7 @@ extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t stat
     }
     Ensemble::Rows &r = c->ens.rows;
     r.kind = Ensemble::ROWS_PEAKS; r.n_rows = 1u; r.n_cols = cols; r.two = false;
-    r.mask = status_mask; r.first = first_step; r.last = last_step; r.threshold = threshold; r.min = min_peak;
+    r.mask = s.mask; r.first = s.first; r.last = s.last; r.threshold = s.threshold; r.min = min_peak; r.burden = burden;
     for (uint32_t *p : { r.hit, r.defined }) HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(uint32_t) * std::max<size_t>(1, cols), c->stream));
     for (unsigned long long *p : { r.sum, r.sumsq, r.sum_o, r.sumsq_o, r.sum_d, r.sumsq_d })
         HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(unsigned long long) * std::max<size_t>(1, cols), c->stream));
@@ -177,6 +189,17 @@ extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t stat
     c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
     members_end(c);
     return ESIM_OK;
+}
+}  // namespace
+
+extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t status_mask, uint32_t first_step, uint32_t last_step, uint32_t threshold, uint32_t min_peak)
+{
+    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
+    const std::string who = "esim_ensemble_begin_peaks";
+    if (min_peak == 0u) return fail(c, ESIM_EINVAL, who + ": min_peak 0");
+    const CurveSpec s = { where, status_mask, first_step, last_step, threshold };
+    if (int rc = curve_check(c, who, s)) return rc;
+    return peaks_begin(c, who, s, min_peak, false);
 }
 
 extern "C" int esim_ensemble_read_peaks(esim_ctx *ctx, uint32_t *members, uint32_t *defined, uint32_t *hit, uint64_t *sum_peak, uint64_t *sumsq_peak,

@@ -333,6 +333,7 @@ int fold_series(esim_ctx_impl *c)
 int fold_transmission(esim_ctx_impl *c);   // (esim_host_ensrows.h: the settings and the reproduction kind)
 int fold_paired(esim_ctx_impl *c);         // (esim_host_compare.h: the paired kind)
 int fold_peaks(esim_ctx_impl *c);          // (esim_host_curves.h: the peaks kind)
+void burden_forget(esim_ctx_impl *c);      // (esim_host_burden.h: the severity tables dropped)
 }  // namespace
 
 extern "C" int esim_area_census(esim_ctx *ctx, int where, uint32_t *counts)
@@ -559,6 +560,7 @@ extern "C" int esim_set_groups(esim_ctx *ctx, const uint16_t *group, uint32_t n_
     dev_free(c, c->grp.lab); dev_free(c, c->grp.size); dev_free(c, c->grp.cnt);
     c->grp.lab = lab; c->grp.size = sz; c->grp.cnt = cnt; c->grp.n = group ? n_groups : 0u;
     if (c->ens.where == ESIM_BY_GROUP) c->ens.valid = false;
+    if (c->burden.set && c->burden.n_groups != 1u && c->burden.n_groups != c->grp.n) burden_forget(c);   // (tables per group of labels that are gone)
     return ESIM_OK;
 }
 

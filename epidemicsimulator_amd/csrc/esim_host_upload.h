@@ -155,6 +155,7 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     c->grp = Groups();                                             // (the labels belong to the population they were set for)
     c->snap = Snapshot();                                          // (so does a snapshot: its buffers went with the rest)
     c->base = Baseline();                                          // (and a kept baseline)
+    c->burden = BurdenState();                                     // (and the severity tables: their groups are this population's labels)
     Dev &d = c->d;
     std::memset(&d, 0, sizeof d);
     d.n = N; d.n_global = u.n_global; d.id_base = pop->citizen_id_base; d.n_bld = B; d.n_room = R;

@@ -60,4 +60,4 @@ ESIM_HD uint32_t esim_u32(uint64_t seed, uint32_t citizen, uint32_t step, uint32
 
 // draw slots (RNG contract)
 enum { ESIM_SLOT_HOME = 0, ESIM_SLOT_WORK = 1, ESIM_SLOT_BUS = 2, ESIM_SLOT_BUS_ORDER = 3,
-       ESIM_SLOT_VACCINE = 4, ESIM_SLOT_INFECTOR = 5, ESIM_SLOT_ROOM0 = 16 };   // (6 .. 15: free)
+       ESIM_SLOT_VACCINE = 4, ESIM_SLOT_INFECTOR = 5, ESIM_SLOT_BURDEN = 6, ESIM_SLOT_ROOM0 = 16 };   // (7 .. 15: free)

@@ -193,7 +193,8 @@ class EnsembleResult:
         hit, mean, var, and codes where area codes were given -- and ensemble_areas.json is then null, as without a summary; the
         summary of area kind "settings" goes to ensemble_area_settings.npz the same way, that of kind "reproduction" to
         ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes; that of
-        kind "peaks" to ensemble_area_peaks.npz: the arrays of peaks_summary, members, and codes.  The members' exposures by setting, where they
+        kind "peaks" to ensemble_area_peaks.npz: the arrays of peaks_summary, members, and codes (kind "burden_peaks": the same of
+        the bed occupancy, to ensemble_area_burden.npz).  The members' exposures by setting, where they
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
         ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names.  The quantile maps, where the area dict
         asked for them, go to ensemble_area_quantiles.npz: probs, quantiles, thresholds, exceed, steps for a summary over rows, and
@@ -206,12 +207,12 @@ class EnsembleResult:
         with open(os.path.join(directory, "ensemble_stats.json"), "w") as fh:
             json.dump(stats, fh)
         doc = None
-        if self.area is not None and self.area_kind == "peaks":      # arrays by column: nine of them, too many for the JSON's three
+        if self.area is not None and self.area_kind in ("peaks", "burden_peaks"):      # arrays by column: nine of them, too many for the JSON's three
             arrays = {k: self.area[k] for k in PEAKS_ARRAYS}
             arrays["members"] = np.asarray(self.area["members"], np.uint32)
             if self.area_codes is not None:
                 arrays["codes"] = np.asarray(self.area_codes)
-            np.savez(os.path.join(directory, "ensemble_area_peaks.npz"), **arrays)
+            np.savez(os.path.join(directory, "ensemble_area_burden.npz" if self.area_kind == "burden_peaks" else "ensemble_area_peaks.npz"), **arrays)
         elif self.area is not None and "steps" in self.area:     # a summary over rows: arrays by (row, column), too many for JSON
             a = self.area
             ratio = "r" in a
@@ -524,25 +525,29 @@ def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_met
     if method not in ("nearest", "linear"):
         raise ValueError("%s: quantile_method must be 'nearest' or 'linear', got %r" % (who, method))
     what = given.get("keep", "value")
-    if what not in Simulator.KEEP_WHAT or (what != "value" and kind != "peaks"):
+    if what not in Simulator.KEEP_WHAT or (what != "value" and kind not in ("peaks", "burden_peaks")):
         raise ValueError("%s: keep must be 'value', or for the peaks kind 'peak_step' or 'duration', got %r" % (who, what))
     if n_members is not None and int(n_members) > _lib.MEMBERS_MAX:
         raise ValueError("%s: %d members, the store of the quantile maps takes %d (ESIM_MEMBERS_MAX)" % (who, int(n_members), _lib.MEMBERS_MAX))
     return dict(probs=probs, method=method, thresholds=[int(t) for t in (given.get("exceed") or ())], what=what)
 
 
-_KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks")
-_ROW_KINDS = ("series", "settings", "reproduction", "peaks")      # a member that stopped early has no rows behind its last step
+_KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks")
+_ROW_KINDS = ("series", "settings", "reproduction", "peaks", "burden_peaks")      # a member that stopped early has no rows behind its last step
 
 
 class Ensemble:
     """Owns one Simulator; every member is a restart of it under the base parameters changed by the member's overrides."""
 
-    def __init__(self, population, params=None, area_codes=None, group=None):
-        """group: None, or (labels, n_groups) for Simulator.set_groups -- what run(area=dict(where="group", ...)) counts by."""
+    def __init__(self, population, params=None, area_codes=None, group=None, burden=None):
+        """group: None, or (labels, n_groups) for Simulator.set_groups -- what run(area=dict(where="group", ...)) counts by.
+        burden: None, or the tables of _lib.burden_tables for Simulator.set_burden, set once for every member -- what
+        run(area=dict(kind="burden_peaks", ...)) summarises (tables of several groups need `group` with as many)."""
         self.simulator = Simulator(population, params, area_codes=area_codes)
         if group is not None:
             self.simulator.set_groups(*group)
+        if burden is not None:
+            self.simulator.set_burden(burden)
         self.area_codes = area_codes
         self.base = _lib.Params()
         C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
@@ -560,7 +565,7 @@ class Ensemble:
         area = dict(area)
         kind = area.pop("kind", "census")
         if kind not in _KINDS:
-            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction' or 'peaks', got %r" % (who, kind))
+            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction', 'peaks' or 'burden_peaks', got %r" % (who, kind))
         self._keep_spec = _keep_spec("Ensemble." + who, kind, area, n_members)
         if kind in _ROW_KINDS and stop_when_done:
             raise ValueError("Ensemble.%s: area kind %r cannot go with stop_when_done=True (a member that stopped early has no "
@@ -568,7 +573,7 @@ class Ensemble:
         if kind == "settings" and area.get("n_rows") is None:
             first, stride = int(area.get("first_step", 1)), int(area.get("stride", 1))
             area["n_rows"] = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
-        if kind == "peaks" and area.get("last_step") is None:
+        if kind in ("peaks", "burden_peaks") and area.get("last_step") is None:
             area["last_step"] = int(n_steps)
         if kind == "reproduction":
             complete = area.pop("complete", True)
@@ -590,7 +595,8 @@ class Ensemble:
         sim = self.simulator
         if kind is not None:
             getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
-                          "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks"}[kind])(**area)
+                          "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks",
+                          "burden_peaks": "ensemble_begin_burden_peaks"}[kind])(**area)
 
     def _keep_begin(self, n_members):
         """Behind the begin: the store of the quantile maps, where the area dict asked for them."""
@@ -604,7 +610,7 @@ class Ensemble:
         if spec is None or summary is None or not n_members:
             return summary
         sim = self.simulator
-        flat = (lambda a: a[:, 0]) if kind in ("census", "arrival", "peaks") else (lambda a: a)
+        flat = (lambda a: a[:, 0]) if kind in ("census", "arrival", "peaks", "burden_peaks") else (lambda a: a)
         out = dict(summary, probs=np.asarray(spec["probs"], np.float64), thresholds=np.asarray(spec["thresholds"], np.int64))
         out["quantiles"] = flat(sim.ensemble_quantiles(spec["probs"], spec["method"])) if spec["probs"] else None
         out["exceed"] = flat(sim.ensemble_exceedance(spec["thresholds"])) if spec["thresholds"] else None
@@ -614,7 +620,7 @@ class Ensemble:
         sim = self.simulator
         if kind is None:
             return None
-        if kind == "peaks":
+        if kind in ("peaks", "burden_peaks"):
             return peaks_summary(sim.ensemble_read_peaks())
         if kind == "reproduction":
             return reproduction_summary(sim.ensemble_read_reproduction(), area.get("first_step", 0), area.get("stride", 24))
@@ -809,7 +815,10 @@ class Ensemble:
         n_rows=..., stride=..., min_cohort=..., r=(num, den), complete=True) for the cohort rows (Simulator.
         ensemble_begin_reproduction; the summary is a reproduction_summary); or dict(kind="peaks", where=..., status=...,
         first_step=..., last_step=..., threshold=..., min_peak=...) for the shape of every member's curve per column
-        (Simulator.ensemble_begin_peaks; last_step=None: n_steps; the summary is a peaks_summary).  With complete=True and n_rows=None only complete
+        (Simulator.ensemble_begin_peaks; last_step=None: n_steps; the summary is a peaks_summary); or dict(kind="burden_peaks",
+        where=..., first_step=..., last_step=..., threshold=..., min_peak=...) for the same of every member's bed occupancy
+        under the tables of Ensemble(..., burden=...) (Simulator.ensemble_begin_burden_peaks: per column P(peak occupancy >=
+        min_peak) and the mean and deviation of peak, peak step and duration).  With complete=True and n_rows=None only complete
         cohort rows are taken -- an incomplete cohort biases R down -- and ValueError is raised when there is none.  Neither goes
         with stop_when_done=True.
         Every kind but reproduction also takes quantiles=(0.05, 0.5, 0.95), quantile_method="nearest" or "linear", exceed=(1, 5)

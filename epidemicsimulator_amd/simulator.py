@@ -575,6 +575,78 @@ class Simulator:
         _lib.check(self.lib.esim_ensemble_read_peaks(self._ctx, C.byref(members), *ptrs), self._ctx)
         return dict(out, members=int(members.value))
 
+    # -- hospital burden: admissions, bed occupancy and deaths over a finished run (esim_burden_*) -------
+    BURDEN_KEYS = ("peak", "peak_step", "steps_at_least", "first_at_least", "last_at_least", "bed_steps", "admissions", "deaths")
+
+    def set_burden(self, tables=None, **kw):
+        """The severity tables in force (esim_burden_set): the dict of _lib.burden_tables, or its arguments as keywords.  Tables
+        of several groups need set_groups with as many groups first.  They stay through restart, snapshot and rollback."""
+        t = dict(tables) if tables is not None else _lib.burden_tables(**kw)
+        arr = {k: np.ascontiguousarray(t[k], np.uint32) for k in ("admit_thr", "death_thr", "delay_cdf", "stay_cdf")}
+        if arr["admit_thr"].shape != arr["death_thr"].shape or arr["admit_thr"].ndim != 1:
+            raise ValueError("Simulator.set_burden: admit_thr and death_thr must have one entry per group each")
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        p = _lib.BurdenParams(arr["admit_thr"].size, ptr(arr["admit_thr"]), ptr(arr["death_thr"]), int(t.get("delay_unit", 24)), arr["delay_cdf"].size,
+                              ptr(arr["delay_cdf"]), int(t.get("stay_unit", 24)), arr["stay_cdf"].size, ptr(arr["stay_cdf"]))
+        _lib.check(self.lib.esim_burden_set(self._ctx, C.byref(p)), self._ctx)
+
+    def drop_burden(self):
+        _lib.check(self.lib.esim_burden_drop(self._ctx), self._ctx)
+
+    def burden(self):
+        """The tables in force as set_burden takes them (esim_burden_get); EsimError (ESTATE) without any."""
+        n = [C.c_uint32(0) for _ in range(5)]               # n_groups, delay_unit, n_delay, stay_unit, n_stay
+        _lib.check(self.lib.esim_burden_get(self._ctx, C.byref(n[0]), None, None, C.byref(n[1]), C.byref(n[2]), None, C.byref(n[3]), C.byref(n[4]), None), self._ctx)
+        admit, death = np.zeros(n[0].value, np.uint32), np.zeros(n[0].value, np.uint32)
+        delay, stay = np.zeros(_lib.BURDEN_BINS, np.uint32), np.zeros(_lib.BURDEN_BINS, np.uint32)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        _lib.check(self.lib.esim_burden_get(self._ctx, None, ptr(admit), ptr(death), None, None, ptr(delay), None, None, ptr(stay)), self._ctx)
+        return dict(admit_thr=admit, death_thr=death, delay_cdf=delay[:n[2].value].copy(), stay_cdf=stay[:n[4].value].copy(),
+                    delay_unit=int(n[1].value), stay_unit=int(n[3].value))
+
+    def burden_outcomes(self):
+        """{"admit_step", "end_step": uint32 [n_citizens], _lib.NEVER where the citizen is no admitted case; "died": bool
+        [n_citizens]} (esim_burden_outcomes).  A case occupies a bed after the steps admit_step .. end_step - 1 and, where it
+        dies, dies at end_step; both may lie beyond the steps run."""
+        n = self.population.n_citizens
+        admit, end, died = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        _lib.check(self.lib.esim_burden_outcomes(self._ctx, admit.ctypes.data_as(C.POINTER(C.c_uint32)), end.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 died.ctypes.data_as(C.POINTER(C.c_uint8))), self._ctx)
+        return {"admit_step": admit, "end_step": end, "died": died.astype(bool)}
+
+    def _burden_where(self, where):
+        place = {"all": _lib.BY_ALL, "home": _lib.AREA_HOME, "group": _lib.BY_GROUP, "current": _lib.AREA_CURRENT}.get(where, where)   # ("current": refused by the library)
+        return int(place), 1 if place == _lib.BY_ALL else max(1, self._n_groups) if place == _lib.BY_GROUP else self.population.n_areas
+
+    def burden_series(self, what="occupancy", where="all", first_step=1, n_rows=None, stride=1):
+        """uint32 [n_rows, n_cols] over the steps already run (esim_burden_series): row i is step first_step + i * stride.
+        what: "occupancy" (beds occupied after that step), "admissions" or "deaths" (those of the `stride` steps from that one
+        on).  where: "all" (one column), "home" or "group".  n_rows=None: up to the last step run."""
+        code = {k: i for i, k in enumerate(_lib.BURDEN_NAMES)}.get(what, what)
+        place, n_cols = self._burden_where(where)
+        return self._series(self.lib.esim_burden_series, (place, code), n_cols, first_step, n_rows, stride)
+
+    def burden_summary(self, where="all", first_step=1, last_step=None, threshold=1):
+        """curve_summary of the bed occupancy over first_step .. last_step (None: the last step run), a dict of [n_cols] arrays
+        (esim_burden_summary): peak, peak_step, steps_at_least, first_at_least, last_at_least as there, bed_steps (uint64) the
+        sum of the curve, and the admissions and deaths of the window."""
+        place, n_cols = self._burden_where(where)
+        last = self._steps if last_step is None else int(last_step)
+        out = {k: np.zeros(n_cols, np.uint64 if k == "bed_steps" else np.uint32) for k in self.BURDEN_KEYS}
+        ptrs = [out[k].ctypes.data_as(C.POINTER(C.c_uint64 if k == "bed_steps" else C.c_uint32)) for k in self.BURDEN_KEYS]
+        _lib.check(self.lib.esim_burden_summary(self._ctx, place, int(first_step), last, int(threshold), *ptrs), self._ctx)
+        return out
+
+    def ensemble_begin_burden_peaks(self, where="all", first_step=1, last_step=None, threshold=1, min_peak=1):
+        """The peaks kind of the accumulators over the bed occupancy (esim_ensemble_begin_burden_peaks): ensemble_fold computes
+        the member's burden_summary(where, first_step, last_step, threshold) on the device and folds it as ensemble_begin_peaks
+        folds a status curve; ensemble_read_peaks reads them.  last_step=None: the last step of the run (params.max_steps)."""
+        place, n_cols = self._burden_where(where)
+        last = int(self.params.max_steps) if last_step is None else int(last_step)
+        _lib.check(self.lib.esim_ensemble_begin_burden_peaks(self._ctx, place, int(first_step), last, int(threshold), int(min_peak)), self._ctx)
+        self._ens_rows = 1
+        self._ens_n = n_cols
+
     # -- ensemble quantile maps: the members kept on the device, order statistics per cell (esim_ensemble_keep_members) -------
     KEEP_WHAT = {"value": _lib.KEEP_VALUE, "peak_step": _lib.KEEP_PEAK_STEP, "duration": _lib.KEEP_DURATION}
 

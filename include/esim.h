@@ -1045,6 +1045,72 @@ int  esim_ensemble_read_members(esim_ctx *ctx, uint32_t first_member, uint32_t n
 int  esim_ensemble_quantiles(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const uint32_t *ranks, uint32_t n_ranks, uint32_t *out);
 int  esim_ensemble_exceedance(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const int64_t *thresholds, uint32_t n_thresholds, uint32_t *out);
 
+/* Hospital burden: admissions, bed occupancy and deaths laid over a finished run.  In the model's SEIR(+V) rules
+ * nothing that happens to a case after its onset feeds back into transmission, so severity is drawn after the fact, one Philox
+ * block per case under the contract below, as the infector draw is.  No step kernel is touched; a run that never asks pays nothing.
+ * Steps are hours.
+ * Parameters: esim_burden_params holds thresholds per group (the labels of esim_set_groups; Population.age_bands gives age bands)
+ *        and two CDFs, all uint32: admit_thr[n_groups], death_thr[n_groups]; delay_cdf[n_delay] and stay_cdf[n_stay], ascending,
+ *        n_delay, n_stay <= ESIM_BURDEN_BINS (a count of 0 is a fixed delay of 0 / a fixed stay of one unit); 1 <= delay_unit,
+ *        stay_unit <= 65535.  esim_burden_set copies them to the device.  With n_groups > 1 it needs labels with the same n_groups
+ *        (ESIM_ESTATE otherwise); with n_groups == 1 no labels are needed: everybody is group 0.  ESIM_EINVAL: a null table,
+ *        n_groups 0 or above ESIM_MAX_GROUPS, a count above ESIM_BURDEN_BINS, a CDF that descends, a unit of 0 or above 65535.
+ *        The tables stay in force through esim_reset, esim_restart, esim_restart_seeded, esim_snapshot and esim_rollback; they are
+ *        dropped by an upload, by esim_burden_drop, and (tables of several groups) by an esim_set_groups with another group count;
+ *        not part of a checkpoint.  esim_burden_get returns the tables in force (any pointer NULL; the CDF outputs hold
+ *        ESIM_BURDEN_BINS entries, of which the counts are written); ESIM_ESTATE without tables.
+ * Cases: a citizen of the exposure log with an onset: onset = ts + exposed_time + 1 for the exposure step ts, 0 for an index case
+ *        -- the first step after which the citizen is Infected.  onset <= t_done must hold (t_done: the steps run), and a
+ *        citizen vaccinated at the end of step v is a case only if v - 1 >= onset: it was Infected after at least one step.  A
+ *        citizen vaccinated while Exposed is no case; a later vaccination changes nothing about a case's outcome.
+ * Draw:  for a case with global id g = citizen_id_base + c in group k, (w0, w1, w2, w3) = Philox4x32-10 over the counter
+ *        (g, onset, ESIM_SLOT_BURDEN = 6, 0) under the seed, the raw block.  After an esim_rollback under another seed the
+ *        snapshot's seed applies where onset <= the snapshot's step, the new one otherwise.
+ *          admitted    iff w0 < admit_thr[k]
+ *          admit_step  = onset + delay_unit * #{i : delay_cdf[i] <= w1}
+ *          end_step    = admit_step + stay_unit * (1 + #{i : stay_cdf[i] <= w2})
+ *          died        iff admitted and w3 < death_thr[k], at end_step
+ *        An admitted case occupies a bed after the steps admit_step .. end_step - 1.  All of it is determined at onset:
+ *        admit_step and end_step may lie beyond the steps run.
+ * esim_burden_outcomes: per citizen, admit_step and end_step (ESIM_NEVER where the citizen is no admitted case) and died (1 / 0);
+ *        any output may be NULL.
+ * esim_burden_series: rows [n_rows][n_cols] under the row conventions of esim_area_status_series.  what = ESIM_BURDEN_ADMISSIONS /
+ *        ESIM_BURDEN_DEATHS: event rows, a row sums the admissions (deaths) of the `stride` steps from its step on;
+ *        ESIM_BURDEN_OCCUPANCY: the beds occupied after the row's step.  where = ESIM_BY_ALL (one column), ESIM_AREA_HOME or
+ *        ESIM_BY_GROUP.  ESIM_ERANGE for first_step 0 and for rows beyond the steps run: what happens later appears in
+ *        esim_burden_outcomes and in no row.
+ * esim_burden_summary: esim_curve_summary of the occupancy curve over [first_step, last_step] -- peak, peak_step, steps_at_least,
+ *        first_at_least, last_at_least as there, bed_steps the sum of the curve -- and the admissions and the deaths whose step
+ *        lies inside the window, [n_cols] each, any NULL.  Arguments are checked as esim_curve_summary checks them; the pair
+ *        engine, scan and reduction are the same, and esim_pair_stats reports the call.
+ * esim_ensemble_begin_burden_peaks: the peaks kind of the ensemble accumulators over the occupancy curve: esim_ensemble_fold
+ *        summarises the member as esim_burden_summary does and folds it as the peaks kind folds a status curve;
+ *        esim_ensemble_read_peaks reads it, esim_ensemble_keep_members, quantiles and exceedance work behind it unchanged.
+ * Every call is ESIM_ESTATE before an upload, without tables in force, with tables of several groups whose labels are gone, on a
+ * context that holds a shard or has a communicator of several ranks; a refused call leaves its outputs untouched.  The calls
+ * leave the simulation state, the records and the exposure log as they are.  Temporary device memory as esim_curve_summary, plus
+ * 8 B per column (summary), 4 B per cell (series), 9 B per citizen (outcomes). */
+#define ESIM_BURDEN_BINS 64
+enum { ESIM_BURDEN_ADMISSIONS = 0, ESIM_BURDEN_OCCUPANCY = 1, ESIM_BURDEN_DEATHS = 2 };   /* `what` of esim_burden_series */
+typedef struct esim_burden_params {
+    uint32_t n_groups;
+    const uint32_t *admit_thr, *death_thr;         /* [n_groups] each */
+    uint32_t delay_unit, n_delay;
+    const uint32_t *delay_cdf;                     /* [n_delay] */
+    uint32_t stay_unit, n_stay;
+    const uint32_t *stay_cdf;                      /* [n_stay] */
+} esim_burden_params;
+int  esim_burden_set(esim_ctx *ctx, const esim_burden_params *p);
+int  esim_burden_drop(esim_ctx *ctx);
+int  esim_burden_get(esim_ctx *ctx, uint32_t *n_groups, uint32_t *admit_thr, uint32_t *death_thr, uint32_t *delay_unit, uint32_t *n_delay,
+                     uint32_t *delay_cdf, uint32_t *stay_unit, uint32_t *n_stay, uint32_t *stay_cdf);
+int  esim_burden_outcomes(esim_ctx *ctx, uint32_t *admit_step, uint32_t *end_step, uint8_t *died /* [n_citizens] each, any may be NULL */);
+int  esim_burden_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out /* [n_rows * n_cols] */);
+int  esim_burden_summary(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step, uint32_t threshold,
+                         uint32_t *peak, uint32_t *peak_step, uint32_t *steps_at_least, uint32_t *first_at_least, uint32_t *last_at_least,
+                         uint64_t *bed_steps, uint32_t *admissions, uint32_t *deaths /* [n_cols] each, any may be NULL */);
+int  esim_ensemble_begin_burden_peaks(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step, uint32_t threshold, uint32_t min_peak);
+
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
  *   out[0] "Generate Exposures", out[1] "Apply Exposures", out[2] "Apply Interventions", out[3] total.
