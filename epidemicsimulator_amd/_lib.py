@@ -297,14 +297,21 @@ def check(code, ctx=None):
         raise EsimError(code, text.decode() if text else "")
 
 
-def default_params(**overrides):
+def with_overrides(params, overrides):
+    """A copy of `params` with the fields of the dict `overrides` set; AttributeError for a field esim_params does not have."""
     p = Params()
-    load().esim_default_params(C.byref(p))
+    C.memmove(C.byref(p), C.byref(params), C.sizeof(Params))
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError("esim_params has no field %r" % k)
         setattr(p, k, v)
     return p
+
+
+def default_params(**overrides):
+    p = Params()
+    load().esim_default_params(C.byref(p))
+    return with_overrides(p, overrides)
 
 
 def _burden_words(who, x):

@@ -3,18 +3,23 @@ or under other index cases (where the outbreak starts), one member after another
 esim_restart_seeded), summarised per step on the host and per Output Area -- or per citizen group -- on the device
 (esim_ensemble_*); or, as a forecast, as branches from one snapshot of a shared history (esim_snapshot, esim_rollback).  The
 population is validated, hashed and uploaded once."""
-import ctypes as C
 import json
 import os
 
 import numpy as np
 
 from . import _lib
+from ._marshal import rate as _rate
 from .simulator import RECORD_DTYPE, Simulator, check_probs
 
 QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)           # the rows of ensemble_stats.json
 STAT_FIELDS = ("susceptible", "exposed", "infected", "recovered", "vaccinated", "exposures_building", "exposures_bus", "vaccinated_now")
 _EVENT_FIELDS = ("exposures_building", "exposures_bus", "vaccinated_now", "n_riders")   # what happens IN a step: zero in a step that did not run
+
+
+def _stack(rows, shape, dtype):
+    """The members' tables of `shape` as one array [members, *shape] of `dtype`; without members [0, *shape]."""
+    return np.stack(rows).astype(dtype) if rows else np.zeros((0,) + tuple(shape), dtype)
 
 
 def pad_records(rec, n_steps):
@@ -48,8 +53,8 @@ def arrival_summary(members, hit, total, sumsq):
     the population variance of the arrival step; both NaN where hit == 0."""
     hit = np.asarray(hit, np.uint32)
     total, sumsq, h = np.asarray(total, np.float64), np.asarray(sumsq, np.float64), hit.astype(np.float64)
+    mean = _rate(total, h)
     with np.errstate(invalid="ignore", divide="ignore"):
-        mean = np.where(hit > 0, total / h, np.nan)
         var = np.where(hit > 0, np.maximum(sumsq / h - mean * mean, 0.0), np.nan)
     return {"members": int(members), "hit": hit, "mean": mean, "var": var}
 
@@ -86,9 +91,8 @@ def reproduction_summary(acc, first_step=0, stride=24):
     sx, sy = np.asarray(acc["sum_cases"], np.uint64), np.asarray(acc["sum_offspring"], np.uint64)
     defined, hit = np.asarray(acc["defined"], np.uint32), np.asarray(acc["hit"], np.uint32)
     fx, fy = sx.astype(np.float64), sy.astype(np.float64)
+    r, p_r = _rate(sy, sx), _rate(hit, defined)
     with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.where(sx > 0, fy / fx, np.nan)
-        p_r = np.where(defined > 0, hit.astype(np.float64) / defined.astype(np.float64), np.nan)
         if m >= 2:
             resid = _ratio_residuals(sx, sy, acc["sumsq_cases"], acc["sumsq_offspring"], acc["sum_cross"])
             r_se = np.where(sx > 0, np.sqrt(resid * (m / (m - 1.0))) / (fx * fx), np.nan)
@@ -121,8 +125,7 @@ def paired_summary(acc, first_step=0, stride=24):
     defined, hit = np.asarray(acc["defined"], np.uint32), np.asarray(acc["hit"], np.uint32)
     fb, fc = sb.astype(np.float64), sc.astype(np.float64)
     diff = sb.astype(np.int64) - sc.astype(np.int64)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        p_averted = np.where(defined > 0, hit.astype(np.float64) / defined.astype(np.float64), np.nan)
+    p_averted = _rate(hit, defined)
     if m >= 2:
         wide = max((int(a.max()) if a.size else 0) for a in (sbb, scc, sbc)) >= 1 << 60
         sq = (lambda a: a.astype(object)) if wide else (lambda a: a.astype(np.int64))
@@ -281,6 +284,13 @@ class OutbreakResult:
         np.savez(os.path.join(directory, "ensemble_outbreaks.npz"), **arrays)
 
 
+def _size_and_pair_tables(sizes, pairs, bins, n_cols):
+    """The four stacked tables of HouseholdResult and PlaceResult from every member's two size tables, uint32 [bins, bins], and
+    two pair tables, uint64 [n_cols, n_cols]."""
+    return (*(_stack([t[i] for t in sizes], (bins, bins), np.uint32) for i in (0, 1)),
+            *(_stack([t[i] for t in pairs], (n_cols, n_cols), np.uint64) for i in (0, 1)))
+
+
 class HouseholdResult:
     """What Ensemble.households gathers: the final-size tables and the household pair tables of every member."""
 
@@ -294,19 +304,12 @@ class HouseholdResult:
     @classmethod
     def gathered(cls, members, sizes, pairs, n_cols=1):
         """From every member's Simulator.household_final_sizes() and household_sar() tuples."""
-        b = _lib.HH_BINS
-
-        def stack(rows, shape, dtype):
-            return np.stack(rows).astype(dtype) if rows else np.zeros((0,) + shape, dtype)
-        return cls(members, stack([t[0] for t in sizes], (b, b), np.uint32), stack([t[1] for t in sizes], (b, b), np.uint32),
-                   stack([t[0] for t in pairs], (n_cols, n_cols), np.uint64), stack([t[1] for t in pairs], (n_cols, n_cols), np.uint64))
+        return cls(members, *_size_and_pair_tables(sizes, pairs, _lib.HH_BINS, n_cols))
 
     def sar(self):
         """float64 [n_cols, n_cols]: the household secondary attack rate pooled over the members -- the sum of secondary
         divided by the sum of at_risk --, NaN where nobody was at risk."""
-        at, sec = self.at_risk.sum(axis=0).astype(np.float64), self.secondary.sum(axis=0).astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(at > 0, sec / at, np.nan)
+        return _rate(self.secondary.sum(axis=0), self.at_risk.sum(axis=0))
 
     def dump(self, directory):
         """ensemble_households.npz: final_size, introductions, at_risk, secondary and the pooled sar."""
@@ -328,27 +331,19 @@ class PlaceResult:
     @classmethod
     def gathered(cls, members, sizes, pairs, n_cols=1):
         """From every member's Simulator.place_sizes() and place_sar() tuples."""
-        b = _lib.PLACE_BINS
-
-        def stack(rows, shape, dtype):
-            return np.stack(rows).astype(dtype) if rows else np.zeros((0,) + shape, dtype)
-        return cls(members, stack([t[0] for t in sizes], (b, b), np.uint32), stack([t[1] for t in sizes], (b, b), np.uint32),
-                   stack([t[0] for t in pairs], (n_cols, n_cols), np.uint64), stack([t[1] for t in pairs], (n_cols, n_cols), np.uint64))
+        return cls(members, *_size_and_pair_tables(sizes, pairs, _lib.PLACE_BINS, n_cols))
 
     def sar(self):
         """float64 [n_cols, n_cols]: the secondary attack rate pooled over the members -- the sum of secondary divided by the
         sum of at_risk --, NaN where nobody was at risk."""
-        at, sec = self.at_risk.sum(axis=0).astype(np.float64), self.secondary.sum(axis=0).astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(at > 0, sec / at, np.nan)
+        return _rate(self.secondary.sum(axis=0), self.at_risk.sum(axis=0))
 
     def attack_rate_by_size(self):
         """float64 [32]: per size bin, the share of the places (pooled over the members) that had at least one case, NaN for a
         bin without a place."""
         tab = self.final_size.sum(axis=0).astype(np.float64)
         places = tab.sum(axis=1)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(places > 0, (places - tab[:, 0]) / places, np.nan)
+        return _rate(places - tab[:, 0], places)
 
     def dump(self, directory):
         """ensemble_places.npz: final_size, introduced, at_risk, secondary, the pooled sar and attack_rate_by_size."""
@@ -368,16 +363,12 @@ class ContactResult:
     @classmethod
     def gathered(cls, members, tables, n_cols=1):
         """From every member's Simulator.contact_hours() dict."""
-        def stack(key):
-            return np.stack([t[key] for t in tables]).astype(np.uint64) if tables else np.zeros((0, _lib.N_SETTINGS, n_cols, n_cols), np.uint64)
-        return cls(members, stack("hours"), stack("transmissions"))
+        return cls(members, *(_stack([t[k] for t in tables], (_lib.N_SETTINGS, n_cols, n_cols), np.uint64) for k in ("hours", "transmissions")))
 
     def rate(self):
         """float64 [4, n_cols, n_cols]: transmissions per contact-hour pooled over the members -- the sum of transmissions
         divided by the sum of hours --, NaN where there was no contact-hour."""
-        h, t = self.hours.sum(axis=0).astype(np.float64), self.transmissions.sum(axis=0).astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(h > 0, t / h, np.nan)
+        return _rate(self.transmissions.sum(axis=0), self.hours.sum(axis=0))
 
     def dump(self, directory):
         """ensemble_contacts.npz: hours, transmissions and the pooled rate."""
@@ -400,10 +391,8 @@ class FlowResult:
     @classmethod
     def gathered(cls, members, imports, invasions, n_areas):
         """From every member's Simulator.area_imports() and area_invasion() dicts."""
-        def stack(rows):
-            return np.stack(rows).astype(np.uint32) if rows else np.zeros((0, n_areas), np.uint32)
-        return cls(members, *(stack([t[k] for t in imports]) for k in ("local", "imported", "exported")),
-                   *(stack([t[k] for t in invasions]) for k in ("step", "source_area")))
+        return cls(members, *(_stack([t[k] for t in imports], (n_areas,), np.uint32) for k in ("local", "imported", "exported")),
+                   *(_stack([t[k] for t in invasions], (n_areas,), np.uint32) for k in ("step", "source_area")))
 
     def imported_share(self):
         """float64 [n_areas]: of the area's infected residents whose infector is known, the share infected by a resident of
@@ -411,8 +400,7 @@ class FlowResult:
         are no cases."""
         imp = self.imported.sum(axis=0, dtype=np.uint64).astype(np.float64)
         tot = imp + self.local.sum(axis=0, dtype=np.uint64).astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(tot > 0, imp / tot, np.nan)
+        return _rate(imp, tot)
 
     def dump(self, directory):
         """ensemble_flows.npz: local, imported, exported, step, source_area and the pooled imported_share."""
@@ -438,7 +426,7 @@ class EventResult:
     @classmethod
     def gathered(cls, members, sizes, tops, top):
         """From every member's Simulator.event_sizes() table and Simulator.transmission_events(order="size", limit=top) dict."""
-        table = np.stack(sizes).astype(np.uint32) if sizes else np.zeros((0, _lib.N_SETTINGS, _lib.EVENT_BINS), np.uint32)
+        table = _stack(sizes, (_lib.N_SETTINGS, _lib.EVENT_BINS), np.uint32)
         rows = {k: np.full((len(tops), int(top)), _lib.NEVER, np.uint32) for k in cls.KEYS}
         for i, t in enumerate(tops):
             for k in cls.KEYS:
@@ -451,8 +439,7 @@ class EventResult:
         b = np.arange(_lib.EVENT_BINS, dtype=np.float64)
         weight = self.sizes.astype(np.float64) * b
         tot, big = weight.sum(axis=2), weight[:, :, min(int(min_size), _lib.EVENT_BINS):].sum(axis=2)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(tot > 0, big / tot, np.nan)
+        return _rate(big, tot)
 
     def dump(self, directory):
         """ensemble_events.npz: sizes and the five [members, top] arrays of the largest events."""
@@ -481,12 +468,11 @@ class CompareResult:
     @classmethod
     def gathered(cls, members, tables, records_baseline, records_policy, n_cols, n_steps, summary=None, where="all", area_codes=None):
         """From every member's Simulator.compare() dict and the records of its two arms."""
-        k = len(tables)
-        counts = np.stack([t["counts"] for t in tables]) if k else np.zeros((0, n_cols, _lib.CMP_N), np.uint64)
-        delay = np.stack([t["delay"] for t in tables]) if k else np.zeros((0, n_cols), np.int64)
+        counts = _stack([t["counts"] for t in tables], (n_cols, _lib.CMP_N), np.uint64)
+        delay = _stack([t["delay"] for t in tables], (n_cols,), np.int64)
         div = [-1 if t["first_divergence"] is None else t["first_divergence"] for t in tables]
-        stack = lambda rows: np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
-        return cls(members, counts, delay, div, stack(records_baseline), stack(records_policy), summary, where, area_codes)
+        return cls(members, counts, delay, div, _stack(records_baseline, (n_steps,), RECORD_DTYPE), _stack(records_policy, (n_steps,), RECORD_DTYPE),
+                   summary, where, area_codes)
 
     def averted(self):
         """int64 [members, n_cols]: the cases the policy averted net of those it added, AVERTED - ADDED."""
@@ -549,8 +535,7 @@ class Ensemble:
         if burden is not None:
             self.simulator.set_burden(burden)
         self.area_codes = area_codes
-        self.base = _lib.Params()
-        C.memmove(C.byref(self.base), C.byref(self.simulator.params), C.sizeof(_lib.Params))
+        self.base = _lib.with_overrides(self.simulator.params, {})
         self._own_seeds = True            # the seeds in force are the uploaded population's
 
     def _area_kind(self, who, area, n_steps, stop_when_done=False, n_members=None):
@@ -710,96 +695,70 @@ class Ensemble:
         sim.restart(self.base, seeds=seeds, **over)
         self._own_seeds = "index_cases" not in m
 
+    def _gather(self, members, n_steps, *calls):
+        """What outbreaks() .. events() share: every member (as for run()) is restarted and run for n_steps steps, and what each
+        of `calls` returns for the simulator then is kept.  Returns (members, one list per call)."""
+        members = self._members(members)
+        out = [[] for _ in calls]
+        for m in members:
+            self._restart_member(m)
+            self.simulator.run(n_steps)
+            for rows, call in zip(out, calls):
+                rows.append(call(self.simulator))
+        return (members, *out)
+
+    def _group_cols(self, where):
+        """The columns of the pair tables: the groups given to Ensemble(...) for where="group", else one."""
+        return max(1, self.simulator._n_groups) if where in ("group", _lib.BY_GROUP) else 1
+
     def outbreaks(self, members, n_steps, ages=False):
         """Which introduction took off: every member (as for run()) is run for n_steps steps and its outbreak table gathered
         (Simulator.outbreaks: size, depth and last step per index case) and, with ages=True, its infectious-age profile
         (Simulator.transmission_ages).  Returns an OutbreakResult."""
-        sim = self.simulator
-        members = self._members(members)
-        tables, profiles = [], []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            tables.append(sim.outbreaks())
-            if ages:
-                profiles.append(sim.transmission_ages())
-        return OutbreakResult.gathered(members, tables, profiles if ages else None)
+        calls = (lambda sim: sim.outbreaks(),) + ((lambda sim: sim.transmission_ages(),) if ages else ())
+        members, tables, *profiles = self._gather(members, n_steps, *calls)
+        return OutbreakResult.gathered(members, tables, profiles[0] if ages else None)
 
     def households(self, members, n_steps, where="all", first_step=0, last_step=None):
         """Household outbreaks over an ensemble: every member (as for run()) is run for n_steps steps and its final-size tables
         (Simulator.household_final_sizes) and household pair tables (Simulator.household_sar(where, first_step, last_step),
         complete cohorts only) gathered.  where="group" counts by the groups given to Ensemble(...).  Returns a HouseholdResult."""
-        sim = self.simulator
-        members = self._members(members)
-        sizes, pairs = [], []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            sizes.append(sim.household_final_sizes())
-            pairs.append(sim.household_sar(where, first_step, last_step))
-        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
-        return HouseholdResult.gathered(members, sizes, pairs, n_cols)
+        got = self._gather(members, n_steps, lambda sim: sim.household_final_sizes(), lambda sim: sim.household_sar(where, first_step, last_step))
+        return HouseholdResult.gathered(*got, self._group_cols(where))
 
     def places(self, members, n_steps, kind="work", where="all", first_step=0, last_step=None):
         """Work place or school outbreaks over an ensemble: every member (as for run()) is run for n_steps steps and its size
         tables (Simulator.place_sizes(kind)) and, for kind "work" or "room", its pair tables (Simulator.place_sar(kind, where,
         first_step, last_step), complete cohorts only) gathered; kind "school" has no pairs, its two pair tables stay 0.
         where="group" counts by the groups given to Ensemble(...).  Returns a PlaceResult."""
-        sim = self.simulator
-        members = self._members(members)
-        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
-        sizes, pairs = [], []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            sizes.append(sim.place_sizes(kind))
-            if kind in ("school", _lib.PLACE_SCHOOL):
-                pairs.append((np.zeros((n_cols, n_cols), np.uint64),) * 2)
-            else:
-                pairs.append(sim.place_sar(kind, where, first_step, last_step))
-        return PlaceResult.gathered(members, sizes, pairs, n_cols)
+        n_cols = self._group_cols(where)
+        if kind in ("school", _lib.PLACE_SCHOOL):
+            pairs = lambda sim: (np.zeros((n_cols, n_cols), np.uint64),) * 2
+        else:
+            pairs = lambda sim: sim.place_sar(kind, where, first_step, last_step)
+        return PlaceResult.gathered(*self._gather(members, n_steps, lambda sim: sim.place_sizes(kind), pairs), n_cols)
 
     def contacts(self, members, n_steps, where="all", settings=None, first_step=1, last_step=None):
         """Contact-hours at risk over an ensemble: every member (as for run()) is run for n_steps steps and its two tables
         (Simulator.contact_hours(where, settings, first_step, last_step)) gathered.  where="group" counts by the groups given to
         Ensemble(...).  Returns a ContactResult."""
-        sim = self.simulator
-        members = self._members(members)
-        tables = []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            tables.append(sim.contact_hours(where, settings, first_step, last_step))
-        n_cols = max(1, sim._n_groups) if where in ("group", _lib.BY_GROUP) else 1
-        return ContactResult.gathered(members, tables, n_cols)
+        got = self._gather(members, n_steps, lambda sim: sim.contact_hours(where, settings, first_step, last_step))
+        return ContactResult.gathered(*got, self._group_cols(where))
 
     def flows(self, members, n_steps, settings=None, first_step=1, last_step=None):
         """How the epidemic travels, over an ensemble: every member (as for run()) is run for n_steps steps and its imports table
         (Simulator.area_imports(settings, first_step, last_step)) and invasion tree (Simulator.area_invasion) gathered.  Returns a
         FlowResult."""
-        sim = self.simulator
-        members = self._members(members)
-        imports, invasions = [], []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            imports.append(sim.area_imports(settings, first_step, last_step))
-            invasions.append(sim.area_invasion())
-        return FlowResult.gathered(members, imports, invasions, sim.population.n_areas)
+        got = self._gather(members, n_steps, lambda sim: sim.area_imports(settings, first_step, last_step), lambda sim: sim.area_invasion())
+        return FlowResult.gathered(*got, self.simulator.population.n_areas)
 
     def events(self, members, n_steps, settings=None, first_step=1, last_step=None, top=16):
         """Superspreading events over an ensemble: every member (as for run()) is run for n_steps steps and its event-size table
         (Simulator.event_sizes(settings, first_step, last_step)) and its `top` largest events
         (Simulator.transmission_events(..., order="size", limit=top)) gathered.  Returns an EventResult."""
-        sim = self.simulator
-        members = self._members(members)
-        sizes, tops = [], []
-        for m in members:
-            self._restart_member(m)
-            sim.run(n_steps)
-            sizes.append(sim.event_sizes(settings, first_step, last_step))
-            tops.append(sim.transmission_events(settings, first_step, last_step, order="size", limit=top))
-        return EventResult.gathered(members, sizes, tops, top)
+        got = self._gather(members, n_steps, lambda sim: sim.event_sizes(settings, first_step, last_step),
+                           lambda sim: sim.transmission_events(settings, first_step, last_step, order="size", limit=top))
+        return EventResult.gathered(*got, top)
 
     def run(self, members, n_steps, stop_when_done=False, area=None, settings=None, reproduction=None):
         """members: iterable of override dicts (Ensemble.seeds, Ensemble.index_cases); beside fields of esim_params a dict may
@@ -850,7 +809,7 @@ class Ensemble:
                 by_cohort.append(self._reproduction_of_member(r_spec))
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
-        records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
+        records = _stack(rows, (n_steps,), RECORD_DTYPE)
         summary = self._keep_summary(self._summary(kind, area), kind, len(members))
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
@@ -890,7 +849,7 @@ class Ensemble:
                 by_cohort.append(self._reproduction_of_member(r_spec))
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
-        records = np.stack(rows) if rows else np.zeros((0, n_steps), RECORD_DTYPE)
+        records = _stack(rows, (n_steps,), RECORD_DTYPE)
         summary = self._keep_summary(self._summary(kind, area), kind, len(members))
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
