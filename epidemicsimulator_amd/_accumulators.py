@@ -1,8 +1,8 @@
 """The accumulators of Simulator over the members of an ensemble, kept on the device (esim_ensemble_*): the begin of every
-kind -- census, arrival, series, settings, reproduction, paired, peaks, burden peaks --, the fold of the state as it stands,
+kind -- census, arrival, series, settings, reproduction, paired, peaks, burden peaks, burden series, burden paired --, the fold of the state as it stands,
 the readers, and the members kept beside the accumulators for the quantile maps.  _Accumulators only holds methods: the state
-and the helpers _n_cols and _last are Simulator's (simulator.py), _setting_mask, _compare_place, _compare_rows and _curve_args
-the outputs' (_outputs.py) whose rows a member contributes.
+and the helpers _n_cols and _last are Simulator's (simulator.py), _setting_mask, _compare_place, _compare_rows, _curve_args and
+_burden_what the outputs' (_outputs.py) whose rows a member contributes.
 
 A begin remembers the rows and columns it asked for (_begun): the readers and the calls on the members kept size their
 buffers by them.  Its n_rows=None and last_step=None mean up to the last step of the run (params.max_steps).  The library
@@ -188,6 +188,29 @@ class _Accumulators:
         place = place_code(where, "all home group current")
         _lib.check(self.lib.esim_ensemble_begin_burden_peaks(self._ctx, place, int(first_step), self._last(last_step, run=False), int(threshold), int(min_peak)), self._ctx)
         self._begun(1, place)
+
+    # -- over rows made from a member's list of admitted cases (esim_ensemble_begin_burden_series, esim_ensemble_begin_burden_paired) -------
+    def ensemble_begin_burden_series(self, where="all", what="occupancy", first_step=1, n_rows=None, stride=24, min_count=1):
+        """Accumulators over the rows of the hospital burden (esim_ensemble_begin_burden_series): a member contributes, cell for
+        cell, the rows burden_series(what, where, first_step, n_rows, stride) would return for it; ensemble_fold adds
+        hit += (x >= min_count) -- beds against a capacity --, sum += x, sumsq += x * x per cell on the device.  n_rows=None: up
+        to the last step of the run (params.max_steps).  ensemble_read_series reads them."""
+        place = self._compare_place("ensemble_begin_burden_series", where)
+        n_rows = self._begin_rows(first_step, n_rows, stride, 1)
+        _lib.check(self.lib.esim_ensemble_begin_burden_series(self._ctx, place, self._burden_what(what), int(first_step), n_rows, int(stride), int(min_count)), self._ctx)
+        self._begun(n_rows, place)
+
+    def ensemble_begin_burden_paired(self, where="all", what="occupancy", first_step=1, n_rows=None, stride=24, cumulative=False, min_baseline=1, min_averted=1):
+        """The paired kind over the hospital burden (esim_ensemble_begin_burden_paired): a member contributes the (baseline,
+        current) rows burden_compare_series(what, where, first_step, n_rows, stride, cumulative) would return for it, folded as
+        ensemble_begin_paired folds the cases.  ensemble_read_paired reads them; the members kept are baseline - current."""
+        place = self._compare_place("ensemble_begin_burden_paired", where)
+        n_rows = self._begin_rows(first_step, n_rows, stride, 1)
+        if int(min_averted) < 1 or int(min_baseline) < 0:
+            raise ValueError("ensemble_begin_burden_paired: min_averted must be >= 1 and min_baseline >= 0")
+        _lib.check(self.lib.esim_ensemble_begin_burden_paired(self._ctx, place, self._burden_what(what), int(first_step), n_rows, int(stride), int(bool(cumulative)),
+                                                              int(min_baseline), int(min_averted)), self._ctx)
+        self._begun(n_rows, place)
 
     def ensemble_read_peaks(self):
         """{"members": int, "defined", "hit": uint32 [n_cols], "sum_peak", "sumsq_peak", "sum_step", "sumsq_step", "sum_duration",

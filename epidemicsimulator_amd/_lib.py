@@ -100,6 +100,8 @@ SYMBOLS = [
     "esim_read_records", "esim_synchronize",
     "esim_download_state", "esim_download_exposure_log", "esim_area_census", "esim_area_arrival", "esim_area_series", "esim_area_status_series", "esim_set_groups", "esim_group_census", "esim_group_series", "esim_exposure_settings", "esim_setting_series", "esim_building_exposures", "esim_transmission_tree", "esim_offspring", "esim_reproduction_series", "esim_mixing_matrix", "esim_transmission_chains", "esim_outbreaks", "esim_transmission_ages", "esim_household_outbreaks", "esim_household_final_sizes", "esim_household_sar", "esim_place_outbreaks", "esim_place_sizes", "esim_place_sar", "esim_contact_hours", "esim_area_flows", "esim_area_imports", "esim_area_invasion", "esim_lineage_areas", "esim_pair_stats", "esim_transmission_events", "esim_routes", "esim_ensemble_begin", "esim_ensemble_begin_arrival", "esim_ensemble_fold", "esim_ensemble_read", "esim_ensemble_begin_series", "esim_ensemble_read_series", "esim_ensemble_begin_settings", "esim_ensemble_begin_reproduction", "esim_ensemble_read_reproduction", "esim_checkpoint_size", "esim_checkpoint_save", "esim_checkpoint_restore", "esim_snapshot", "esim_rollback", "esim_snapshot_info", "esim_snapshot_drop", "esim_baseline_keep", "esim_baseline_info", "esim_baseline_drop", "esim_compare", "esim_compare_series", "esim_ensemble_begin_paired", "esim_ensemble_read_paired", "esim_curve_summary", "esim_ensemble_begin_peaks", "esim_ensemble_read_peaks",
     "esim_burden_set", "esim_burden_drop", "esim_burden_get", "esim_burden_outcomes", "esim_burden_series", "esim_burden_summary", "esim_ensemble_begin_burden_peaks",
+    "esim_burden_baseline_keep", "esim_burden_baseline_info", "esim_burden_baseline_drop", "esim_burden_baseline_read", "esim_burden_compare", "esim_burden_compare_series",
+    "esim_ensemble_begin_burden_series", "esim_ensemble_begin_burden_paired",
     "esim_ensemble_keep_members", "esim_ensemble_members_info", "esim_ensemble_read_members", "esim_ensemble_quantiles", "esim_ensemble_exceedance", "esim_enable_phase_timing", "esim_phase_timings",
     "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters", "esim_debug_launches",
     "esim_last_error", "esim_destroy",
@@ -217,6 +219,14 @@ def load():
         "esim_burden_series": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),
         "esim_burden_summary": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p, _u32p, C.POINTER(C.c_uint64), _u32p, _u32p]),
         "esim_ensemble_begin_burden_peaks": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "esim_burden_baseline_keep": (C.c_int, [vp]),
+        "esim_burden_baseline_info": (C.c_int, [vp, _u32p, _u32p, _u32p, C.POINTER(Params)]),
+        "esim_burden_baseline_drop": (C.c_int, [vp]),
+        "esim_burden_baseline_read": (C.c_int, [vp, _u32p, _u32p, _u32p, _u8p, C.c_uint32, _u32p]),
+        "esim_burden_compare": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u32p, _u32p, _u32p, _u32p]),
+        "esim_burden_compare_series": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p]),
+        "esim_ensemble_begin_burden_series": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "esim_ensemble_begin_burden_paired": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32]),
         "esim_ensemble_keep_members": (C.c_int, [vp, C.c_uint32, C.c_int]),
         "esim_ensemble_members_info": (C.c_int, [vp, _u32p, _u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "esim_ensemble_read_members": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u32p]),

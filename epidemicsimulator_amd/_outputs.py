@@ -1,6 +1,6 @@
 """The output families of Simulator, computed on the device from the state and the exposure log of the run as it stands:
 area, group, settings, tree, chains, households, places, contacts, flows and events, the paired comparison with a kept
-baseline, the curve summaries and the hospital burden.  _Outputs only holds methods: the state they use (lib, _ctx, _steps,
+baseline, the curve summaries, the hospital burden and its comparison with a kept burden baseline.  _Outputs only holds methods: the state they use (lib, _ctx, _steps,
 _n_groups, population, params) and the helpers _n_cols, _last and _complete_last are Simulator's (simulator.py); the
 marshalling rules are _marshal's.
 
@@ -33,13 +33,13 @@ class _Outputs:
         _lib.check(self.lib.esim_area_arrival(self._ctx, place, ptr(out)), self._ctx)
         return out
 
-    def _series(self, call, codes, n_cols, first_step, n_rows, stride, lowest=1, outputs=1):
+    def _series(self, call, codes, n_cols, first_step, n_rows, stride, lowest=1, outputs=1, flags=()):
         """One of the series calls: `outputs` arrays uint32 [n_rows, n_cols] (one: the array itself); n_rows=None: up to the
-        last step run, from step `lowest` at the earliest."""
+        last step run, from step `lowest` at the earliest.  flags: what the call takes between the stride and its outputs."""
         if n_rows is None:
             n_rows = default_rows(first_step, stride, self._steps, lowest)
         out = [np.zeros((max(0, int(n_rows)), n_cols), np.uint32) for _ in range(outputs)]
-        _lib.check(call(self._ctx, *(int(c) for c in codes), int(first_step), int(n_rows), int(stride), *(ptr(a) for a in out)), self._ctx)
+        _lib.check(call(self._ctx, *(int(c) for c in codes), int(first_step), int(n_rows), int(stride), *flags, *(ptr(a) for a in out)), self._ctx)
         return out[0] if outputs == 1 else tuple(out)
 
     def area_series(self, what, first_step=1, n_rows=None, stride=1):
@@ -525,3 +525,64 @@ class _Outputs:
         place = place_code(where, "all home group current")
         return self._by_key(self.lib.esim_burden_summary, (place, int(first_step), self._last(last_step), int(threshold)), self.BURDEN_KEYS,
                             self._n_cols(place), u64=("bed_steps",))
+
+    # -- hospital burden across runs: the admitted cases kept as a list on the device (esim_burden_baseline_*, esim_burden_compare*) -------
+    @staticmethod
+    def _burden_what(what):
+        return int({k: i for i, k in enumerate(_lib.BURDEN_NAMES)}.get(what, what))
+
+    def keep_burden_baseline(self):
+        """Keeps the admitted cases of the run as it stands as a list on the device (esim_burden_baseline_keep): the baseline
+        that burden_compare() and burden_compare_series() set a later run against.  It survives reset, restart, snapshot and
+        rollback; set_burden, drop_burden and an upload drop it."""
+        _lib.check(self.lib.esim_burden_baseline_keep(self._ctx), self._ctx)
+
+    def burden_baseline_info(self):
+        """{"steps", "n_admitted", "n_died", "params"} of the burden baseline kept (esim_burden_baseline_info)."""
+        n, p = [C.c_uint32(0) for _ in range(3)], _lib.Params()
+        _lib.check(self.lib.esim_burden_baseline_info(self._ctx, *(C.byref(x) for x in n), C.byref(p)), self._ctx)
+        return {"steps": int(n[0].value), "n_admitted": int(n[1].value), "n_died": int(n[2].value), "params": p}
+
+    def drop_burden_baseline(self):
+        """Forgets the burden baseline kept (esim_burden_baseline_drop)."""
+        _lib.check(self.lib.esim_burden_baseline_drop(self._ctx), self._ctx)
+
+    def burden_baseline_cases(self):
+        """The admitted cases of the burden baseline (esim_burden_baseline_read), a dict of [n_admitted] arrays sorted by
+        citizen: citizen, admit_step, end_step (uint32) and died (bool).  The steps may lie beyond the baseline's run."""
+        keys = ("citizen", "admit_step", "end_step", "died")
+        code, out = sized(lambda ptrs, cap, n: self.lib.esim_burden_baseline_read(self._ctx, *ptrs, cap, n), lambda n: zeros(keys, n, u8=("died",)))
+        _lib.check(code, self._ctx)
+        order = np.argsort(out["citizen"], kind="stable")
+        return {k: (out[k][order].astype(bool) if k == "died" else out[k][order]) for k in keys}
+
+    def _burden_compare_last(self):
+        """The last step both runs have (without a baseline: of this run; the library refuses then)."""
+        steps = C.c_uint32(0)
+        if self.lib.esim_burden_baseline_info(self._ctx, C.byref(steps), None, None, None) != _lib.OK:
+            return self._steps
+        return min(self._steps, int(steps.value))
+
+    def burden_compare(self, where="all", first_step=1, last_step=None):
+        """The run as it stands against the burden baseline kept, over the steps first_step .. last_step (None: the last step
+        of the shorter run), a dict of [n_cols] arrays (esim_burden_compare): bed_steps_baseline, bed_steps_current (uint64),
+        admissions_baseline, admissions_current, deaths_baseline, deaths_current (uint32) -- the totals burden_summary gave at
+        the keep and gives now -- and bed_steps_averted, admissions_averted, deaths_averted (int64): baseline - current."""
+        place = self._compare_place("burden_compare", where)
+        last = self._burden_compare_last() if last_step is None else int(last_step)
+        keys = ("bed_steps_baseline", "bed_steps_current", "admissions_baseline", "admissions_current", "deaths_baseline", "deaths_current")
+        out = self._by_key(self.lib.esim_burden_compare, (place, int(first_step), last), keys, self._n_cols(place), u64=keys[:2])
+        for k in ("bed_steps", "admissions", "deaths"):
+            out[k + "_averted"] = out[k + "_baseline"].astype(np.int64) - out[k + "_current"].astype(np.int64)
+        return out
+
+    def burden_compare_series(self, what="occupancy", where="all", first_step=1, n_rows=None, stride=24, cumulative=False):
+        """(baseline, current), uint32 [n_rows, n_cols] each (esim_burden_compare_series): the rows of burden_series(what, where,
+        first_step, n_rows, stride) of the burden baseline kept and of the run as it stands; with cumulative=True (admissions
+        and deaths only) the events from first_step up to the row's last step.  n_rows=None: up to the last step of the
+        shorter run."""
+        place = self._compare_place("burden_compare_series", where)
+        if n_rows is None:
+            n_rows = default_rows(first_step, stride, self._burden_compare_last(), 1)
+        return self._series(self.lib.esim_burden_compare_series, (place, self._burden_what(what)), self._n_cols(place), first_step, n_rows, stride,
+                            outputs=2, flags=(int(bool(cumulative)),))

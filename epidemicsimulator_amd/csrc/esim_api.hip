@@ -32,6 +32,7 @@
 #include "esim_host_flows.h"
 #include "esim_host_curves.h"
 #include "esim_host_burden.h"
+#include "esim_host_beds.h"
 #include "esim_host_events.h"
 #include "esim_host_ckpt.h"
 #include "esim_host_snapshot.h"

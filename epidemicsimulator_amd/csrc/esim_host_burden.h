@@ -14,6 +14,7 @@ void burden_forget(esim_ctx_impl *c)
     if (c->burden.tab) (void)hipStreamSynchronize(c->stream);     // (a fold on the stream may still be reading them)
     dev_free(c, c->burden.tab);
     c->burden = BurdenState();
+    c->beds.held = false;                                         // (a kept burden baseline was drawn under these tables; its list stays for the next keep)
 }
 
 // What every call that computes refuses alike, in front of its own argument checks.

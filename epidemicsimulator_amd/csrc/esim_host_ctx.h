@@ -102,7 +102,9 @@ struct Ensemble {
         unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
         uint32_t last = 0, threshold = 0;         // ROWS_PEAKS: the window [first, last], the threshold of the duration (mask: the statuses, min: min_peak)
         unsigned long long *sum_d = nullptr, *sumsq_d = nullptr;   // ... sums of the duration and of its square
-        bool burden = false;                      // ... the curve a fold summarises: bed occupancy (esim_ensemble_begin_burden_peaks) instead of a status
+        bool burden = false;                      // ... the curve a fold summarises: bed occupancy (esim_ensemble_begin_burden_peaks) instead of a status;
+                                                  // under ROWS_SETTINGS / ROWS_PAIRED: a fold makes the rows (what, cumulative) from lists of admitted cases
+                                                  // (esim_ensemble_begin_burden_series / _burden_paired, esim_host_beds.h)
         uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
     } rows;
     bool series = false;
@@ -141,6 +143,20 @@ struct Baseline {
     uint32_t *plane = nullptr;
     bool held = false;
     uint32_t steps = 0, n_cases = 0;
+    esim_params P;
+};
+
+// esim_burden_baseline_keep: the admitted cases of a finished run as a list on the device -- three planes of `cap`
+// entries in one allocation (citizen, admit_step, end_step | died << 31) and the two counts --, with the steps run, the entries,
+// the deaths among them and the parameters then in force (the seed among them).  Allocated at the first keep, grown when a
+// later run needs more; held == false: none is kept.  Independent of Baseline.
+struct BedsBaseline {
+    uint32_t *list = nullptr, *count = nullptr;
+    size_t cap = 0;
+    uint32_t *tmp = nullptr, *tmp_count = nullptr;      // the scratch list of the run as it stands (esim_burden_compare, the folds): kept between calls
+    size_t tmp_cap = 0;
+    bool held = false;
+    uint32_t steps = 0, n = 0, n_died = 0;
     esim_params P;
 };
 
@@ -245,6 +261,7 @@ struct esim_ctx_impl {
     Groups grp;
     Snapshot snap;
     Baseline base;
+    BedsBaseline beds;
     BurdenState burden;
     Seam seam;
     DrawSeam draw_seam;               // of the history the context stands on

@@ -40,6 +40,7 @@ int ensrows_begin(esim_ctx_impl *c, const std::string &who, int kind, uint32_t n
     }
     Ensemble::Rows &r = c->ens.rows;
     r.kind = kind; r.n_rows = n_rows; r.n_cols = cols; r.two = ratio;
+    r.burden = false;                                              // (a Rows reused: the burden kinds of esim_host_beds.h set it behind this call)
     HIP_TRY(c, hipMemsetAsync(r.hit, 0, sizeof(uint32_t) * cells, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.sum, 0, sizeof(unsigned long long) * cells, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.sumsq, 0, sizeof(unsigned long long) * cells, c->stream));

@@ -333,6 +333,7 @@ int fold_series(esim_ctx_impl *c)
 int fold_transmission(esim_ctx_impl *c);   // (esim_host_ensrows.h: the settings and the reproduction kind)
 int fold_paired(esim_ctx_impl *c);         // (esim_host_compare.h: the paired kind)
 int fold_peaks(esim_ctx_impl *c);          // (esim_host_curves.h: the peaks kind)
+int fold_beds(esim_ctx_impl *c);           // (esim_host_beds.h: the burden-series and the burden-paired kind, where Rows::burden says so)
 void burden_forget(esim_ctx_impl *c);      // (esim_host_burden.h: the severity tables dropped)
 }  // namespace
 
@@ -394,6 +395,7 @@ extern "C" int esim_ensemble_fold(esim_ctx *ctx)
         return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
     if (int rc = members_full(c)) return rc;
     if (c->ens.series && c->ens.rows.kind == Ensemble::ROWS_PEAKS) return fold_peaks(c);
+    if (c->ens.series && c->ens.rows.burden) return fold_beds(c);
     if (c->ens.series) return c->ens.rows.kind == Ensemble::ROWS_SERIES ? fold_series(c) : c->ens.rows.kind == Ensemble::ROWS_PAIRED ? fold_paired(c) : fold_transmission(c);
     HIP_TRY(c, hipSetDevice(c->P.device));
     int rc;

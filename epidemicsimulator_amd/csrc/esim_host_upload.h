@@ -155,6 +155,7 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     c->grp = Groups();                                             // (the labels belong to the population they were set for)
     c->snap = Snapshot();                                          // (so does a snapshot: its buffers went with the rest)
     c->base = Baseline();                                          // (and a kept baseline)
+    c->beds = BedsBaseline();                                      // (and a kept burden baseline)
     c->burden = BurdenState();                                     // (and the severity tables: their groups are this population's labels)
     Dev &d = c->d;
     std::memset(&d, 0, sizeof d);

@@ -45,5 +45,6 @@
 #include "esim_kernels_compare.h"
 #include "esim_kernels_curves.h"
 #include "esim_kernels_burden.h"
+#include "esim_kernels_beds.h"
 #include "esim_kernels_members.h"
 #include "esim_kernels_snapshot.h"

@@ -197,7 +197,8 @@ class EnsembleResult:
         summary of area kind "settings" goes to ensemble_area_settings.npz the same way, that of kind "reproduction" to
         ensemble_area_reproduction.npz: steps, defined, hit, cases_mean, offspring_mean, r, p_r, r_se, members, and codes; that of
         kind "peaks" to ensemble_area_peaks.npz: the arrays of peaks_summary, members, and codes (kind "burden_peaks": the same of
-        the bed occupancy, to ensemble_area_burden.npz).  The members' exposures by setting, where they
+        the bed occupancy, to ensemble_area_burden.npz); that of kind "burden_series" to ensemble_area_burden_series.npz, as a
+        series summary.  The members' exposures by setting, where they
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
         ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names.  The quantile maps, where the area dict
         asked for them, go to ensemble_area_quantiles.npz: probs, quantiles, thresholds, exceed, steps for a summary over rows, and
@@ -224,7 +225,8 @@ class EnsembleResult:
                 arrays["members"] = np.asarray(a["members"], np.uint32)
             if self.area_codes is not None:
                 arrays["codes"] = np.asarray(self.area_codes)
-            name = "ensemble_area_reproduction.npz" if ratio else "ensemble_area_settings.npz" if self.area_kind == "settings" else "ensemble_area_series.npz"
+            name = ("ensemble_area_reproduction.npz" if ratio else "ensemble_area_settings.npz" if self.area_kind == "settings" else
+                    "ensemble_area_burden_series.npz" if self.area_kind == "burden_series" else "ensemble_area_series.npz")
             np.savez(os.path.join(directory, name), **arrays)
         elif self.area is not None:
             a = self.area
@@ -497,6 +499,64 @@ class CompareResult:
             np.savez(os.path.join(directory, "ensemble_area_quantiles.npz"), **extra)
 
 
+class BurdenCompareResult:
+    """What Ensemble.compare_burden gathers: every member's hospital burden under the policy against its own baseline run."""
+
+    KEYS = CompareResult.KEYS
+    TOTALS = ("bed_steps", "admissions", "deaths")
+
+    def __init__(self, members, totals, records_baseline, records_policy, summary=None, where="all", what="occupancy", area_codes=None):
+        self.members = list(members)      # the overrides of every member
+        self.totals = totals              # {"bed_steps_baseline", "bed_steps_current", "admissions_baseline", ...}: [members, n_cols] each
+        self.records_baseline = records_baseline                     # structured [members, n_steps]
+        self.records_policy = records_policy
+        self.summary = summary            # paired_summary(...) of the rows of `what` where rows were asked for, else None
+        self.where, self.what = where, what
+        self.area_codes = area_codes
+        self.quantile_probs = None        # float64 [n_q], and
+        self.averted_quantiles = None     # [n_q, n_rows, n_cols]: quantiles over the members of baseline - policy per cell, where compare_burden(quantiles=...) asked
+
+    @classmethod
+    def gathered(cls, members, tables, records_baseline, records_policy, n_cols, n_steps, summary=None, where="all", what="occupancy", area_codes=None):
+        """From every member's Simulator.burden_compare() dict and the records of its two arms."""
+        totals = {}
+        for k in cls.TOTALS:
+            for arm in ("_baseline", "_current"):
+                totals[k + arm] = _stack([t[k + arm] for t in tables], (n_cols,), np.uint64 if k == "bed_steps" else np.uint32)
+        return cls(members, totals, _stack(records_baseline, (n_steps,), RECORD_DTYPE), _stack(records_policy, (n_steps,), RECORD_DTYPE), summary, where, what, area_codes)
+
+    def _averted(self, key):
+        return self.totals[key + "_baseline"].astype(np.int64) - self.totals[key + "_current"].astype(np.int64)
+
+    def bed_days_averted(self):
+        """float64 [members, n_cols]: the bed-days the policy averted, (bed-steps of the baseline - of the policy run) / 24."""
+        return self._averted("bed_steps") / 24.0
+
+    def admissions_averted(self):
+        """int64 [members, n_cols]."""
+        return self._averted("admissions")
+
+    def deaths_averted(self):
+        """int64 [members, n_cols]."""
+        return self._averted("deaths")
+
+    def dump(self, directory):
+        """ensemble_burden_compare.npz: the six totals, bed_days_averted, admissions_averted, deaths_averted, what, and the arrays
+        of the summary (with a summary_ prefix) where rows were asked for; codes where area codes name the columns; probs and
+        quantiles where they were asked for."""
+        os.makedirs(directory, exist_ok=True)
+        arrays = dict(self.totals, bed_days_averted=self.bed_days_averted(), admissions_averted=self.admissions_averted(), deaths_averted=self.deaths_averted(),
+                      what=np.asarray(self.what))
+        if self.summary is not None:
+            arrays.update({"summary_" + k: self.summary[k] for k in self.KEYS})
+            arrays["summary_members"] = np.asarray(self.summary["members"], np.uint32)
+        if self.area_codes is not None:
+            arrays["codes"] = np.asarray(self.area_codes)
+        if self.averted_quantiles is not None:
+            arrays.update(probs=self.quantile_probs, quantiles=self.averted_quantiles)
+        np.savez(os.path.join(directory, "ensemble_burden_compare.npz"), **arrays)
+
+
 def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep")):
     """The keys of the quantile maps popped from `area` and checked before any library call: None where none is given, else
     dict(probs, method, thresholds, what).  ValueError for the reproduction kind (a ratio per cell is not kept), a probability
@@ -518,8 +578,8 @@ def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_met
     return dict(probs=probs, method=method, thresholds=[int(t) for t in (given.get("exceed") or ())], what=what)
 
 
-_KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks")
-_ROW_KINDS = ("series", "settings", "reproduction", "peaks", "burden_peaks")      # a member that stopped early has no rows behind its last step
+_KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")
+_ROW_KINDS = ("series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")      # a member that stopped early has no rows behind its last step
 
 
 class Ensemble:
@@ -528,7 +588,8 @@ class Ensemble:
     def __init__(self, population, params=None, area_codes=None, group=None, burden=None):
         """group: None, or (labels, n_groups) for Simulator.set_groups -- what run(area=dict(where="group", ...)) counts by.
         burden: None, or the tables of _lib.burden_tables for Simulator.set_burden, set once for every member -- what
-        run(area=dict(kind="burden_peaks", ...)) summarises (tables of several groups need `group` with as many)."""
+        run(area=dict(kind="burden_peaks", ...)) and run(area=dict(kind="burden_series", ...)) summarise and compare_burden()
+        compares (tables of several groups need `group` with as many)."""
         self.simulator = Simulator(population, params, area_codes=area_codes)
         if group is not None:
             self.simulator.set_groups(*group)
@@ -550,13 +611,16 @@ class Ensemble:
         area = dict(area)
         kind = area.pop("kind", "census")
         if kind not in _KINDS:
-            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction', 'peaks' or 'burden_peaks', got %r" % (who, kind))
+            raise ValueError("Ensemble.%s: area kind must be 'census', 'arrival' or 'series', or 'settings', 'reproduction', 'peaks', 'burden_peaks' or 'burden_series', got %r" % (who, kind))
         self._keep_spec = _keep_spec("Ensemble." + who, kind, area, n_members)
         if kind in _ROW_KINDS and stop_when_done:
             raise ValueError("Ensemble.%s: area kind %r cannot go with stop_when_done=True (a member that stopped early has no "
                              "rows behind its last step, and the library refuses the fold)" % (who, kind))
         if kind == "settings" and area.get("n_rows") is None:
             first, stride = int(area.get("first_step", 1)), int(area.get("stride", 1))
+            area["n_rows"] = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
+        if kind == "burden_series" and area.get("n_rows") is None:
+            first, stride = int(area.get("first_step", 1)), int(area.get("stride", 24))
             area["n_rows"] = (int(n_steps) - first) // stride + 1 if stride > 0 and 1 <= first <= int(n_steps) else 0
         if kind in ("peaks", "burden_peaks") and area.get("last_step") is None:
             area["last_step"] = int(n_steps)
@@ -581,7 +645,7 @@ class Ensemble:
         if kind is not None:
             getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
                           "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks",
-                          "burden_peaks": "ensemble_begin_burden_peaks"}[kind])(**area)
+                          "burden_peaks": "ensemble_begin_burden_peaks", "burden_series": "ensemble_begin_burden_series"}[kind])(**area)
 
     def _keep_begin(self, n_members):
         """Behind the begin: the store of the quantile maps, where the area dict asked for them."""
@@ -609,9 +673,9 @@ class Ensemble:
             return peaks_summary(sim.ensemble_read_peaks())
         if kind == "reproduction":
             return reproduction_summary(sim.ensemble_read_reproduction(), area.get("first_step", 0), area.get("stride", 24))
-        if kind in ("series", "settings"):
+        if kind in ("series", "settings", "burden_series"):
             r = sim.ensemble_read_series()
-            return series_summary(r["members"], r["hit"], r["sum"], r["sumsq"], area.get("first_step", 1), area.get("stride", 1))
+            return series_summary(r["members"], r["hit"], r["sum"], r["sumsq"], area.get("first_step", 1), area.get("stride", 24 if kind == "burden_series" else 1))
         r = sim.ensemble_read()
         return (arrival_summary if kind == "arrival" else area_summary)(r["members"], r["hit"], r["sum"], r["sumsq"])
 
@@ -777,7 +841,10 @@ class Ensemble:
         (Simulator.ensemble_begin_peaks; last_step=None: n_steps; the summary is a peaks_summary); or dict(kind="burden_peaks",
         where=..., first_step=..., last_step=..., threshold=..., min_peak=...) for the same of every member's bed occupancy
         under the tables of Ensemble(..., burden=...) (Simulator.ensemble_begin_burden_peaks: per column P(peak occupancy >=
-        min_peak) and the mean and deviation of peak, peak step and duration).  With complete=True and n_rows=None only complete
+        min_peak) and the mean and deviation of peak, peak step and duration); or dict(kind="burden_series", what=..., where=...,
+        first_step=..., n_rows=..., stride=..., min_count=...) for the rows of every member's hospital burden (Simulator.
+        ensemble_begin_burden_series: the fan chart -- per row and column hit = the members with at least min_count, beds
+        against a capacity, and mean and var; a series_summary).  With complete=True and n_rows=None only complete
         cohort rows are taken -- an incomplete cohort biases R down -- and ValueError is raised when there is none.  Neither goes
         with stop_when_done=True.
         Every kind but reproduction also takes quantiles=(0.05, 0.5, 0.95), quantile_method="nearest" or "linear", exceed=(1, 5)
@@ -872,20 +939,8 @@ class Ensemble:
         int32 for quantile_method="nearest", float64 for "linear".  Returns a CompareResult."""
         sim = self.simulator
         n_steps = int(n_steps)
-        baseline, policy = dict(baseline), dict(policy)
-        members = self._members(members)
         place = sim._compare_place("Ensemble.compare", where)
-        if "index_cases" in baseline or "index_cases" in policy:
-            raise ValueError("Ensemble.compare: the index cases belong to the member, not to an arm (the pairing needs the same ones in both)")
-        if history_steps is not None:
-            history_steps = int(history_steps)
-            if not 1 <= history_steps <= n_steps:
-                raise ValueError("Ensemble.compare: history_steps must be in 1..n_steps")
-            if any("index_cases" in m for m in members):
-                raise ValueError("Ensemble.compare: a branch cannot change the index cases of the shared history")
-            fixed = sorted(k for k in self._FIXED_BY_HISTORY if k in baseline or k in policy)
-            if fixed:
-                raise ValueError("Ensemble.compare: %s cannot change behind a shared history" % ", ".join(fixed))
+        baseline, policy, members, history_steps = self._paired_check("Ensemble.compare", baseline, policy, members, n_steps, history_steps)
         keep = _keep_spec("Ensemble.compare", "paired", dict(quantiles=quantiles, quantile_method=quantile_method), len(members)) if quantiles is not None else None
         if keep is not None and rows is None:
             raise ValueError("Ensemble.compare: quantiles are taken of the paired rows: give rows= too")
@@ -899,6 +954,38 @@ class Ensemble:
             sim.ensemble_begin_paired(where, **rows)
             if keep is not None and members:
                 sim.ensemble_keep_members(len(members))
+        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, sim.keep_baseline, lambda: sim.compare(where, 0, n_steps), rows is not None)
+        summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
+        codes = self.area_codes if place == _lib.AREA_HOME else None
+        out = CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
+        if keep is not None and members and keep["probs"]:
+            out.quantile_probs = np.asarray(keep["probs"], np.float64)
+            out.averted_quantiles = sim.ensemble_quantiles(keep["probs"], keep["method"])
+        return out
+
+    def _paired_check(self, who, baseline, policy, members, n_steps, history_steps):
+        """The arguments compare() and compare_burden() share, checked before anything runs: (baseline, policy, members,
+        history_steps) as dicts, a list of dicts and an int or None."""
+        baseline, policy = dict(baseline), dict(policy)
+        members = self._members(members)
+        if "index_cases" in baseline or "index_cases" in policy:
+            raise ValueError("%s: the index cases belong to the member, not to an arm (the pairing needs the same ones in both)" % who)
+        if history_steps is not None:
+            history_steps = int(history_steps)
+            if not 1 <= history_steps <= n_steps:
+                raise ValueError("%s: history_steps must be in 1..n_steps" % who)
+            if any("index_cases" in m for m in members):
+                raise ValueError("%s: a branch cannot change the index cases of the shared history" % who)
+            fixed = sorted(k for k in self._FIXED_BY_HISTORY if k in baseline or k in policy)
+            if fixed:
+                raise ValueError("%s: %s cannot change behind a shared history" % (who, ", ".join(fixed)))
+        return baseline, policy, members, history_steps
+
+    def _paired_members(self, baseline, policy, members, n_steps, history_steps, keep, table, fold):
+        """The member loop compare() and compare_burden() share, behind their begins: the shared history once where asked for;
+        then per member the baseline arm, keep(), the policy arm, table() -- gathered -- and, with `fold`, the fold into the
+        accumulators in force.  Returns (the tables, the padded records of the baseline arms, of the policy arms)."""
+        sim = self.simulator
         history = np.zeros(0, RECORD_DTYPE)
         if history_steps is not None:
             sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
@@ -917,14 +1004,50 @@ class Ensemble:
         tables, rec_b, rec_p = [], [], []
         for m in members:
             rec_b.append(pad_records(arm(baseline, m), n_steps))
-            sim.keep_baseline()
+            keep()
             rec_p.append(pad_records(arm(policy, m), n_steps))
-            tables.append(sim.compare(where, 0, n_steps))
-            if rows is not None:
+            tables.append(table())
+            if fold:
                 sim.ensemble_fold()
+        return tables, rec_b, rec_p
+
+    def compare_burden(self, baseline, policy, members, n_steps, history_steps=None, where="all", what="occupancy", rows=None, quantiles=None):
+        """compare() for the hospital burden under the tables of Ensemble(..., burden=...): every member is run under `baseline`,
+        its admitted cases are kept on the device (Simulator.keep_burden_baseline), it is run again under `policy` with the same
+        seed and index cases, and Simulator.burden_compare(where) over the steps 1 .. n_steps is gathered -- bed-steps,
+        admissions and deaths of both arms per column.  A case's outcome is keyed by its onset: cases that keep theirs have the
+        same outcome in both arms, which is what reduces the variance of the difference.  rows: None, or dict(first_step=...,
+        n_rows=..., stride=..., cumulative=..., min_baseline=..., min_averted=...): every member is also folded into the
+        burden-paired accumulators of `what` ("occupancy", "admissions" or "deaths"; Simulator.ensemble_begin_burden_paired)
+        and the result carries paired_summary of them.  quantiles: None, or probabilities (with rows): the quantiles over the
+        members of baseline - policy per cell, BurdenCompareResult.averted_quantiles (int32, the inverted CDF).  history_steps as
+        for compare().  Returns a BurdenCompareResult."""
+        sim = self.simulator
+        n_steps = int(n_steps)
+        who = "Ensemble.compare_burden"
+        place = sim._compare_place(who, where)
+        baseline, policy, members, history_steps = self._paired_check(who, baseline, policy, members, n_steps, history_steps)
+        keep = _keep_spec(who, "paired", dict(quantiles=quantiles), len(members)) if quantiles is not None else None
+        if keep is not None and rows is None:
+            raise ValueError("%s: quantiles are taken of the paired rows: give rows= too" % who)
+        if rows is not None:
+            unknown = set(rows) - {"first_step", "n_rows", "stride", "cumulative", "min_baseline", "min_averted"}
+            if unknown:
+                raise ValueError("%s: rows takes first_step, n_rows, stride, cumulative, min_baseline and min_averted, got %s" % (who, sorted(unknown)))
+            rows = dict(rows)
+            first, stride = int(rows.get("first_step", 1)), int(rows.get("stride", 24))
+            n_rows = rows.get("n_rows")
+            if n_rows is None:
+                n_rows = (n_steps - first) // stride + 1 if stride > 0 and 1 <= first <= n_steps else 0
+            rows.update(first_step=first, n_rows=int(n_rows), stride=stride)
+            sim.ensemble_begin_burden_paired(where, what, **rows)
+            if keep is not None and members:
+                sim.ensemble_keep_members(len(members))
+        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, sim.keep_burden_baseline,
+                                                    lambda: sim.burden_compare(where, 1, n_steps), rows is not None)
         summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
         codes = self.area_codes if place == _lib.AREA_HOME else None
-        out = CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
+        out = BurdenCompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, what, codes)
         if keep is not None and members and keep["probs"]:
             out.quantile_probs = np.asarray(keep["probs"], np.float64)
             out.averted_quantiles = sim.ensemble_quantiles(keep["probs"], keep["method"])

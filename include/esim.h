@@ -1111,6 +1111,66 @@ int  esim_burden_summary(esim_ctx *ctx, int where, uint32_t first_step, uint32_t
                          uint64_t *bed_steps, uint32_t *admissions, uint32_t *deaths /* [n_cols] each, any may be NULL */);
 int  esim_ensemble_begin_burden_peaks(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step, uint32_t threshold, uint32_t min_peak);
 
+/* Hospital burden across runs: a run's ADMITTED CASES AS A LIST ON THE DEVICE that outlives the run -- one entry
+ * (citizen, admit_step, end_step, died) of 12 B for every case the contract above admits, under the tables and labels in force and
+ * the steps run; admit_step and end_step may lie beyond the run, the consumers clip them.  The order of a list is unspecified;
+ * every output below is an integer sum over it, exact and reproducible.  No step kernel is touched and no existing output changes.
+ * esim_burden_baseline_keep: collects the list of the run as it stands and keeps it: 12 B per entry of the exposure log, allocated
+ *        at the first keep and grown when a later run needs more; one baseline per context, a later keep replaces it.  Kept with
+ *        it: the steps run, the entries, the deaths among them and the parameters in force (the seed among them).  Independent
+ *        of esim_baseline_keep.  It is kept through esim_reset, esim_restart, esim_restart_seeded, esim_snapshot, esim_rollback and
+ *        esim_checkpoint_restore; dropped by an upload, esim_burden_baseline_drop and esim_destroy, and whenever the severity
+ *        tables are replaced or dropped (esim_burden_set, esim_burden_drop, the esim_set_groups that drops tables of several
+ *        groups): a comparison of two severity models is not what this is.  An esim_set_groups with the SAME group count keeps
+ *        tables and baseline: the entries kept were drawn under the labels in force at the keep, and a caller who then sets other
+ *        labels compares outcomes under two labelings.  Not part of a checkpoint.  Errors: those of esim_burden_outcomes, and
+ *        ESIM_ENOMEM.  A keep that fails behind its checks (ESIM_ENOMEM, ESIM_ENODEVICE) leaves NO baseline kept: the earlier
+ *        one is given up before the new one is collected, as esim_baseline_keep does.
+ * esim_burden_baseline_info: the steps, the entries, the deaths among them and the parameters of the baseline kept; any pointer
+ *        may be NULL.  esim_burden_baseline_drop forgets it (the allocation stays for the next keep).  Both are ESIM_ESTATE
+ *        without a baseline.
+ * esim_burden_baseline_read: the entries in no particular order, under the sized-call convention of esim_outbreaks: *n_out = the
+ *        entries; ESIM_ERANGE with nothing written where cap is smaller; any array may be NULL.
+ * esim_burden_compare: over the window [first_step, last_step], per column, the three totals of esim_burden_summary for both runs:
+ *        bed_steps = the sum over the entries of |[admit_step, end_step - 1] cut to the window|, admissions = the entries with
+ *        admit_step inside, deaths = the entries that died with end_step inside.  Each _b output is, cell for cell, what
+ *        esim_burden_summary returned for that window at the moment of the keep, each _c output what it returns now; [n_cols]
+ *        each, any NULL.  where = ESIM_BY_ALL, ESIM_AREA_HOME or ESIM_BY_GROUP (the labels in force NOW make the columns of both
+ *        runs).  ESIM_ERANGE for first_step 0, last_step < first_step, or a last_step beyond the steps of either run;
+ *        ESIM_ESTATE without a baseline.
+ * esim_burden_compare_series: the rows of esim_burden_series(where, what, ...) for both runs, the baseline clipped at its own
+ *        steps run, the current run at its own; either output may be NULL.  cumulative != 0: the prefix over the rows of the
+ *        event kinds, summed on the device; ESIM_EINVAL with ESIM_BURDEN_OCCUPANCY.  ESIM_ERANGE for first_step 0 and when
+ *        the last row's step lies beyond either run.
+ * PAIRING: a case's Philox block is keyed by (citizen, onset).  A citizen who is a case in both runs with the same onset has the
+ *        same outcome in both; a citizen whose onset shifts draws a different outcome.  The difference of two runs under one
+ *        seed is therefore unbiased, and its variance is reduced only for the cases whose onset does not move.
+ * esim_ensemble_begin_burden_series: accumulators [n_rows][n_cols] over the rows of esim_burden_series: esim_ensemble_fold makes
+ *        the member's rows and adds members += 1 once and, per cell with value v, sum += v, sumsq += v * v, hit += 1 iff
+ *        v >= min_count (beds against a capacity).  Read by esim_ensemble_read_series; esim_ensemble_keep_members, quantiles
+ *        and exceedance work behind it unchanged.  A fold is ESIM_ERANGE, with nothing folded, when the last row lies beyond
+ *        the member's steps.
+ * esim_ensemble_begin_burden_paired: the paired kind's accumulators over the two row planes of esim_burden_compare_series; read by
+ *        esim_ensemble_read_paired, the kept members are baseline - current, signed.  A fold is ESIM_ESTATE without a burden
+ *        baseline: every member keeps its own before its policy run.  min_averted >= 1.
+ * Every call that computes is ESIM_ESTATE in the cases esim_burden_outcomes names; a refused call leaves its outputs untouched.
+ * Device memory beside the baseline: 12 B per log entry for the list of the run as it stands, allocated by the first call that
+ * compares or folds and kept for the next (grown when a log is longer; freed by an upload and esim_destroy).  Temporary, freed
+ * when the call returns: 4 B per citizen for the vaccination replay once a programme has run, 32 B per column (compare), 8 B per
+ * cell (compare_series). */
+int  esim_burden_baseline_keep(esim_ctx *ctx);
+int  esim_burden_baseline_info(esim_ctx *ctx, uint32_t *steps, uint32_t *n_admitted, uint32_t *n_died, esim_params *p);
+int  esim_burden_baseline_drop(esim_ctx *ctx);
+int  esim_burden_baseline_read(esim_ctx *ctx, uint32_t *citizen, uint32_t *admit_step, uint32_t *end_step, uint8_t *died /* [cap] each, any may be NULL */,
+                               uint32_t cap, uint32_t *n_out);
+int  esim_burden_compare(esim_ctx *ctx, int where, uint32_t first_step, uint32_t last_step, uint64_t *bed_steps_b, uint64_t *bed_steps_c,
+                         uint32_t *admissions_b, uint32_t *admissions_c, uint32_t *deaths_b, uint32_t *deaths_c /* [n_cols] each, any may be NULL */);
+int  esim_burden_compare_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, int cumulative,
+                                uint32_t *baseline /* [n_rows * n_cols] or NULL */, uint32_t *current /* same, or NULL */);
+int  esim_ensemble_begin_burden_series(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t min_count);
+int  esim_ensemble_begin_burden_paired(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, int cumulative,
+                                       uint32_t min_baseline, uint32_t min_averted);
+
 /* GPU time per phase since the last reset, seconds, in the reference's timer labels
  * (simulator.rs:137,140,143; statistics.rs:138-140):
  *   out[0] "Generate Exposures", out[1] "Apply Exposures", out[2] "Apply Interventions", out[3] total.
