@@ -35,7 +35,8 @@ def table_set_t():
 
 def oracle_run(pop, ep, n_steps):
     """Steps the oracle n_steps times: dict(onset [n] -- NEVER for a citizen never Infected after a step --, vax_exposed,
-    vax_infected (citizens Vaccinated after a step that were Exposed / Infected after the one before), records, final_state)."""
+    vax_infected (citizens Vaccinated after a step that were Exposed / Infected after the one before), records, final_state,
+    exposure_step (the step of the citizen's exposure in the oracle's log, 0: none))."""
     orc = _oracle.Oracle(pop, _oracle.params_from_esim(ep))
     n = pop.n_citizens
     before = orc.state()["status"].copy()
@@ -52,8 +53,9 @@ def oracle_run(pop, ep, n_steps):
         vax_e |= now & (before == _lib.EXPOSED)
         vax_i |= now & (before == _lib.INFECTED)
         before = after.copy()
+    exposure_step = orc.exposures()[0].astype(np.int64)
     orc.close()
-    return dict(onset=onset, vax_exposed=vax_e, vax_infected=vax_i, records=records, final_state=state)
+    return dict(onset=onset, vax_exposed=vax_e, vax_infected=vax_i, records=records, final_state=state, exposure_step=exposure_step)
 
 
 def blocks(seed_of, ids, onset):
@@ -157,12 +159,20 @@ def w2():
     return pop, ep, labels, n_groups
 
 
-def build(pop, ep, labels, n_groups, n_steps):
-    """dict(pop, ep, labels, n_groups, n_steps, run = oracle_run, full = the outcomes under table set T, cols = {where: (labels, n_cols)})."""
-    run = oracle_run(pop, ep, n_steps)
-    full = outcomes(run["onset"], labels, table_set_t(), lambda s: int(ep.seed), pop.citizen_id_base)
+def table_groups(tables, labels):
+    """The group of every citizen under `tables`: the labels, or group 0 for all under tables of one group, whatever the labels."""
+    return np.asarray(labels) if len(tables["admit_thr"]) != 1 else np.zeros(len(labels), np.uint16)
+
+
+def build(pop, ep, labels, n_groups, n_steps, tables=None, run=None):
+    """dict(pop, ep, labels, n_groups, n_steps, tables, run = oracle_run, full = the outcomes under the tables, cols = {where: (labels,
+    n_cols)}).  tables: None for table set T; tables of one group apply to everybody, and the labels only make the columns by
+    group.  run: an oracle_run of (pop, ep, n_steps) made before, for several table sets over one run."""
+    tables = table_set_t() if tables is None else tables
+    run = oracle_run(pop, ep, n_steps) if run is None else run
+    full = outcomes(run["onset"], table_groups(tables, labels), tables, lambda s: int(ep.seed), pop.citizen_id_base)
     cols = {where: _curve_ref.labels_for(pop, where, (labels, n_groups)) for where in WHERES}
-    return dict(pop=pop, ep=ep, labels=np.asarray(labels), n_groups=n_groups, n_steps=n_steps, run=run, full=full, cols=cols)
+    return dict(pop=pop, ep=ep, labels=np.asarray(labels), n_groups=n_groups, n_steps=n_steps, tables=tables, run=run, full=full, cols=cols)
 
 
 def counts(world):

@@ -52,13 +52,15 @@ def series_windows(t):
     return ((1, None, 1), (1, None, 24), (t // 3, None, 24))
 
 
-def check_compare(sim, cols, o_base, t_base, o_cur, t_cur, note, kept_summary=None):
+def check_compare(sim, cols, o_base, t_base, o_cur, t_cur, note, kept_summary=None, spans=None, series=None):
     """Everything the comparison calls give against the outcomes of both arms; the _c side also against the library's own
-    burden_summary and burden_series of the run as it stands, the _b side against the summaries taken at the keep."""
+    burden_summary and burden_series of the run as it stands, the _b side against the summaries taken at the keep.  spans: the
+    (first_step, last_step) of the totals instead of the three below; series: the (first_step, n_rows, stride) instead of
+    series_windows(t)."""
     t = min(t_base, t_cur)
     for where in WHERES:
         lab, n_cols = cols[where]
-        for first, last in ((1, t), (min(200, t), min(500, t)), (t, t)):
+        for first, last in (((1, t), (min(200, t), min(500, t)), (t, t)) if spans is None else spans):
             got = sim.burden_compare(where, first, last)
             what = "%s: by %s, steps %d..%d" % (note, where, first, last)
             same_totals(got, beds.totals(o_base, lab, n_cols, t_base, first, last), "_baseline", what)
@@ -69,10 +71,10 @@ def check_compare(sim, cols, o_base, t_base, o_cur, t_cur, note, kept_summary=No
             for k in beds.TOTALS:
                 same(got[k + "_averted"], got[k + "_baseline"].astype(np.int64) - got[k + "_current"].astype(np.int64), what + ": averted " + k)
         for what in WHATS:
-            for first, n_rows, stride in series_windows(t):
+            for first, n_rows, stride in (series_windows(t) if series is None else series):
                 for cumulative in ((False,) if what == "occupancy" else (False, True)):
                     b, c = sim.burden_compare_series(what, where, first, n_rows, stride, cumulative)
-                    k = (t - first) // stride + 1
+                    k = (t - first) // stride + 1 if n_rows is None else n_rows
                     tag = "%s: %s by %s from step %d, stride %d%s" % (note, what, where, first, stride, ", cumulative" if cumulative else "")
                     same(b, beds.rows(o_base, what, lab, n_cols, t_base, first, k, stride, cumulative), tag + ", baseline")
                     same(c, beds.rows(o_cur, what, lab, n_cols, t_cur, first, k, stride, cumulative), tag + ", current")

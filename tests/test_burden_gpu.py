@@ -55,30 +55,31 @@ def windows(t):
     return out
 
 
-def check_world(sim, cols, o, t, note):
-    """Everything the library gives after t steps against the outcomes `o` of the reference."""
+def check_world(sim, cols, o, t, note, series=None, summaries=None):
+    """Everything the library gives after t steps against the outcomes `o` of the reference.  series: the (first_step, n_rows,
+    stride) of the series calls instead of windows(t); summaries: the (first_step, last_step, threshold) of the summary calls."""
     same_outcomes(sim, o, note)
     for where in WHERES:
         lab, n_cols = cols[where]
         for what in WHATS:
-            for first, n_rows, stride in windows(t):
+            for first, n_rows, stride in (windows(t) if series is None else series):
                 same(sim.burden_series(what, where, first, n_rows, stride), ref.series(o, what, lab, n_cols, t, first, n_rows, stride),
                      "%s: %s by %s from step %d, stride %d" % (note, what, where, first, stride))
-        spans = [(1, t, 1), (1, t, 10)] + ([(t // 3, t - 7, 10), (t // 2, t // 2, 1)] if t >= 48 else [])
+        spans = summaries if summaries is not None else [(1, t, 1), (1, t, 10)] + ([(t // 3, t - 7, 10), (t // 2, t // 2, 1)] if t >= 48 else [])
         for first, last, threshold in spans:
             same_summary(sim.burden_summary(where, first, last, threshold), ref.summary(o, lab, n_cols, t, first, last, threshold),
                          "%s: summary by %s, steps %d..%d, threshold %d" % (note, where, first, last, threshold))
 
 
-def check_stops(world, stops, note):
+def check_stops(world, stops, note, tables=T, **windows_of_check_world):
     sim = Simulator(world["pop"], world["ep"])
     sim.set_groups(world["labels"], world["n_groups"])
-    sim.set_burden(T)
+    sim.set_burden(tables)
     done = 0
     for s in stops:
         sim.run(s - done)
         done = s
-        check_world(sim, world["cols"], ref.at_stop(world["full"], s), s, "%s, %d steps run" % (note, s))
+        check_world(sim, world["cols"], ref.at_stop(world["full"], s), s, "%s, %d steps run" % (note, s), **windows_of_check_world)
     return sim
 
 
