@@ -59,18 +59,18 @@ extern "C" int esim_contact_hours(esim_ctx *ctx, int where, uint32_t setting_mas
     if (e == hipSuccess && per_case) e = hipMemsetAsync(cases.p, 0, sizeof(uint32_t) * std::max<size_t>(1, d.n), c->stream);
     if (e != hipSuccess) return leave(ESIM_ENODEVICE, hipGetErrorString(e));
     if (hours || per_case) {
-        const int mode = where == ESIM_BY_ALL ? CT_ONE_CELL : lds <= CONTACT_LDS_BYTES ? CT_LDS : CT_GLOBAL;
+        const int mode = pairtab_mode(where, lds);
         if ((setting_mask >> ESIM_SETTING_HOUSEHOLD) & 1u) {
             const dim3 grid(grid_capped(c, log_len, TPB, 4096));
-            if (mode == CT_ONE_CELL) hipLaunchKernelGGL(k_contact_home<CT_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
-            else if (mode == CT_LDS) hipLaunchKernelGGL(k_contact_home<CT_LDS>, dim3(grid_capped(c, log_len, TPB * HH_SAR_PER_LANE, 4096, TPB)), dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
-            else hipLaunchKernelGGL(k_contact_home<CT_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
+            if (mode == PAIRTAB_ONE_CELL) hipLaunchKernelGGL(k_contact_home<PAIRTAB_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
+            else if (mode == PAIRTAB_LDS) hipLaunchKernelGGL(k_contact_home<PAIRTAB_LDS>, dim3(grid_capped(c, log_len, TPB * HH_SAR_PER_LANE, 4096, TPB)), dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
+            else hipLaunchKernelGGL(k_contact_home<PAIRTAB_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
         }
         if (setting_mask & ~(1u << ESIM_SETTING_HOUSEHOLD)) {
             const dim3 grid(grid_capped(c, log_len, TPB / 64u, 4096));
-            if (mode == CT_ONE_CELL) hipLaunchKernelGGL(k_contact_wide<CT_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
-            else if (mode == CT_LDS) hipLaunchKernelGGL(k_contact_wide<CT_LDS>, grid, dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
-            else hipLaunchKernelGGL(k_contact_wide<CT_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
+            if (mode == PAIRTAB_ONE_CELL) hipLaunchKernelGGL(k_contact_wide<PAIRTAB_ONE_CELL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
+            else if (mode == PAIRTAB_LDS) hipLaunchKernelGGL(k_contact_wide<PAIRTAB_LDS>, grid, dim3(TPB), lds, c->stream, d, w.s.q, k, log_len);
+            else hipLaunchKernelGGL(k_contact_wide<PAIRTAB_GLOBAL>, grid, dim3(TPB), 0, c->stream, d, w.s.q, k, log_len);
         }
     }
     if (long_routes && n_bus && d.n_routes) {

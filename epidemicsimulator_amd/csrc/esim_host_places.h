@@ -1,12 +1,13 @@
 // esim_host_places.h -- work place and school outbreaks: esim_place_outbreaks, esim_place_sizes (on top of settings_enqueue /
-// settings_finish) and esim_place_sar (on top of tree_enqueue / tree_finish); the kernels: esim_kernels_places.h; DESIGN 24.
+// settings_finish) and esim_place_sar (on top of sar_begin / sar_finish of esim_host_household.h); the kernels: esim_kernels_household.h,
+// esim_kernels_places.h; DESIGN 24.
 // All three work in temporary device memory that lives as long as the call, and leave the context as it is.
 namespace {
 
 struct PlaceWork {
     DevTmp<uint32_t> tab;             // members, cases, introductions, first_step of the rooms or work places, of the schools
                                       // where they are asked for, then the two tables of PLACE_CELLS
-    Place list, out;                  // what k_place_members fills; what the call delivers (the schools, or `list` again)
+    Place list, out;                  // what k_list_members fills; what the call delivers (the schools, or `list` again)
 };
 
 bool place_kind_known(int kind) { return kind == ESIM_PLACE_WORK || kind == ESIM_PLACE_ROOM || kind == ESIM_PLACE_SCHOOL; }
@@ -30,11 +31,11 @@ int place_enqueue(esim_ctx_impl *c, const std::string &who, int kind, const Sett
     if (e == hipSuccess && n_list) e = hipMemsetAsync(w->list.first, 0xFF, sizeof(uint32_t) * n_list, c->stream);   // (a population without a room has no row)
     if (e == hipSuccess && kind == ESIM_PLACE_SCHOOL && n_out) e = hipMemsetAsync(w->out.first, 0xFF, sizeof(uint32_t) * n_out, c->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, ESIM_ENODEVICE, who + ": " + hipGetErrorString(e)); }
-    if (kind == ESIM_PLACE_WORK) hipLaunchKernelGGL(k_place_members<false>, dim3(grid_capped(c, d.n_wrk_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
-    else hipLaunchKernelGGL(k_place_members<true>, dim3(grid_capped(c, d.n_room_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
+    if (kind == ESIM_PLACE_WORK) hipLaunchKernelGGL(k_list_members<LIST_WORK>, dim3(grid_capped(c, d.n_wrk_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
+    else hipLaunchKernelGGL(k_list_members<LIST_ROOM>, dim3(grid_capped(c, d.n_room_idx, TPB, 4096)), dim3(TPB), 0, c->stream, d, q, w->list);
     if (kind == ESIM_PLACE_SCHOOL) hipLaunchKernelGGL(k_place_schools, dim3(grid_capped(c, d.n_room, TPB, 4096)), dim3(TPB), 0, c->stream, d, w->list, w->out);
-    // (a workgroup of k_place_tables bins 32 places per lane at least before it hands over its table of 2048 counters at most)
-    if (tables) hipLaunchKernelGGL(k_place_tables, dim3(grid_capped(c, n_out, TPB * 32u, 1024, TPB)), dim3(TPB), 0, c->stream, w->out);
+    // (a workgroup of k_list_tables bins 32 places per lane at least before it hands over its table of 2048 counters at most)
+    if (tables) hipLaunchKernelGGL(k_list_tables<false>, dim3(grid_capped(c, n_out, TPB * 32u, 1024, TPB)), dim3(TPB), 0, c->stream, d, w->out);
     return ESIM_OK;
 }
 
@@ -86,42 +87,17 @@ extern "C" int esim_place_sar(esim_ctx *ctx, int kind, int where, uint32_t first
     if ((!at_risk && !secondary) || (where != ESIM_BY_ALL && where != ESIM_BY_GROUP) || (kind != ESIM_PLACE_WORK && kind != ESIM_PLACE_ROOM))
         return fail(c, ESIM_EINVAL, who + ": no output, a `where` that is neither ESIM_BY_ALL nor ESIM_BY_GROUP, or a `kind` that is neither ESIM_PLACE_WORK nor ESIM_PLACE_ROOM "
                                           "(the infector of a school exposure is somebody of the room)");
-    if (int rc = tree_check(c, who)) return rc;
-    if (where == ESIM_BY_GROUP && !c->grp.lab) return fail(c, ESIM_ESTATE, who + ": by group without labels (esim_set_groups)");
-    if (last_step < first_step || last_step > c->host_t - 1u)
-        return fail(c, ESIM_ERANGE, who + ": last_step before first_step, or beyond the steps run so far");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the pair counters are 64 bits wide");
-    PlaceSar s;
-    s.first = first_step; s.last = last_step;
-    s.n_cols = where == ESIM_BY_ALL ? 1u : c->grp.n;
-    s.grp = where == ESIM_BY_GROUP ? (const uint16_t *)c->grp.lab : nullptr;
-    const size_t cells = (size_t)s.n_cols * s.n_cols, lds = 2 * cells * sizeof(unsigned long long);
-    DevTmp<unsigned long long> tab;
-    if (tab.alloc(2 * cells) != hipSuccess) { (void)hipGetLastError(); return fail(c, ESIM_ENOMEM, who + ": no device memory for the pair tables (16 B per cell)"); }
-    s.at_risk = tab.p; s.secondary = tab.p + cells;
-    TreeWork w;
+    SarWork k;
     PlaceWork pw;
-    if (int rc = tree_enqueue(c, who, &w, false)) return rc;
-    if (int rc = place_enqueue(c, who, kind, w.s.q, &pw, false)) return rc;
-    HIP_TRY(c, hipMemsetAsync(tab.p, 0, sizeof(unsigned long long) * std::max<size_t>(1, 2 * cells), c->stream));
+    if (int rc = sar_begin(c, who, where, first_step, last_step, &k)) return rc;
+    if (int rc = place_enqueue(c, who, kind, k.w.s.q, &pw, false)) return rc;
     const bool rooms = kind == ESIM_PLACE_ROOM;
-#ifndef PLACE_SAR_PER_CASE
     // a workgroup scans TPB places at a time; the grid stays wide, the long places lie where they lie
     const dim3 grid(grid_capped(c, pw.list.n_places, TPB, 16384));
-#define PLACE_SAR_LAUNCH(MODE, ROOMS, LDS) hipLaunchKernelGGL((k_place_sar<MODE, ROOMS>), grid, dim3(TPB), LDS, c->stream, c->d, w.s.q, w.t, pw.list, s)
-#else
-    const uint32_t log_len = w.s.log_len;
-    const dim3 grid(grid_capped(c, log_len, TPB / 64u, 4096));
-#define PLACE_SAR_LAUNCH(MODE, ROOMS, LDS) hipLaunchKernelGGL((k_place_sar<MODE, ROOMS>), grid, dim3(TPB), LDS, c->stream, c->d, w.s.q, w.t, pw.list, s, log_len)
-#endif
-    if (where == ESIM_BY_ALL) { if (rooms) PLACE_SAR_LAUNCH(PLACE_ONE_CELL, true, 0); else PLACE_SAR_LAUNCH(PLACE_ONE_CELL, false, 0); }
-    else if (lds <= PLACE_LDS_BYTES) { if (rooms) PLACE_SAR_LAUNCH(PLACE_LDS, true, lds); else PLACE_SAR_LAUNCH(PLACE_LDS, false, lds); }
-    else { if (rooms) PLACE_SAR_LAUNCH(PLACE_GLOBAL, true, 0); else PLACE_SAR_LAUNCH(PLACE_GLOBAL, false, 0); }
+#define PLACE_SAR_LAUNCH(MODE, ROOMS, LDS) hipLaunchKernelGGL((k_place_sar<MODE, ROOMS>), grid, dim3(TPB), LDS, c->stream, c->d, k.w.s.q, k.w.t, pw.list, k.s)
+    if (k.mode == PAIRTAB_ONE_CELL) { if (rooms) PLACE_SAR_LAUNCH(PAIRTAB_ONE_CELL, true, 0); else PLACE_SAR_LAUNCH(PAIRTAB_ONE_CELL, false, 0); }
+    else if (k.mode == PAIRTAB_LDS) { if (rooms) PLACE_SAR_LAUNCH(PAIRTAB_LDS, true, k.lds); else PLACE_SAR_LAUNCH(PAIRTAB_LDS, false, k.lds); }
+    else { if (rooms) PLACE_SAR_LAUNCH(PAIRTAB_GLOBAL, true, 0); else PLACE_SAR_LAUNCH(PAIRTAB_GLOBAL, false, 0); }
 #undef PLACE_SAR_LAUNCH
-    const int rc = tree_finish(c, who, &w);
-    if (rc && rc != ESIM_ESIM) return rc;
-    if (at_risk) HIP_TRY(c, hipMemcpy(at_risk, s.at_risk, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
-    if (secondary) HIP_TRY(c, hipMemcpy(secondary, s.secondary, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
-    return rc;
+    return sar_finish(c, who, &k, at_risk, secondary);
 }

@@ -36,6 +36,7 @@
 #include "esim_kernels_setting.h"
 #include "esim_kernels_tree.h"
 #include "esim_kernels_chains.h"
+#include "esim_kernels_pairtab.h"
 #include "esim_kernels_household.h"
 #include "esim_kernels_places.h"
 #include "esim_kernels_contacts.h"

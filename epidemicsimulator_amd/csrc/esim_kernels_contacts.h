@@ -10,11 +10,8 @@
 // setting.  Nothing here writes simulation state.
 #pragma once
 
-// k_contact_home and k_contact_wide keep the four planes of `hours` in LDS while their 4 * n_cols^2 64-bit counters fit here
-// (n_cols <= 32), a fifth of a compute unit's LDS as HH_LDS_BYTES; beyond it every pair goes to the global table.
-#ifndef CONTACT_LDS_BYTES
-#define CONTACT_LDS_BYTES 32768u
-#endif
+// k_contact_home and k_contact_wide count in the modes of esim_kernels_pairtab.h: the four planes of `hours` are one table of
+// 4 * n_cols^2 counters, in LDS while it fits PAIRTAB_LDS_BYTES (n_cols <= 32).
 #define CONTACT_ROUTE_GROUPS 1024u    // k_contact_route counts the Susceptible of a bus by group in LDS up to this many groups
 #define CONTACT_INF   0x80000000u     // on a rider's word: Infected in the step
 #define CONTACT_TAKES 0x40000000u     // ... Susceptible and taking the bus draw
@@ -33,7 +30,6 @@ struct Contact {
     uint32_t *per_case;              // [n] zeroed by the caller, or nullptr
 };
 
-enum { CT_ONE_CELL = 0, CT_LDS = 1, CT_GLOBAL = 2 };
 enum { CT_SET_WORK = 0xAu, CT_SET_BUS = 0xCu };        // the combinations with the work bit, with the bus bit
 
 // The Infected steps of citizen j inside the window, [*f, *l] (empty: *f > *l): exposed_time + 1 steps behind its exposure
@@ -90,26 +86,7 @@ __device__ __forceinline__ void contact_add(const Contact &k, unsigned long long
     if (!cnt) return;
     const uint32_t gm = k.grp[m];
     if (gm >= k.n_cols) return;
-    const uint32_t cell = s * k.n_cols * k.n_cols + row + gm;
-    if (MODE == CT_LDS) atomicAdd(&lds[cell], (unsigned long long)cnt);
-    else atomicAdd(&k.hours[cell], (unsigned long long)cnt);
-}
-
-__device__ __forceinline__ unsigned long long contact_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// The workgroup's LDS table handed to the global one, non-zero counters only.
-__device__ __forceinline__ void contact_flush(const Contact &k, const unsigned long long *lds)
-{
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < 4u * k.n_cols * k.n_cols; i += TPB) {
-        const unsigned long long v = lds[i];
-        if (v) atomicAdd(&k.hours[i], v);
-    }
+    pairtab_add<MODE>(lds, k.hours, s * k.n_cols * k.n_cols + row + gm, cnt);
 }
 
 // Households: a lane per entry of the log, one walk over the household of case j.
@@ -117,10 +94,7 @@ template <int MODE>
 __global__ __launch_bounds__(TPB) void k_contact_home(Dev d, Setting q, Contact k, uint32_t log_len)
 {
     extern __shared__ unsigned long long ct_lds[];
-    if (MODE == CT_LDS) {
-        for (uint32_t i = threadIdx.x; i < 4u * k.n_cols * k.n_cols; i += TPB) ct_lds[i] = 0ull;
-        __syncthreads();
-    }
+    if (MODE == PAIRTAB_LDS) pairtab_clear(ct_lds, 4u * k.n_cols * k.n_cols);
     unsigned long long sum = 0ull;
     for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < (uint64_t)log_len; i += (uint64_t)gridDim.x * TPB) {
         const uint32_t j = d.log[i];
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(TPB) void k_contact_home(Dev d, Setting q, Contact 
         const uint32_t lo = d.res_off[b], hi = d.res_off[b + 1u];
         if (lo > hi || hi > d.n) continue;
         uint32_t row = 0u;
-        if (MODE != CT_ONE_CELL) {
+        if (MODE != PAIRTAB_ONE_CELL) {
             const uint32_t gj = k.grp[j];
             if (gj >= k.n_cols) continue;
             row = gj * k.n_cols;
@@ -146,22 +120,19 @@ __global__ __launch_bounds__(TPB) void k_contact_home(Dev d, Setting q, Contact 
             if (m >= d.n || m == j) continue;
             const uint32_t end = hh_susceptible_end(d, q, m);
             const uint32_t cnt = contact_steps(k, set_j & contact_set_home_sus(d.cit[m]), f, end < l ? end : l);
-            if (MODE == CT_ONE_CELL) { mine += cnt; continue; }
+            if (MODE == PAIRTAB_ONE_CELL) { mine += cnt; continue; }
             if (cnt && k.grp[m] < k.n_cols) mine += cnt;
             contact_add<MODE>(k, ct_lds, ESIM_SETTING_HOUSEHOLD, row, m, cnt);
         }
         sum += mine;
         if (k.per_case && mine) atomicAdd(&k.per_case[j], mine);
     }
-    if (MODE == CT_ONE_CELL) {
-        sum = contact_wave_sum(sum);
-        if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(&k.hours[ESIM_SETTING_HOUSEHOLD], sum);
-    }
-    if (MODE == CT_LDS) contact_flush(k, ct_lds);
+    if (MODE == PAIRTAB_ONE_CELL) pairtab_wave_add(&k.hours[ESIM_SETTING_HOUSEHOLD], sum);
+    if (MODE == PAIRTAB_LDS) pairtab_flush(ct_lds, k.hours, 4u * k.n_cols * k.n_cols);
 }
 
 // One member list [lo, hi) of case j by one wavefront, ids read coalesced.  KIND 0: a work place or a room, 1: a route that is
-// one bus.  Returns the lane's share of the contact-hours (counted into the cells already unless MODE is CT_ONE_CELL).
+// one bus.  Returns the lane's share of the contact-hours (counted into the cells already unless MODE is PAIRTAB_ONE_CELL).
 template <int MODE, int KIND>
 __device__ __forceinline__ uint32_t contact_member_list(const Dev &d, const Setting &q, const Contact &k, unsigned long long *lds, const uint32_t *idx, uint32_t lo, uint32_t hi,
                                                         uint32_t j, uint32_t set_j, uint32_t f, uint32_t l, uint32_t s, uint32_t row, uint32_t lane)
@@ -173,7 +144,7 @@ __device__ __forceinline__ uint32_t contact_member_list(const Dev &d, const Sett
         const uint32_t wm = d.cit[m];
         const uint32_t end = KIND == 0 ? hh_susceptible_end(d, q, m) : contact_bus_end(d, q, m, wm);
         const uint32_t cnt = contact_steps(k, set_j & (KIND == 0 ? contact_set_work_sus(wm) : (uint32_t)CT_SET_BUS), f, end < l ? end : l);
-        if (MODE == CT_ONE_CELL) { mine += cnt; continue; }
+        if (MODE == PAIRTAB_ONE_CELL) { mine += cnt; continue; }
         if (cnt && k.grp[m] < k.n_cols) mine += cnt;
         contact_add<MODE>(k, lds, s, row, m, cnt);
     }
@@ -185,10 +156,7 @@ template <int MODE>
 __global__ __launch_bounds__(TPB) void k_contact_wide(Dev d, Setting q, Contact k, uint32_t log_len)
 {
     extern __shared__ unsigned long long ct_lds[];
-    if (MODE == CT_LDS) {
-        for (uint32_t i = threadIdx.x; i < 4u * k.n_cols * k.n_cols; i += TPB) ct_lds[i] = 0ull;
-        __syncthreads();
-    }
+    if (MODE == PAIRTAB_LDS) pairtab_clear(ct_lds, 4u * k.n_cols * k.n_cols);
     const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * (TPB / 64u) + (threadIdx.x >> 6), n_waves = gridDim.x * (TPB / 64u);
     unsigned long long sum[3] = { 0ull, 0ull, 0ull };                       // work place, school, transport
     for (uint32_t e = wave; e < log_len; e += n_waves) {
@@ -199,7 +167,7 @@ __global__ __launch_bounds__(TPB) void k_contact_wide(Dev d, Setting q, Contact 
         contact_infected_span(d, q, k, j, wj, &f, &l);
         if (f > l) continue;
         uint32_t row = 0u;
-        if (MODE != CT_ONE_CELL) {
+        if (MODE != PAIRTAB_ONE_CELL) {
             const uint32_t gj = k.grp[j];
             if (gj >= k.n_cols) continue;
             row = gj * k.n_cols;
@@ -238,19 +206,16 @@ __global__ __launch_bounds__(TPB) void k_contact_wide(Dev d, Setting q, Contact 
             }
         }
         if (k.per_case) {
-            const uint32_t all = (uint32_t)contact_wave_sum((unsigned long long)mine);
+            const uint32_t all = (uint32_t)pairtab_wave_sum((unsigned long long)mine);
             if (lane == 0u && all) atomicAdd(&k.per_case[j], all);
         }
     }
-    if (MODE == CT_ONE_CELL) {
+    if (MODE == PAIRTAB_ONE_CELL) {
         const uint32_t plane[3] = { ESIM_SETTING_WORKPLACE, ESIM_SETTING_SCHOOL, ESIM_SETTING_TRANSPORT };
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const unsigned long long v = contact_wave_sum(sum[p]);
-            if (lane == 0u && v) atomicAdd(&k.hours[plane[p]], v);
-        }
+        for (int p = 0; p < 3; ++p) pairtab_wave_add(&k.hours[plane[p]], sum[p]);
     }
-    if (MODE == CT_LDS) contact_flush(k, ct_lds);
+    if (MODE == PAIRTAB_LDS) pairtab_flush(ct_lds, k.hours, 4u * k.n_cols * k.n_cols);
 }
 
 // Routes longer than a bus: a bit per (bus step number i in [i_lo, i_hi) of the window's bus steps, route) in which a rider of
@@ -404,7 +369,7 @@ __global__ __launch_bounds__(TPB) void k_contact_trans(Dev d, Setting q, Tree t,
         if (a < k.n_cols && b < k.n_cols) atomicAdd(&k.trans[(size_t)s * k.n_cols * k.n_cols + (size_t)a * k.n_cols + b], 1ull);
     }
     if (k.grp) return;
-    const unsigned long long v0 = contact_wave_sum(n0), v1 = contact_wave_sum(n1), v2 = contact_wave_sum(n2), v3 = contact_wave_sum(n3);
+    const unsigned long long v0 = pairtab_wave_sum(n0), v1 = pairtab_wave_sum(n1), v2 = pairtab_wave_sum(n2), v3 = pairtab_wave_sum(n3);
     if ((threadIdx.x & 63u) == 0u) {
         if (v0) atomicAdd(&k.trans[0], v0);
         if (v1) atomicAdd(&k.trans[1], v1);

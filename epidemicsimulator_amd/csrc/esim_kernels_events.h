@@ -50,7 +50,7 @@ __global__ __launch_bounds__(TPB) void k_event_keys(Dev d, Setting q, Tree t, ui
 
 // sizes[setting][min(count, ESIM_EVENT_BINS - 1)] += 1 per occupied slot of the table.  A lane per slot; almost every event
 // falls into the first few bins, so a workgroup counts in a table of its own in LDS (4 KB) and hands its non-zero counters over
-// once, as k_hh_tables does.
+// once, as k_list_tables does.
 __global__ __launch_bounds__(PAIR_TPB) void k_event_hist(PairTable t, uint32_t *sizes)
 {
     __shared__ uint32_t tab[ESIM_N_SETTINGS * ESIM_EVENT_BINS];

@@ -60,7 +60,7 @@ TABLE = {}                               # (cap, site) -> [launches, clipped, ma
 # branch that is not compiled cannot be reached).
 SITE_FILES = ["esim_host_%s.h" % k for k in ("outputs", "settings", "tree", "household", "places", "contacts", "flows", "events", "curves", "compare",
                                              "ensrows", "snapshot", "upload")]
-NOT_DEFINED = ("PLACE_SAR_PER_CASE",)
+NOT_DEFINED = ()
 # Sites that need not be clipped: only such whose item count is a constant independent of the population.  There is none.
 ALLOWED_UNCLIPPED = {}
 
@@ -212,7 +212,7 @@ def test_households(cap, launches):
         sim, pop, ep, n, ref, house = t_households.started(name)
         t_households.check_all(sim, pop, n, ref, house, t_households.cached_pairs_of(name), "%s, cap %d" % (name, cap))
         sim.close()
-    pop, ep, n, ref, _ = areas800()                                  # 10 936 buildings: k_hh_tables' grid is clipped
+    pop, ep, n, ref, _ = areas800()                                  # 10 936 buildings: k_list_tables' grid is clipped
     sus, house = once("areas800 sus", lambda: hh.sus_until(pop, ep, n)), dict(hh.households(ref, pop), jm=hh.all_pairs(ref, pop))
     sim = run_of(pop, ep, n)
     t_households.check_all(sim, pop, n, ref, house, lambda first, last, g: hh.pairs(ref, pop, ep, sus, first, last, hh.labels(pop, g) if g else None, max(1, g), jm=house["jm"]),
@@ -240,7 +240,7 @@ def test_places(cap, launches):
         t_places.check_kind(sim, pop, n, kind, pl.outbreaks(ref, pop, kind), lambda first, last, g, kind=kind: pl.pairs_counting(world, kind, first, last, g), windows,
                             "714 rooms, cap %d" % cap)
     sim.close()
-    pop, ep, n, ref, _ = areas800()                                  # 10 936 buildings: k_place_tables' grid is clipped
+    pop, ep, n, ref, _ = areas800()                                  # 10 936 buildings: k_list_tables' grid is clipped
     world = (pop, ep, n, ref, once("areas800 sus", lambda: hh.sus_until(pop, ep, n)))
     sim = run_of(pop, ep, n)
     t_places.check_kind(sim, pop, n, "work", pl.outbreaks(ref, pop, "work"), lambda first, last, g: pl.pairs_counting(world, "work", first, last, g), ((0, n), (100, 300)),

@@ -1,5 +1,5 @@
 """Compile-time checks on the parts of the kernel translation unit (hipcc cross-compiles here, no GPU needed).  Every part of the
-chunk pass names what it depends on: a translation unit of esim_kernels_common.h and the part alone compiles.  And the three
+chunk pass, and the pair-table layer the household, place and contact outputs share, names what it depends on: a translation unit of esim_kernels_common.h and the part alone compiles.  And the three
 diagnostics builds of csrc/Makefile (prof, prof-units, count) still compile: their macros sit inside the kernels, so they are the
 first thing a change to a kernel breaks, and the product build does not see them."""
 import os
@@ -10,7 +10,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "epidemicsimulator_amd", "csrc")
 SYNTAX = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-fsyntax-only", "-std=c++17", "-I", CSRC]
-PARTS = ("esim_chunk_sets.h", "esim_kernels_plan.h", "esim_kernels_marks.h", "esim_kernels_draw.h", "esim_kernels_books.h", "esim_kernels_tiny.h")
+PARTS = ("esim_chunk_sets.h", "esim_kernels_plan.h", "esim_kernels_marks.h", "esim_kernels_draw.h", "esim_kernels_books.h", "esim_kernels_tiny.h",
+         "esim_kernels_pairtab.h")
 
 
 @pytest.mark.parametrize("part", PARTS)

@@ -6,8 +6,8 @@ calls, with esim_mixing_matrix (which shares the tree replay with the attack rat
 
     python tools/place_outbreaks.py [preset] [steps] [--repeats 9] [--variant NAME=LIBRARY ...] [--out FILE]
 
-Every --variant names another build of the library (make -C epidemicsimulator_amd/csrc places-per-case, or the product's
-sources with -DPLACE_TILE=...): the same run is made on a second context of that build in the same process, its esim_place_sar
+Every --variant names another build of the library (make -C epidemicsimulator_amd/csrc places-tile-1024: the product's
+sources with -DPLACE_TILE=...; or the library of another commit): the same run is made on a second context of that build in the same process, its esim_place_sar
 is checked against the product's, and the two are timed in turns -- a warm-up call of each, then `repeats` times one call of
 the product and one of the variant.  Every time is the time between two device events recorded on the null stream around one
 library call (the calls are synchronous: they end with their own stream wait), as the median with the smallest and the largest
