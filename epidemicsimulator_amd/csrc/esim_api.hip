@@ -12,11 +12,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "esim_host_ctx.h"
+#include "esim_host_ensemble.h"
 #include "esim_host_members.h"
 #include "esim_host_upload.h"
 #include "esim_host_run.h"

@@ -1,8 +1,8 @@
 // esim_host_beds.h -- a run's admitted cases as a list on the device and what hangs on it: the kept burden baseline
 // (esim_burden_baseline_keep / _info / _read / _drop), the comparison of the run as it stands with it (esim_burden_compare,
 // esim_burden_compare_series), and two kinds of the ensemble accumulators over rows made from lists -- the burden-series kind
-// (esim_ensemble_begin_burden_series, under ROWS_SETTINGS) and the burden-paired kind (esim_ensemble_begin_burden_paired, under
-// ROWS_PAIRED), both marked by Rows::burden, which esim_ensemble_fold dispatches on (fold_beds).  The kernels:
+// (esim_ensemble_begin_burden_series: the buffers and the reader of the settings kind) and the burden-paired kind
+// (esim_ensemble_begin_burden_paired: those of the paired kind), which esim_ensemble_fold folds with fold_beds.  The kernels:
 // esim_kernels_beds.h; every launch of the family is in this file.  The checks, the run's front half and the column key are
 // those of esim_host_burden.h.  A run that never asks allocates nothing here.
 namespace {
@@ -79,14 +79,15 @@ bool beds_rows_inside(const esim_ctx_impl *c, uint32_t first_step, uint32_t n_ro
 // the accumulators were allocated under, and the wait -- the replay's plane goes when the call returns.
 int fold_beds(esim_ctx_impl *c)
 {
-    Ensemble::Rows &r = c->ens.rows;
+    Rows &r = c->ens.rows;
+    const Ensemble::Par &par = c->ens.par;
     const std::string who = "esim_ensemble_fold";
     const int where = c->ens.where;
-    const bool paired = r.kind == Ensemble::ROWS_PAIRED;
+    const bool paired = c->ens.kind == Ensemble::ENS_BURDEN_PAIRED;
     if (int rc = burden_ready(c, who)) return rc;
     if (curve_cols(c, where) != r.n_cols || (where == ESIM_BY_GROUP && !c->grp.lab)) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
     if (paired && !c->beds.held) return fail(c, ESIM_ESTATE, who + ": no burden baseline is kept (esim_burden_baseline_keep)");
-    if (!beds_rows_inside(c, r.first, r.n_rows, r.stride, paired))
+    if (!beds_rows_inside(c, par.first, r.n_rows, par.stride, paired))
         return fail(c, ESIM_ERANGE, paired ? who + ": rows outside the steps of the burden baseline or of the run as it stands" : who + ": rows outside the steps run so far");
     DevTmp<uint32_t> vax;
     BurdenRun run;
@@ -96,16 +97,11 @@ int fold_beds(esim_ctx_impl *c)
     const uint64_t cells = (uint64_t)r.n_rows * r.n_cols;
     const uint32_t fold_grid = grid_capped(c, (size_t)(cells >> 2), TPB, 2048);
     hipError_t e = enqueue_beds_collect(c, run, vax.p, cur.dev());
-    if (e == hipSuccess && paired) e = enqueue_beds_rows(c, beds_kept(c), c->beds.n, c->beds.steps, where, r.what, r.first, r.n_rows, r.stride, r.cumulative, r.p0);
-    if (e == hipSuccess) e = enqueue_beds_rows(c, cur.dev(), run.log_len, run.t_done, where, r.what, r.first, r.n_rows, r.stride, paired && r.cumulative, paired ? r.p1 : r.p0);
+    if (e == hipSuccess && paired) e = enqueue_beds_rows(c, beds_kept(c), c->beds.n, c->beds.steps, where, par.burden_what, par.first, r.n_rows, par.stride, par.cumulative, r.p0);
+    if (e == hipSuccess) e = enqueue_beds_rows(c, cur.dev(), run.log_len, run.t_done, where, par.burden_what, par.first, r.n_rows, par.stride, par.cumulative, paired ? r.p1 : r.p0);
     if (e == hipSuccess) {
-        if (paired) {
-            RatioAcc a;
-            a.defined = r.defined; a.hit = r.hit; a.members = r.members; a.sum_c = r.sum; a.sum_o = r.sum_o; a.sq_c = r.sumsq; a.sq_o = r.sumsq_o; a.cross = r.cross;
-            hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.min_averted, a);
-        } else {
-            hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
-        }
+        if (paired) hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, par.min_defined, par.min_averted, ratio_acc(r));
+        else hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(fold_grid), dim3(TPB), 0, c->stream, r.p0, cells, par.min_hit, r.hit, r.sum, r.sumsq, r.members);
         e = members_keep(c);
         if (e == hipSuccess) e = hipGetLastError();
     }
@@ -287,12 +283,9 @@ extern "C" int esim_ensemble_begin_burden_series(esim_ctx *ctx, int where, int w
     if (first_step == 0u) return fail(c, ESIM_ERANGE, who + ": first_step is 1-based");
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint32_t cols = curve_cols(c, where);
-    if (int rc = ensrows_begin(c, who, Ensemble::ROWS_SETTINGS, n_rows, cols)) return rc;
-    Ensemble::Rows &r = c->ens.rows;
-    r.burden = true; r.what = what; r.first = first_step; r.stride = stride; r.min = min_count; r.cumulative = false;
-    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.burden_what = what; par.first = first_step; par.stride = stride; par.min_hit = min_count;
+    return ens_begin(c, who, Ensemble::ENS_BURDEN_SERIES, where, n_rows, cols, par);
 }
 
 extern "C" int esim_ensemble_begin_burden_paired(esim_ctx *ctx, int where, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, int cumulative,
@@ -306,10 +299,7 @@ extern "C" int esim_ensemble_begin_burden_paired(esim_ctx *ctx, int where, int w
     if (first_step == 0u) return fail(c, ESIM_ERANGE, who + ": first_step is 1-based");
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint32_t cols = curve_cols(c, where);
-    if (int rc = ensrows_begin(c, who, Ensemble::ROWS_PAIRED, n_rows, cols)) return rc;
-    Ensemble::Rows &r = c->ens.rows;
-    r.burden = true; r.what = what; r.first = first_step; r.stride = stride; r.min = min_baseline; r.min_averted = min_averted; r.cumulative = cumulative != 0;
-    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.burden_what = what; par.first = first_step; par.stride = stride; par.min_defined = min_baseline; par.min_averted = min_averted; par.cumulative = cumulative != 0;
+    return ens_begin(c, who, Ensemble::ENS_BURDEN_PAIRED, where, n_rows, cols, par);
 }

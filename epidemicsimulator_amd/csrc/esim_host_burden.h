@@ -94,15 +94,15 @@ int burden_enqueue(esim_ctx_impl *c, const std::string &who, const CurveSpec &s,
 
 const char *BURDEN_WHERE = ": `where` must be ESIM_BY_ALL, ESIM_AREA_HOME or ESIM_BY_GROUP";
 
-// One member's occupancy summary folded into the accumulators of the peaks kind (fold_peaks dispatches here).
+// One member's occupancy summary folded into the accumulators of the burden-peaks kind.
 int fold_burden_peaks(esim_ctx_impl *c)
 {
-    Ensemble::Rows &r = c->ens.rows;
+    const Ensemble::Par &par = c->ens.par;
     const std::string who = "esim_ensemble_fold";
-    const CurveSpec s = { c->ens.where, CURVE_MASK_I, r.first, r.last, r.threshold };
+    const CurveSpec s = { c->ens.where, CURVE_MASK_I, par.first, par.last, par.threshold };
     if (int rc = burden_ready(c, who)) return rc;
     if (int rc = curve_check(c, who, s)) return rc;
-    if (curve_cols(c, s.where) != r.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
+    if (curve_cols(c, s.where) != c->ens.rows.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
     CurveWork w;
     BurdenCounts n;
     if (int rc = burden_enqueue(c, who, s, &w, &n)) return rc;
@@ -280,5 +280,5 @@ extern "C" int esim_ensemble_begin_burden_peaks(esim_ctx *ctx, int where, uint32
     const CurveSpec s = { where, CURVE_MASK_I, first_step, last_step, threshold };
     if (int rc = burden_ready(c, who)) return rc;
     if (int rc = curve_check(c, who, s)) return rc;
-    return peaks_begin(c, who, s, min_peak, true);
+    return peaks_kind_begin(c, who, Ensemble::ENS_BURDEN_PEAKS, s, min_peak);
 }

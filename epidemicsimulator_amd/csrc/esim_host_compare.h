@@ -65,25 +65,24 @@ bool rows_inside(const esim_ctx_impl *c, uint32_t first_step, uint32_t n_rows, u
 // device memory, the rows of both runs into the kept planes, the fold kernel.
 int fold_paired(esim_ctx_impl *c)
 {
-    Ensemble::Rows &r = c->ens.rows;
+    Rows &r = c->ens.rows;
+    const Ensemble::Par &par = c->ens.par;
     const std::string who = "esim_ensemble_fold";
     const int where = c->ens.where;
     if (int rc = compare_check(c, who)) return rc;
     if (where == ESIM_BY_GROUP && (!c->grp.lab || c->grp.n != r.n_cols)) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
     if (!c->base.held) return fail(c, ESIM_ESTATE, who + ": no baseline is kept (esim_baseline_keep)");
-    if (!rows_inside(c, r.first, r.n_rows, r.stride)) return fail(c, ESIM_ERANGE, who + ": rows outside the steps of the baseline or of the run as it stands");
+    if (!rows_inside(c, par.first, r.n_rows, par.stride)) return fail(c, ESIM_ERANGE, who + ": rows outside the steps of the baseline or of the run as it stands");
     HIP_TRY(c, hipSetDevice(c->P.device));
     uint32_t log_len = 0;
     if (int rc = compare_wait(c, &log_len)) return rc;
     DevTmp<uint32_t> cur;
     if (cur.alloc(c->d.n) != hipSuccess) { (void)hipGetLastError(); return fail(c, ESIM_ENOMEM, who + ": no device memory for the exposure steps (4 B per citizen)"); }
     hipError_t e = enqueue_plane(c, log_len, cur.p);
-    if (e == hipSuccess) e = enqueue_compare_rows(c, where, r.first, r.n_rows, r.stride, r.cumulative, r.n_cols, cur.p, r.p0, r.p1);
+    if (e == hipSuccess) e = enqueue_compare_rows(c, where, par.first, r.n_rows, par.stride, par.cumulative, r.n_cols, cur.p, r.p0, r.p1);
     if (e == hipSuccess) {
-        RatioAcc a;
-        a.defined = r.defined; a.hit = r.hit; a.members = r.members; a.sum_c = r.sum; a.sum_o = r.sum_o; a.sq_c = r.sumsq; a.sq_o = r.sumsq_o; a.cross = r.cross;
         const uint64_t cells = (uint64_t)r.n_rows * r.n_cols;
-        hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, r.min, r.min_averted, a);
+        hipLaunchKernelGGL(k_ensemble_fold_paired, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, cells, par.min_defined, par.min_averted, ratio_acc(r));
         e = members_keep(c);
         if (e == hipSuccess) e = hipGetLastError();
     }
@@ -226,18 +225,15 @@ extern "C" int esim_ensemble_begin_paired(esim_ctx *ctx, int where, uint32_t fir
     if (int rc = ensrows_begin_check(c, who, where)) return rc;
     HIP_TRY(c, hipSetDevice(c->P.device));
     const uint32_t cols = compare_cols(c, where);
-    if (int rc = ensrows_begin(c, who, Ensemble::ROWS_PAIRED, n_rows, cols)) return rc;
-    Ensemble::Rows &r = c->ens.rows;
-    r.first = first_step; r.stride = stride; r.min = min_baseline; r.min_averted = min_averted; r.cumulative = cumulative != 0;
-    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.first = first_step; par.stride = stride; par.min_defined = min_baseline; par.min_averted = min_averted; par.cumulative = cumulative != 0;
+    return ens_begin(c, who, Ensemble::ENS_PAIRED, where, n_rows, cols, par);
 }
 
 extern "C" int esim_ensemble_read_paired(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *defined, uint32_t *hit,
                                          uint64_t *sum_baseline, uint64_t *sum_current, uint64_t *sumsq_baseline, uint64_t *sumsq_current, uint64_t *sum_cross)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    return read_two_planes(c, "esim_ensemble_read_paired", Ensemble::ROWS_PAIRED, first_row, n, members, defined, hit,
-                           sum_baseline, sum_current, sumsq_baseline, sumsq_current, sum_cross);
+    return ens_read(c, READ_PAIRED, first_row, n, members, { { defined, &Rows::defined }, { hit, &Rows::hit } },
+                    { { sum_baseline, &Rows::sum }, { sum_current, &Rows::sum_o }, { sumsq_baseline, &Rows::sumsq }, { sumsq_current, &Rows::sumsq_o }, { sum_cross, &Rows::cross } });
 }

@@ -69,45 +69,44 @@ struct RestartStaging {
     hipEvent_t ev = nullptr; bool ev_used = false;
 };
 
-// esim_ensemble_*: accumulators over the members of an ensemble, [n_areas] each (nullptr before the first esim_ensemble_begin).
+// esim_ensemble_*: accumulators over the members of an ensemble, on the device.  One kind is in force at a time (`kind`; the table
+// of esim_host_ensemble.h says per kind which buffers of `rows` it owns, which reader reads it and what is kept of a member;
+// DESIGN 34), begun by ens_begin, which assigns every field below but `store` and `folds` -- nothing survives from the kind
+// before.  where, n: the column key and the columns (n_areas, n_groups by group, four settings, one); valid == false: the labels
+// a kind by group was begun for are gone.
 struct Ensemble {
-    uint32_t *hit = nullptr, *members = nullptr;
-    unsigned long long *sum = nullptr, *sumsq = nullptr;
-    int where = ESIM_AREA_HOME; uint32_t mask = 0, min = 0;
-    bool arrival = false; uint32_t horizon = 0;   // esim_ensemble_begin_arrival: a member contributes its arrival step, reached = arrival <= horizon
-    uint32_t n = 0; bool valid = false;           // entries in use (n_areas, or n_groups by group); false: the labels they were begun for are gone
-    // esim_ensemble_begin_series: accumulators of their own, [n_rows][n_cols] each, beside the row plane(s) the series engine
-    // writes a member's rows into and the engine's small temporaries -- all kept from the begin on, so that a fold allocates
-    // nothing proportional to rows x columns (the 4 B per citizen of the vaccination replay: at the first fold that needs them).
-    // series == true: this kind is in force (where, n and valid as for the other two).
-    // esim_ensemble_begin_settings and esim_ensemble_begin_reproduction (esim_host_ensrows.h) are kinds of the same family:
-    // rows.kind tells them apart.  The settings kind keeps hit, sum, sumsq and plane 0 only; the reproduction kind keeps hit,
-    // sum and sumsq for the cases, both planes (cases, offspring) and the four accumulators below.
-    // esim_ensemble_begin_paired (esim_host_compare.h) is the fourth: the reproduction kind's accumulators over the event rows of
-    // the kept baseline (plane 0) and of the run as it stands (plane 1).
-    // esim_ensemble_begin_peaks (esim_host_curves.h) is the fifth: one row of columns, no kept plane -- a member's summary of its
-    // curves is computed in temporary memory --, two counters and six sums: the peak in sum / sumsq, its step in sum_o / sumsq_o,
-    // the duration in sum_d / sumsq_d.
-    enum { ROWS_SERIES = 0, ROWS_SETTINGS = 1, ROWS_REPRODUCTION = 2, ROWS_PAIRED = 3, ROWS_PEAKS = 4 };
+    enum Kind { ENS_NONE = 0, ENS_CENSUS, ENS_ARRIVAL, ENS_SERIES, ENS_SETTINGS, ENS_REPRODUCTION, ENS_PAIRED, ENS_PEAKS, ENS_BURDEN_PEAKS, ENS_BURDEN_SERIES,
+                ENS_BURDEN_PAIRED, ENS_KINDS };
+    Kind kind = ENS_NONE;                         // ENS_NONE: no begin since the upload, and no buffer below is allocated
+    int where = ESIM_AREA_HOME; uint32_t n = 0; bool valid = false;
+    // The buffers, [n_rows][n_cols] cells each where the kind owns them (the census and the arrival kind: one row): the counters
+    // and sums a fold adds to, the row plane(s) a fold leaves a member's rows in, and the series engine's small temporaries -- all
+    // kept from the begin on, so that a fold allocates nothing proportional to rows x columns.  vax: the 4 B per citizen of the
+    // vaccination replay, allocated by the first fold of the series kind that needs them and carried from begin to begin.
     struct Rows {
-        uint32_t *hit = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
-        unsigned long long *sum = nullptr, *sumsq = nullptr;
+        uint32_t *hit = nullptr, *defined = nullptr, *members = nullptr, *p0 = nullptr, *p1 = nullptr, *occ = nullptr, *vax = nullptr;
+        unsigned long long *sum = nullptr, *sumsq = nullptr;                         // of the value: cases, count, peak; baseline or cohort size
+        unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // of the second plane (offspring, current run) and of the product; peaks: of the peak's step
+        unsigned long long *sum_d = nullptr, *sumsq_d = nullptr;                     // peaks: of the duration
         uint8_t *aw = nullptr;
-        int what = 0; uint32_t first = 0, n_rows = 0, stride = 0, min = 0, n_cols = 0;
-        bool two = false;                         // p1 is allocated: status rows by the area stood in, or the offspring plane
-        int kind = ROWS_SERIES;
-        uint32_t mask = 0;                        // ROWS_SETTINGS: the setting mask
-        uint32_t r_num = 0, r_den = 0;            // ROWS_REPRODUCTION: hit where offspring / cases >= r_num / r_den (min: the smallest cohort)
-        uint32_t *defined = nullptr;              // ROWS_REPRODUCTION: members with a cohort in the cell
-        unsigned long long *sum_o = nullptr, *sumsq_o = nullptr, *cross = nullptr;   // ... sums of offspring, offspring^2, cases * offspring
-        uint32_t last = 0, threshold = 0;         // ROWS_PEAKS: the window [first, last], the threshold of the duration (mask: the statuses, min: min_peak)
-        unsigned long long *sum_d = nullptr, *sumsq_d = nullptr;   // ... sums of the duration and of its square
-        bool burden = false;                      // ... the curve a fold summarises: bed occupancy (esim_ensemble_begin_burden_peaks) instead of a status;
-                                                  // under ROWS_SETTINGS / ROWS_PAIRED: a fold makes the rows (what, cumulative) from lists of admitted cases
-                                                  // (esim_ensemble_begin_burden_series / _burden_paired, esim_host_beds.h)
-        uint32_t min_averted = 0; bool cumulative = false;   // ROWS_PAIRED: hit where baseline - current >= min_averted (min: the smallest baseline count); rows summed up
+        uint32_t n_rows = 0, n_cols = 0;
+        bool two = false;                         // the series kind: p1 is allocated too (status rows by the area stood in)
     } rows;
-    bool series = false;
+    // What the begin in force was given, under one name per meaning; a begin assigns all of it (the fields of other kinds: 0).
+    struct Par {
+        uint32_t status_mask = 0;                 // census, peaks: the statuses counted
+        uint32_t setting_mask = 0;                // settings
+        uint32_t horizon = 0;                     // arrival: reached = arrival step <= horizon
+        int status = 0;                           // series: the status of the rows, or SERIES_EVENTS
+        int burden_what = 0;                      // burden series, burden paired: ESIM_BURDEN_*
+        uint32_t first = 0, stride = 0;           // the kinds over rows: row i starts at step first + i * stride
+        uint32_t last = 0, threshold = 0;         // peaks, burden peaks: the window [first, last], the threshold of the duration
+        uint32_t min_hit = 0;                     // hit where the value >= this: min_cases, min_count, min_peak
+        uint32_t min_defined = 0;                 // defined where the first plane >= this: min_cohort, min_baseline
+        uint32_t r_num = 0, r_den = 0;            // reproduction: hit where offspring / cases >= r_num / r_den
+        uint32_t min_averted = 0;                 // paired, burden paired: hit where baseline - current >= this
+        bool cumulative = false;                  // ... rows summed up from `first` on
+    } par;
     // esim_ensemble_keep_members (esim_host_members.h): the members' values beside the accumulators in force, [capacity][n_rows *
     // n_cols] keys (signed values with the top bit flipped), `kept` slots filled in the order of the folds.  planes == nullptr: no
     // store.  folds: the members folded since the begin, kept or not (a store may only be opened in front of the first).

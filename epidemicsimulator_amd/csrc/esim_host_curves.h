@@ -123,16 +123,14 @@ extern "C" int esim_curve_summary(esim_ctx *ctx, int where, uint32_t status_mask
 }
 
 namespace {
-int fold_burden_peaks(esim_ctx_impl *c);   // (esim_host_burden.h: a member's occupancy curve, where Rows::burden says so)
-
 // Behind curve_enqueue: the member's tables in w folded into the accumulators, kept where members are kept, and the wait.
 int fold_peaks_tables(esim_ctx_impl *c, const std::string &who, CurveWork &w)
 {
-    Ensemble::Rows &r = c->ens.rows;
+    const Rows &r = c->ens.rows;
     PeakAcc a;
     a.defined = r.defined; a.hit = r.hit; a.members = r.members;
     a.sum_peak = r.sum; a.sq_peak = r.sumsq; a.sum_step = r.sum_o; a.sq_step = r.sumsq_o; a.sum_dur = r.sum_d; a.sq_dur = r.sumsq_d;
-    hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_capped(c, r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, r.min, a);
+    hipLaunchKernelGGL(k_ensemble_fold_peaks, dim3(grid_capped(c, r.n_cols, TPB, 2048)), dim3(TPB), 0, c->stream, w.t, r.n_cols, c->ens.par.min_hit, a);
     hipError_t e = members_keep(c, &w.t);
     if (e == hipSuccess) e = hipGetLastError();
     const hipError_t es = hipStreamSynchronize(c->stream);                   // (the temporary tables go when the call returns)
@@ -144,51 +142,24 @@ int fold_peaks_tables(esim_ctx_impl *c, const std::string &who, CurveWork &w)
 // One member folded into the accumulators of the peaks kind: its summary in temporary memory, the fold kernel, the wait.
 int fold_peaks(esim_ctx_impl *c)
 {
-    Ensemble::Rows &r = c->ens.rows;
-    if (r.burden) return fold_burden_peaks(c);
+    const Ensemble::Par &par = c->ens.par;
     const std::string who = "esim_ensemble_fold";
-    const CurveSpec s = { c->ens.where, r.mask, r.first, r.last, r.threshold };
+    const CurveSpec s = { c->ens.where, par.status_mask, par.first, par.last, par.threshold };
     if (int rc = curve_check(c, who, s)) return rc;
-    if (curve_cols(c, s.where) != r.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
+    if (curve_cols(c, s.where) != c->ens.rows.n_cols) return fail(c, ESIM_ESTATE, who + ": the accumulators were begun for other columns");
     CurveWork w;
     if (int rc = curve_enqueue(c, who, s, &w)) return rc;
     return fold_peaks_tables(c, who, w);
 }
 
-// The begin of the peaks kind behind its caller's checks: the accumulators allocated or reused and zeroed.  burden: a fold
-// summarises the occupancy curve of esim_burden_summary instead of the status curve of the mask.
-int peaks_begin(esim_ctx_impl *c, const std::string &who, const CurveSpec &s, uint32_t min_peak, bool burden)
+// The begin of the two peaks kinds behind their callers' checks: one row of columns; a fold of `kind` summarises the status curve
+// of the mask, or the occupancy curve of esim_burden_summary (esim_host_burden.h).
+int peaks_kind_begin(esim_ctx_impl *c, const std::string &who, Ensemble::Kind kind, const CurveSpec &s, uint32_t min_peak)
 {
-    const int where = s.where;
     HIP_TRY(c, hipSetDevice(c->P.device));
-    const uint32_t cols = curve_cols(c, where);
-    Ensemble::Rows &old = c->ens.rows;
-    if (!old.hit || old.kind != Ensemble::ROWS_PEAKS || old.n_cols != cols) {
-        // another kind or shape: the new one is allocated before the old one goes, so that a refusal leaves everything as it was
-        Ensemble::Rows r;
-        int rc;
-        if ((rc = dev_alloc(c, &r.hit, cols)) || (rc = dev_alloc(c, &r.defined, cols)) || (rc = dev_alloc(c, &r.members, 1)) || (rc = dev_alloc(c, &r.sum, cols)) ||
-            (rc = dev_alloc(c, &r.sumsq, cols)) || (rc = dev_alloc(c, &r.sum_o, cols)) || (rc = dev_alloc(c, &r.sumsq_o, cols)) || (rc = dev_alloc(c, &r.sum_d, cols)) ||
-            (rc = dev_alloc(c, &r.sumsq_d, cols))) {
-            (void)hipGetLastError();
-            rows_free(c, &r);
-            return fail(c, ESIM_ENOMEM, who + ": no device memory for the accumulators (56 B per column)");
-        }
-        if (old.hit) HIP_TRY(c, hipStreamSynchronize(c->stream));    // (a fold on the stream may still be using the old ones)
-        r.vax = old.vax; old.vax = nullptr;                          // (the series kind's 4 B per citizen, whatever the shape)
-        rows_free(c, &old);
-        old = r;
-    }
-    Ensemble::Rows &r = c->ens.rows;
-    r.kind = Ensemble::ROWS_PEAKS; r.n_rows = 1u; r.n_cols = cols; r.two = false;
-    r.mask = s.mask; r.first = s.first; r.last = s.last; r.threshold = s.threshold; r.min = min_peak; r.burden = burden;
-    for (uint32_t *p : { r.hit, r.defined }) HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(uint32_t) * std::max<size_t>(1, cols), c->stream));
-    for (unsigned long long *p : { r.sum, r.sumsq, r.sum_o, r.sumsq_o, r.sum_d, r.sumsq_d })
-        HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(unsigned long long) * std::max<size_t>(1, cols), c->stream));
-    HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
-    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.status_mask = s.mask; par.first = s.first; par.last = s.last; par.threshold = s.threshold; par.min_hit = min_peak;
+    return ens_begin(c, who, kind, s.where, 1u, curve_cols(c, s.where), par);
 }
 }  // namespace
 
@@ -199,28 +170,14 @@ extern "C" int esim_ensemble_begin_peaks(esim_ctx *ctx, int where, uint32_t stat
     if (min_peak == 0u) return fail(c, ESIM_EINVAL, who + ": min_peak 0");
     const CurveSpec s = { where, status_mask, first_step, last_step, threshold };
     if (int rc = curve_check(c, who, s)) return rc;
-    return peaks_begin(c, who, s, min_peak, false);
+    return peaks_kind_begin(c, who, Ensemble::ENS_PEAKS, s, min_peak);
 }
 
 extern "C" int esim_ensemble_read_peaks(esim_ctx *ctx, uint32_t *members, uint32_t *defined, uint32_t *hit, uint64_t *sum_peak, uint64_t *sumsq_peak,
                                         uint64_t *sum_step, uint64_t *sumsq_step, uint64_t *sum_duration, uint64_t *sumsq_duration)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    const std::string who = "esim_ensemble_read_peaks";
-    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit || c->ens.rows.kind != Ensemble::ROWS_PEAKS)
-        return fail(c, ESIM_ESTATE, who + ": no population uploaded, or no esim_ensemble_begin_peaks in force since the upload (or, by group, since esim_set_groups)");
-    const Ensemble::Rows &r = c->ens.rows;
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    Ctrl h; int rc;
-    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for whatever is on the stream)
-    const size_t cols = r.n_cols;
-    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const std::pair<uint32_t *, const uint32_t *> words[] = { { defined, r.defined }, { hit, r.hit } };
-    for (const auto &p : words)
-        if (p.first && cols) HIP_TRY(c, hipMemcpy(p.first, p.second, sizeof(uint32_t) * cols, hipMemcpyDeviceToHost));
-    const std::pair<uint64_t *, const unsigned long long *> sums[] = { { sum_peak, r.sum }, { sumsq_peak, r.sumsq }, { sum_step, r.sum_o }, { sumsq_step, r.sumsq_o },
-                                                                       { sum_duration, r.sum_d }, { sumsq_duration, r.sumsq_d } };
-    for (const auto &p : sums)
-        if (p.first && cols) HIP_TRY(c, hipMemcpy(p.first, p.second, sizeof(uint64_t) * cols, hipMemcpyDeviceToHost));
-    return ctrl_error(c, h);
+    return ens_read(c, READ_PEAKS, 0u, 1u, members, { { defined, &Rows::defined }, { hit, &Rows::hit } },
+                    { { sum_peak, &Rows::sum }, { sumsq_peak, &Rows::sumsq }, { sum_step, &Rows::sum_o }, { sumsq_step, &Rows::sumsq_o }, { sum_duration, &Rows::sum_d },
+                      { sumsq_duration, &Rows::sumsq_d } });
 }

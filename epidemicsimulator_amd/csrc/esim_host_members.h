@@ -34,22 +34,23 @@ hipError_t members_keep(esim_ctx_impl *c, const CurveTabs *t = nullptr)
     uint32_t *slot = s.planes + (size_t)s.kept * cells;
     s.kept += 1u;
     if (!cells) return hipSuccess;
-    if (!e.series) {
+    const Rows &r = e.rows;
+    switch (e.kind) {
+    case Ensemble::ENS_CENSUS: case Ensemble::ENS_ARRIVAL: {
         const uint32_t grid = grid_capped(c, cells, TPB, 2048);
-        if (e.arrival) hipLaunchKernelGGL(k_members_keep_arrival, dim3(grid), dim3(TPB), 0, c->stream, c->arrival, e.n, e.horizon, slot);
-        else hipLaunchKernelGGL(k_members_keep_census, dim3(grid), dim3(TPB), 0, c->stream, e.where == ESIM_BY_GROUP ? c->grp.cnt : c->area_cnt, e.n, e.mask, slot);
+        if (e.kind == Ensemble::ENS_ARRIVAL) hipLaunchKernelGGL(k_members_keep_arrival, dim3(grid), dim3(TPB), 0, c->stream, c->arrival, e.n, e.par.horizon, slot);
+        else hipLaunchKernelGGL(k_members_keep_census, dim3(grid), dim3(TPB), 0, c->stream, e.where == ESIM_BY_GROUP ? c->grp.cnt : c->area_cnt, e.n, e.par.status_mask, slot);
         return hipGetLastError();
     }
-    const Ensemble::Rows &r = e.rows;
-    if (r.kind == Ensemble::ROWS_PAIRED) {
+    case Ensemble::ENS_PAIRED: case Ensemble::ENS_BURDEN_PAIRED:
         hipLaunchKernelGGL(k_members_keep_paired, dim3(grid_capped(c, cells, TPB, 2048)), dim3(TPB), 0, c->stream, r.p0, r.p1, (uint64_t)cells, slot);
         return hipGetLastError();
-    }
-    if (r.kind == Ensemble::ROWS_PEAKS) {
+    case Ensemble::ENS_PEAKS: case Ensemble::ENS_BURDEN_PEAKS:
         hipLaunchKernelGGL(k_members_keep_peaks, dim3(grid_capped(c, cells, TPB, 2048)), dim3(TPB), 0, c->stream, *t, r.n_cols, s.what, slot);
         return hipGetLastError();
+    default:                                     // (the series, the settings and the burden-series kind: plane 0 as it is)
+        return hipMemcpyAsync(slot, r.p0, sizeof(uint32_t) * cells, hipMemcpyDeviceToDevice, c->stream);
     }
-    return hipMemcpyAsync(slot, r.p0, sizeof(uint32_t) * cells, hipMemcpyDeviceToDevice, c->stream);
 }
 
 // What the three reads refuse alike: no store or nothing kept, rows outside it.
@@ -69,12 +70,15 @@ MemberSkip members_skip(const esim_ctx_impl *c)
 {
     const Ensemble &e = c->ens;
     MemberSkip k = { nullptr, 0u, nullptr };
-    if (!e.series) { if (e.arrival) k.never = e.hit; else k.zero = e.sum; return k; }
-    const Ensemble::Rows &r = e.rows;
-    if (r.kind == Ensemble::ROWS_SERIES || r.kind == Ensemble::ROWS_SETTINGS) k.zero = r.sum;
-    if (r.kind == Ensemble::ROWS_PEAKS) {
+    const Rows &r = e.rows;
+    switch (e.kind) {
+    case Ensemble::ENS_ARRIVAL: k.never = r.hit; break;
+    case Ensemble::ENS_CENSUS: case Ensemble::ENS_SERIES: case Ensemble::ENS_SETTINGS: case Ensemble::ENS_BURDEN_SERIES: k.zero = r.sum; break;
+    case Ensemble::ENS_PEAKS: case Ensemble::ENS_BURDEN_PEAKS:
         if (e.store.what == ESIM_KEEP_PEAK_STEP) k.never = r.defined;
         else k.zero = e.store.what == ESIM_KEEP_DURATION ? r.sum_d : r.sum;
+        break;
+    default: break;                              // (a difference of 0 says nothing about the sums of the paired kinds)
     }
     return k;
 }
@@ -100,19 +104,17 @@ extern "C" int esim_ensemble_keep_members(esim_ctx *ctx, uint32_t capacity, int 
     if (capacity == 0u || capacity > (uint32_t)ESIM_MEMBERS_MAX || what < ESIM_KEEP_VALUE || what > ESIM_KEEP_DURATION)
         return fail(c, ESIM_EINVAL, who + ": capacity must be in 1..ESIM_MEMBERS_MAX (256), `what` one of ESIM_KEEP_*");
     Ensemble &e = c->ens;
-    if (!c->uploaded || !e.valid || !(e.series ? e.rows.hit : e.hit))
+    const int keep = ENS_KIND[e.kind].keep;
+    if (!c->uploaded || !e.valid || e.kind == Ensemble::ENS_NONE)
         return fail(c, ESIM_ESTATE, who + ": no population uploaded, or no begin in force since the upload (or, by group, since esim_set_groups)");
-    if (e.series && e.rows.kind == Ensemble::ROWS_REPRODUCTION)
-        return fail(c, ESIM_ESTATE, who + ": the reproduction kind is in force (a ratio per cell is not kept)");
+    if (keep == KEEP_NONE) return fail(c, ESIM_ESTATE, who + ": the reproduction kind is in force (a ratio per cell is not kept)");
     if (e.folds) return fail(c, ESIM_ESTATE, who + ": a member has been folded since the begin (keep in front of the first fold)");
-    const bool peaks = e.series && e.rows.kind == Ensemble::ROWS_PEAKS;
-    if (what != ESIM_KEEP_VALUE && !peaks) return fail(c, ESIM_EINVAL, who + ": only the peaks kind has a `what` beside ESIM_KEEP_VALUE");
+    if (what != ESIM_KEEP_VALUE && keep != KEEP_SUMMARY) return fail(c, ESIM_EINVAL, who + ": only the peaks kind has a `what` beside ESIM_KEEP_VALUE");
     HIP_TRY(c, hipSetDevice(c->P.device));
     Ensemble::Store s;
-    s.capacity = capacity; s.what = what;
-    s.n_rows = e.series ? e.rows.n_rows : 1u; s.n_cols = e.series ? e.rows.n_cols : e.n;
-    s.is_signed = e.series && e.rows.kind == Ensemble::ROWS_PAIRED;
-    s.has_never = (!e.series && e.arrival) || (peaks && what == ESIM_KEEP_PEAK_STEP);
+    s.capacity = capacity; s.what = what; s.n_rows = e.rows.n_rows; s.n_cols = e.rows.n_cols;
+    s.is_signed = keep == KEEP_SIGNED;
+    s.has_never = keep == KEEP_NEVER || (keep == KEEP_SUMMARY && what == ESIM_KEEP_PEAK_STEP);
     const size_t cells = (size_t)s.n_rows * s.n_cols;
     if (dev_alloc(c, &s.planes, (size_t)capacity * cells)) {
         (void)hipGetLastError();

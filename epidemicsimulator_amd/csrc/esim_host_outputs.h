@@ -117,27 +117,6 @@ int arrival_check(esim_ctx_impl *c, int where, const std::string &who)
     return ESIM_OK;
 }
 
-// The accumulators allocated at the first begin -- one allocation serves both kinds: the areas, or up to ESIM_MAX_GROUPS
-// groups -- and zeroed on the stream.
-int ensemble_zero(esim_ctx_impl *c)
-{
-    const size_t na = std::max<size_t>(ESIM_MAX_GROUPS, c->d.n_areas);
-    if (!c->ens.hit) {
-        int rc;
-        uint32_t *hit = nullptr, *mem = nullptr; unsigned long long *sum = nullptr, *sq = nullptr;
-        if ((rc = dev_alloc(c, &hit, na)) || (rc = dev_alloc(c, &sum, na)) || (rc = dev_alloc(c, &sq, na)) || (rc = dev_alloc(c, &mem, 1))) {
-            dev_free(c, hit); dev_free(c, sum); dev_free(c, sq); dev_free(c, mem);
-            return rc;
-        }
-        c->ens.hit = hit; c->ens.sum = sum; c->ens.sumsq = sq; c->ens.members = mem;
-    }
-    HIP_TRY(c, hipMemsetAsync(c->ens.hit, 0, sizeof(uint32_t) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.sum, 0, sizeof(unsigned long long) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.sumsq, 0, sizeof(unsigned long long) * na, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->ens.members, 0, sizeof(uint32_t), c->stream));
-    return ESIM_OK;
-}
-
 // What the series derive from the records of the steps run (rec[1 .. t_done]): the at-work bit after the schedule arm of every
 // step (citizen.rs:176-206: the arm of step s runs iff no lockdown was in force, i.e. the record of step s - 1 has none) and
 // the steps at which it changes; the step that started the vaccination programme (0: none) and the first one that vaccinated
@@ -299,41 +278,57 @@ SeriesSpec fold_spec(int where, int what)
     return {who, "status", where == ESIM_AREA_CURRENT ? KEY_STOOD : KEY_HOME, (uint32_t)what, false, false};          // esim_area_status_series
 }
 
-// The accumulators and kept buffers of a series kind back to the device (nothing may still be using them).
-void rows_free(esim_ctx_impl *c, Ensemble::Rows *r)
-{
-    for (void *q : { (void *)r->hit, (void *)r->members, (void *)r->p0, (void *)r->p1, (void *)r->occ, (void *)r->vax, (void *)r->sum, (void *)r->sumsq, (void *)r->aw,
-                     (void *)r->defined, (void *)r->sum_o, (void *)r->sumsq_o, (void *)r->cross, (void *)r->sum_d, (void *)r->sumsq_d }) dev_free(c, q);
-    *r = Ensemble::Rows();
-}
-
 // One member's rows, as the engine leaves them in the kept planes, folded into the accumulators of a series kind.
 int fold_series(esim_ctx_impl *c)
 {
-    Ensemble::Rows &r = c->ens.rows;
-    const SeriesSpec s = fold_spec(c->ens.where, r.what);
+    Rows &r = c->ens.rows;
+    const Ensemble::Par &par = c->ens.par;
+    const SeriesSpec s = fold_spec(c->ens.where, par.status);
     SeriesPlan p;
-    if (int rc = series_plan(c, s, r.first, r.n_rows, r.stride, &p)) return rc;
+    if (int rc = series_plan(c, s, par.first, r.n_rows, par.stride, &p)) return rc;
     if (p.cols != r.n_cols || p.two != r.two) return fail(c, ESIM_ESTATE, "esim_ensemble_fold: the accumulators were begun for other columns");
     if (p.replay && !r.vax) {
         if (int rc = dev_alloc(c, &r.vax, c->d.n)) { (void)hipGetLastError(); return rc; }
     }
     if (p.stood) std::memcpy(c->pin.aw, p.shape.aw.data(), p.shape.aw.size());   // (the stream is idle behind series_plan's wait)
     const SeriesBufs b = { r.p0, r.p1, r.occ, nullptr, r.vax, r.aw, c->pin.aw };
-    const hipError_t e = series_enqueue(c, s, r.first, r.n_rows, r.stride, p, b);
+    const hipError_t e = series_enqueue(c, s, par.first, r.n_rows, par.stride, p, b);
     if (e != hipSuccess) return fail(c, ESIM_ENODEVICE, std::string("esim_ensemble_fold: ") + hipGetErrorString(e));
     const uint64_t cells = (uint64_t)p.words;
     hipLaunchKernelGGL(k_ensemble_fold_rows, dim3(grid_capped(c, (size_t)(cells >> 2), TPB, 2048)), dim3(TPB), 0, c->stream,
-                       r.p0, cells, r.min, r.hit, r.sum, r.sumsq, r.members);
+                       r.p0, cells, par.min_hit, r.hit, r.sum, r.sumsq, r.members);
     HIP_TRY(c, members_keep(c));
     HIP_TRY(c, hipGetLastError());
     return ESIM_OK;
 }
 
-int fold_transmission(esim_ctx_impl *c);   // (esim_host_ensrows.h: the settings and the reproduction kind)
-int fold_paired(esim_ctx_impl *c);         // (esim_host_compare.h: the paired kind)
-int fold_peaks(esim_ctx_impl *c);          // (esim_host_curves.h: the peaks kind)
-int fold_beds(esim_ctx_impl *c);           // (esim_host_beds.h: the burden-series and the burden-paired kind, where Rows::burden says so)
+// One member's census, counted where the census calls count it, folded into the one row of the census kind.
+int fold_census(esim_ctx_impl *c)
+{
+    const Ensemble &e = c->ens;
+    const bool by_group = e.where == ESIM_BY_GROUP;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, e.where)) return rc;
+    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(e.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       by_group ? c->grp.cnt : c->area_cnt, e.n, e.par.status_mask, e.par.min_hit, e.rows.hit, e.rows.sum, e.rows.sumsq, e.rows.members);
+    HIP_TRY(c, members_keep(c));
+    HIP_TRY(c, hipGetLastError());
+    return ESIM_OK;
+}
+
+// The same for the arrival kind: a member contributes its arrival steps, reached = arrival <= horizon.
+int fold_arrival(esim_ctx_impl *c)
+{
+    const Ensemble &e = c->ens;
+    HIP_TRY(c, hipSetDevice(c->P.device));
+    if (int rc = enqueue_arrival(c, e.where)) return rc;
+    hipLaunchKernelGGL(k_ensemble_fold_arrival, dim3(grid_for(e.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
+                       c->arrival, e.n, e.par.horizon, e.rows.hit, e.rows.sum, e.rows.sumsq, e.rows.members);
+    HIP_TRY(c, members_keep(c));
+    HIP_TRY(c, hipGetLastError());
+    return ESIM_OK;
+}
+
 void burden_forget(esim_ctx_impl *c);      // (esim_host_burden.h: the severity tables dropped)
 }  // namespace
 
@@ -369,11 +364,9 @@ extern "C" int esim_ensemble_begin(esim_ctx *ctx, int where, uint32_t status_mas
     if (!c->uploaded) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: no population uploaded");
     if (where == ESIM_BY_GROUP && (!c->grp.lab || c->comm.world > 1)) return fail(c, ESIM_ESTATE, "esim_ensemble_begin: by group without labels (esim_set_groups)");
     HIP_TRY(c, hipSetDevice(c->P.device));
-    if (int rc = ensemble_zero(c)) return rc;
-    c->ens.where = where; c->ens.mask = status_mask; c->ens.min = min_cases; c->ens.arrival = false; c->ens.series = false;
-    c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.status_mask = status_mask; par.min_hit = min_cases;
+    return ens_begin(c, "esim_ensemble_begin", Ensemble::ENS_CENSUS, where, 1u, where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas, par);
 }
 
 extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t horizon)
@@ -381,57 +374,15 @@ extern "C" int esim_ensemble_begin_arrival(esim_ctx *ctx, int where, uint32_t ho
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
     if (int rc = arrival_check(c, where, "esim_ensemble_begin_arrival")) return rc;
     HIP_TRY(c, hipSetDevice(c->P.device));
-    if (int rc = ensemble_zero(c)) return rc;
-    c->ens.where = where; c->ens.arrival = true; c->ens.series = false; c->ens.horizon = horizon;
-    c->ens.n = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
-}
-
-extern "C" int esim_ensemble_fold(esim_ctx *ctx)
-{
-    esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens.valid || !(c->ens.series ? c->ens.rows.hit : c->ens.hit))
-        return fail(c, ESIM_ESTATE, "esim_ensemble_fold: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
-    if (int rc = members_full(c)) return rc;
-    if (c->ens.series && c->ens.rows.kind == Ensemble::ROWS_PEAKS) return fold_peaks(c);
-    if (c->ens.series && c->ens.rows.burden) return fold_beds(c);
-    if (c->ens.series) return c->ens.rows.kind == Ensemble::ROWS_SERIES ? fold_series(c) : c->ens.rows.kind == Ensemble::ROWS_PAIRED ? fold_paired(c) : fold_transmission(c);
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    int rc;
-    const bool by_group = c->ens.where == ESIM_BY_GROUP;
-    if (c->ens.arrival) {
-        if ((rc = enqueue_arrival(c, c->ens.where))) return rc;
-        hipLaunchKernelGGL(k_ensemble_fold_arrival, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
-                           c->arrival, c->ens.n, c->ens.horizon, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
-        HIP_TRY(c, members_keep(c));
-        HIP_TRY(c, hipGetLastError());
-        return ESIM_OK;
-    }
-    if ((rc = by_group ? enqueue_group_census(c) : enqueue_area_census(c, c->ens.where))) return rc;
-    hipLaunchKernelGGL(k_ensemble_fold, dim3(grid_for(c->ens.n, TPB, 0xFFFFFFFFu)), dim3(TPB), 0, c->stream,
-                       by_group ? c->grp.cnt : c->area_cnt, c->ens.n, c->ens.mask, c->ens.min, c->ens.hit, c->ens.sum, c->ens.sumsq, c->ens.members);
-    HIP_TRY(c, members_keep(c));
-    HIP_TRY(c, hipGetLastError());
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.horizon = horizon;
+    return ens_begin(c, "esim_ensemble_begin_arrival", Ensemble::ENS_ARRIVAL, where, 1u, where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas, par);
 }
 
 extern "C" int esim_ensemble_read(esim_ctx *ctx, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    if (c->uploaded && c->ens.valid && c->ens.series)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read: the accumulators in force were begun over rows (read them with esim_ensemble_read_series, or with esim_ensemble_read_reproduction those of esim_ensemble_begin_reproduction)");
-    if (!c->uploaded || !c->ens.hit || !c->ens.valid)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read: no population uploaded, or no esim_ensemble_begin since the upload (or, by group, since esim_set_groups)");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    Ctrl h; int rc;
-    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
-    const size_t na = c->ens.n;
-    if (members) HIP_TRY(c, hipMemcpy(members, c->ens.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (hit && na) HIP_TRY(c, hipMemcpy(hit, c->ens.hit, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
-    if (sum && na) HIP_TRY(c, hipMemcpy(sum, c->ens.sum, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
-    if (sumsq && na) HIP_TRY(c, hipMemcpy(sumsq, c->ens.sumsq, sizeof(uint64_t) * na, hipMemcpyDeviceToHost));
-    return ctrl_error(c, h);
+    return ens_read(c, READ_CELLS, 0u, 1u, members, { { hit, &Rows::hit } }, { { sum, &Rows::sum }, { sumsq, &Rows::sumsq } });
 }
 
 // ---- the same over the rows of a series: [n_rows][n_cols] accumulators, a member's rows left on the device ---------------
@@ -448,58 +399,15 @@ extern "C" int esim_ensemble_begin_series(esim_ctx *ctx, int where, int what, ui
     const SeriesSpec s = fold_spec(where, what);
     const uint32_t cols = where == ESIM_BY_GROUP ? c->grp.n : c->d.n_areas;
     const bool two = s.key == KEY_STOOD && s.what != SERIES_EVENTS;
-    const size_t cells = (size_t)n_rows * cols;
-    Ensemble::Rows &old = c->ens.rows;
-    if (!old.hit || old.kind != Ensemble::ROWS_SERIES || old.n_rows != n_rows || old.n_cols != cols || old.two != two) {
-        // another shape: the new one is allocated before the old one goes, so that a refusal leaves everything as it was
-        Ensemble::Rows r;
-        int rc;
-        if (!c->pin.aw) HIP_TRY(c, hipHostMalloc((void **)&c->pin.aw, (size_t)c->cap_steps + 1u, hipHostMallocDefault));
-        if ((rc = dev_alloc(c, &r.hit, cells)) || (rc = dev_alloc(c, &r.sum, cells)) || (rc = dev_alloc(c, &r.sumsq, cells)) || (rc = dev_alloc(c, &r.members, 1)) ||
-            (rc = dev_alloc(c, &r.p0, cells)) || (two && (rc = dev_alloc(c, &r.p1, cells))) || (rc = dev_alloc(c, &r.occ, (size_t)cols * 2u)) ||
-            (rc = dev_alloc(c, &r.aw, (size_t)c->cap_steps + 1u))) {
-            (void)hipGetLastError();
-            rows_free(c, &r);
-            return fail(c, ESIM_ENOMEM, "esim_ensemble_begin_series: no device memory for the accumulators and the row planes (ask for fewer rows)");
-        }
-        if (old.hit) HIP_TRY(c, hipStreamSynchronize(c->stream));    // (a fold on the stream may still be using the old ones)
-        r.vax = old.vax; old.vax = nullptr;                          // (4 B per citizen whatever the shape)
-        rows_free(c, &old);
-        old = r;
-    }
-    Ensemble::Rows &r = c->ens.rows;
-    r.kind = Ensemble::ROWS_SERIES; r.what = what; r.first = first_step; r.n_rows = n_rows; r.stride = stride; r.min = min_cases; r.n_cols = cols; r.two = two;
-    HIP_TRY(c, hipMemsetAsync(r.hit, 0, sizeof(uint32_t) * cells, c->stream));
-    HIP_TRY(c, hipMemsetAsync(r.sum, 0, sizeof(unsigned long long) * cells, c->stream));
-    HIP_TRY(c, hipMemsetAsync(r.sumsq, 0, sizeof(unsigned long long) * cells, c->stream));
-    HIP_TRY(c, hipMemsetAsync(r.members, 0, sizeof(uint32_t), c->stream));
-    c->ens.where = where; c->ens.series = true; c->ens.arrival = false; c->ens.n = cols; c->ens.valid = true;
-    members_end(c);
-    return ESIM_OK;
+    Ensemble::Par par;
+    par.status = what; par.first = first_step; par.stride = stride; par.min_hit = min_cases;
+    return ens_begin(c, "esim_ensemble_begin_series", Ensemble::ENS_SERIES, where, n_rows, cols, par, two);
 }
 
 extern "C" int esim_ensemble_read_series(esim_ctx *ctx, uint32_t first_row, uint32_t n, uint32_t *members, uint32_t *hit, uint64_t *sum, uint64_t *sumsq)
 {
     esim_ctx_impl *c = CTX(ctx); if (!c) return ESIM_EINVAL;
-    if (!c->uploaded || !c->ens.valid || !c->ens.series || !c->ens.rows.hit)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: no population uploaded, or no esim_ensemble_begin_series or esim_ensemble_begin_settings in force since the upload (or, by group, since esim_set_groups)");
-    const Ensemble::Rows &r = c->ens.rows;
-    if (r.kind == Ensemble::ROWS_REPRODUCTION)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_reproduction (read them with esim_ensemble_read_reproduction)");
-    if (r.kind == Ensemble::ROWS_PAIRED)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_paired (read them with esim_ensemble_read_paired)");
-    if (r.kind == Ensemble::ROWS_PEAKS)
-        return fail(c, ESIM_ESTATE, "esim_ensemble_read_series: the accumulators in force were begun by esim_ensemble_begin_peaks (read them with esim_ensemble_read_peaks)");
-    if ((uint64_t)first_row + n > r.n_rows) return fail(c, ESIM_ERANGE, "esim_ensemble_read_series: rows outside the accumulators");
-    HIP_TRY(c, hipSetDevice(c->P.device));
-    Ctrl h; int rc;
-    if ((rc = read_ctrl(c, &h))) return rc;                        // (the wait for the folds enqueued so far)
-    const size_t at = (size_t)first_row * r.n_cols, cells = (size_t)n * r.n_cols;
-    if (members) HIP_TRY(c, hipMemcpy(members, r.members, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (hit && cells) HIP_TRY(c, hipMemcpy(hit, r.hit + at, sizeof(uint32_t) * cells, hipMemcpyDeviceToHost));
-    if (sum && cells) HIP_TRY(c, hipMemcpy(sum, r.sum + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
-    if (sumsq && cells) HIP_TRY(c, hipMemcpy(sumsq, r.sumsq + at, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost));
-    return ctrl_error(c, h);
+    return ens_read(c, READ_SERIES, first_row, n, members, { { hit, &Rows::hit } }, { { sum, &Rows::sum }, { sumsq, &Rows::sumsq } });
 }
 
 extern "C" int esim_area_series(esim_ctx *ctx, int what, uint32_t first_step, uint32_t n_rows, uint32_t stride, uint32_t *out)

@@ -149,9 +149,7 @@ int upload_population_tables(esim_ctx_impl *c, const UploadHost &u)
     free_device(c);
     c->rs.seeds_dev = nullptr; c->rs.seeds_cap = 0;                // (freed with the rest; the ensemble accumulators go with the population)
     c->arrival = nullptr;
-    c->ens.hit = c->ens.members = nullptr; c->ens.sum = c->ens.sumsq = nullptr;
-    c->ens.rows = Ensemble::Rows(); c->ens.series = false;
-    c->ens.valid = false;
+    c->ens = Ensemble();                                           // (no kind in force: every buffer and the members kept went with the rest)
     c->grp = Groups();                                             // (the labels belong to the population they were set for)
     c->snap = Snapshot();                                          // (so does a snapshot: its buffers went with the rest)
     c->base = Baseline();                                          // (and a kept baseline)

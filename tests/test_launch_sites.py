@@ -97,6 +97,12 @@ def test_every_output_launch_is_clamped_or_covers_its_items_exactly():
     assert not stale, "listed launches that no longer exist: %s" % stale
 
 
+def test_the_state_of_the_ensemble_accumulators_launches_nothing():
+    # esim_host_ensemble.h holds the kinds' table, begin, read-out and fold dispatch; every fold's launches stay in its family's file
+    text = open(os.path.join(CSRC, "esim_host_ensemble.h")).read()
+    assert "hipLaunchKernelGGL" not in text and not CLAMPED.search(text) and "<<<" not in text and "_enqueue(" not in text
+
+
 def test_the_cap_is_off_unless_the_environment_sets_it_and_is_documented():
     ctx = open(os.path.join(CSRC, "esim_host_ctx.h")).read()
     # by construction: with the knob at 0 the clamp returns the grid it was given before it touches anything
