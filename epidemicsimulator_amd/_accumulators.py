@@ -299,3 +299,43 @@ class _Accumulators:
             k = min(_lib.RANKS_MAX, thr.size - i)
             _lib.check(self.lib.esim_ensemble_exceedance(self._ctx, first_row, n, ptr(thr[i:]), k, ptr(out[i:])), self._ctx)
         return out
+
+    # -- curve-based statistics: the members kept ranked as whole curves (esim_ensemble_depth, esim_ensemble_band) -------
+    def ensemble_depth(self, first_row=0, n_rows=None):
+        """{"depth": uint32 [kept, n_cols], "total": uint64 [kept], "pairs": int, "rows": int, "mbd": float64 [kept, n_cols]}: the
+        modified band depth of every member kept, per column, over the rows [first_row, first_row + n) of the store, counted on
+        the device in integers (esim_ensemble_depth).  depth is the number of pairs of members whose band holds the member's key,
+        summed over the rows; pairs = C(kept, 2); mbd = depth / (rows * pairs), NaN where that is 0 / 0.  total: depth summed
+        over the columns.  n_rows=None: all from first_row on."""
+        kept = self.ensemble_members_info()["kept"]
+        first_row, n, _ = self._members_planes(0, first_row, n_rows)
+        cols = int(getattr(self, "_ens_n", self.population.n_areas))
+        depth, total = np.zeros((kept, cols), np.uint32), np.zeros(kept, np.uint64)
+        _lib.check(self.lib.esim_ensemble_depth(self._ctx, first_row, n, ptr(depth), ptr(total)), self._ctx)
+        pairs = kept * (kept - 1) // 2
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mbd = depth.astype(np.float64) / np.float64(n * pairs)
+        return {"depth": depth, "total": total, "pairs": pairs, "rows": n, "mbd": mbd}
+
+    def ensemble_band(self, coverage=0.5, pooled=False, first_row=0, n_rows=None, need=None):
+        """{"lo", "hi", "median": [n, n_cols], "deepest", "n_in": uint32 [n_cols], "need": int}: the envelope of the most central
+        members kept and the deepest member's curve, over the rows [first_row, first_row + n) (esim_ensemble_band).  The
+        need = max(1, ceil(coverage * kept)) deepest members are in, and every member that ties with the last of them; an
+        explicit need overrides the coverage, which is taken as the decimal it was written as (nearest_rank).  lo and hi are
+        the smallest and largest value over the members that are in, median the curve of member deepest[col]: a real run.
+        pooled=False ranks the members per column; pooled=True by their depth summed over the columns, one set of members and
+        one deepest member for the whole map.  int32 for the paired kind, uint32 otherwise (_lib.NEVER means what it means in
+        the store).  n_rows=None: all from first_row on."""
+        info = self.ensemble_members_info()
+        kept = info["kept"]
+        if need is None:
+            if not 0.0 <= float(coverage) <= 1.0:
+                raise ValueError("Simulator.ensemble_band: coverage must lie in [0, 1], got %r" % (coverage,))
+            need = max(1, nearest_rank(coverage, kept) + 1)
+        first_row, n, planes = self._members_planes(3, first_row, n_rows)
+        cols = zeros(("deepest", "n_in"), planes.shape[2])
+        _lib.check(self.lib.esim_ensemble_band(self._ctx, first_row, n, int(need), int(bool(pooled)), ptr(planes[0]), ptr(planes[1]), ptr(planes[2]),
+                                               ptr(cols["deepest"]), ptr(cols["n_in"])), self._ctx)
+        if info["signed"]:
+            planes = planes.view(np.int32)
+        return dict(cols, lo=planes[0], hi=planes[1], median=planes[2], need=int(need))

@@ -160,6 +160,7 @@ def peaks_summary(acc):
 
 
 PEAKS_ARRAYS = ("defined", "hit", "p_peak", "peak_mean", "peak_var", "peak_step_mean", "peak_step_var", "duration_mean", "duration_var")
+BAND_ARRAYS = ("band_lo", "band_hi", "band_median", "band_deepest", "band_n_in", "band_need", "band_coverage", "band_pooled", "depth")     # of ensemble_area_band.npz
 
 
 def _json_number(x):
@@ -202,7 +203,9 @@ class EnsembleResult:
         were asked for, go to ensemble_settings.npz: settings [members, n_rows, 4] and the four names; their cohort rows to
         ensemble_reproduction.npz: reproduction [members, n_rows, 2] and the two names.  The quantile maps, where the area dict
         asked for them, go to ensemble_area_quantiles.npz: probs, quantiles, thresholds, exceed, steps for a summary over rows, and
-        codes; every other file is what it is without them."""
+        codes; every other file is what it is without them.  The central band, where the area dict asked for it (band=), goes to
+        ensemble_area_band.npz the same way: band_lo, band_hi, band_median, band_deepest, band_n_in, band_need, band_coverage,
+        band_pooled, depth, steps and codes."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -242,6 +245,13 @@ class EnsembleResult:
             if self.area_codes is not None:
                 extra["codes"] = np.asarray(self.area_codes)
             np.savez(os.path.join(directory, "ensemble_area_quantiles.npz"), **extra)
+        if self.area is not None and "band_lo" in self.area:         # the central band: a file of its own too
+            extra = {k: np.asarray(self.area[k]) for k in BAND_ARRAYS}
+            if "steps" in self.area:
+                extra["steps"] = self.area["steps"]
+            if self.area_codes is not None:
+                extra["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_band.npz"), **extra)
         if self.settings is not None:
             np.savez(os.path.join(directory, "ensemble_settings.npz"), settings=self.settings, names=np.asarray(_lib.SETTING_NAMES))
         if self.reproduction is not None:
@@ -557,10 +567,12 @@ class BurdenCompareResult:
         np.savez(os.path.join(directory, "ensemble_burden_compare.npz"), **arrays)
 
 
-def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep")):
-    """The keys of the quantile maps popped from `area` and checked before any library call: None where none is given, else
-    dict(probs, method, thresholds, what).  ValueError for the reproduction kind (a ratio per cell is not kept), a probability
-    outside [0, 1], an unknown method, `keep` on another kind than peaks, or more members than the store takes."""
+def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep", "band", "band_pooled")):
+    """The keys of the quantile maps and of the central band popped from `area` and checked before any library call: None where
+    none is given, else dict(probs, method, thresholds, what) -- and, where band= or band_pooled= is given, band (the coverage),
+    band_pooled and band_only (no key of the quantile maps beside them).  ValueError for the reproduction kind (a ratio per cell
+    is not kept), a probability or a coverage outside [0, 1], an unknown method, `keep` on another kind than peaks, or more
+    members than the store takes."""
     given = {k: area.pop(k) for k in keys if k in area}
     if not given:
         return None
@@ -575,7 +587,13 @@ def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_met
         raise ValueError("%s: keep must be 'value', or for the peaks kind 'peak_step' or 'duration', got %r" % (who, what))
     if n_members is not None and int(n_members) > _lib.MEMBERS_MAX:
         raise ValueError("%s: %d members, the store of the quantile maps takes %d (ESIM_MEMBERS_MAX)" % (who, int(n_members), _lib.MEMBERS_MAX))
-    return dict(probs=probs, method=method, thresholds=[int(t) for t in (given.get("exceed") or ())], what=what)
+    spec = dict(probs=probs, method=method, thresholds=[int(t) for t in (given.get("exceed") or ())], what=what)
+    if "band" in given or "band_pooled" in given:
+        coverage = float(given.get("band", 0.5))
+        if not 0.0 <= coverage <= 1.0:
+            raise ValueError("%s: band is the coverage of the central region and must lie in [0, 1], got %r" % (who, given.get("band")))
+        spec.update(band=coverage, band_pooled=bool(given.get("band_pooled", False)), band_only=all(k in ("band", "band_pooled") for k in given))
+    return spec
 
 
 _KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")
@@ -654,15 +672,24 @@ class Ensemble:
 
     def _keep_summary(self, summary, kind, n_members):
         """The summary with probs, quantiles, thresholds and exceed added: [n_q, n_rows, n_cols], [n_q, n_cols] for the kinds
-        without rows (census, arrival, peaks)."""
+        without rows (census, arrival, peaks).  With band= in the area dict it gains band_lo, band_hi, band_median ([n_rows,
+        n_cols], [n_cols] for the kinds without rows), band_deepest, band_n_in [n_cols], band_need, band_coverage, band_pooled
+        and depth, the modified band depth [members, n_cols] (Simulator.ensemble_band, ensemble_depth)."""
         spec = self._keep_spec
         if spec is None or summary is None or not n_members:
             return summary
         sim = self.simulator
         flat = (lambda a: a[:, 0]) if kind in ("census", "arrival", "peaks", "burden_peaks") else (lambda a: a)
-        out = dict(summary, probs=np.asarray(spec["probs"], np.float64), thresholds=np.asarray(spec["thresholds"], np.int64))
-        out["quantiles"] = flat(sim.ensemble_quantiles(spec["probs"], spec["method"])) if spec["probs"] else None
-        out["exceed"] = flat(sim.ensemble_exceedance(spec["thresholds"])) if spec["thresholds"] else None
+        out = dict(summary)
+        if not spec.get("band_only"):
+            out.update(probs=np.asarray(spec["probs"], np.float64), thresholds=np.asarray(spec["thresholds"], np.int64))
+            out["quantiles"] = flat(sim.ensemble_quantiles(spec["probs"], spec["method"])) if spec["probs"] else None
+            out["exceed"] = flat(sim.ensemble_exceedance(spec["thresholds"])) if spec["thresholds"] else None
+        if "band" in spec:
+            b = sim.ensemble_band(spec["band"], spec["band_pooled"])
+            row = (lambda a: a[0]) if kind in ("census", "arrival", "peaks", "burden_peaks") else (lambda a: a)
+            out.update(band_lo=row(b["lo"]), band_hi=row(b["hi"]), band_median=row(b["median"]), band_deepest=b["deepest"], band_n_in=b["n_in"], band_need=b["need"],
+                       band_coverage=spec["band"], band_pooled=spec["band_pooled"], depth=sim.ensemble_depth()["mbd"])
         return out
 
     def _summary(self, kind, area):
@@ -851,6 +878,11 @@ class Ensemble:
         and, for peaks, keep="value", "peak_step" or "duration": the members' values per cell are then kept on the device
         (Simulator.ensemble_keep_members) and the summary gains probs, quantiles [n_q, n_rows, n_cols] ([n_q, n_cols] for the
         kinds without rows), thresholds and exceed -- the members at or above each threshold.  At most 256 members.
+        They also take band=0.5 and band_pooled=False: the members are ranked as whole curves on the device (modified band
+        depth, Simulator.ensemble_depth) and the summary gains band_lo and band_hi, the envelope of the most central
+        ceil(band x members) of them, band_median, the curve of the deepest member -- a real run, unlike a row of quantiles --,
+        band_deepest, band_n_in, band_need and depth [members, n_cols] (Simulator.ensemble_band); band_pooled=True ranks the
+        members once for all columns, by default every column ranks its own.
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
         (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
         with stop_when_done=True either.

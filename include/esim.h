@@ -1045,6 +1045,35 @@ int  esim_ensemble_read_members(esim_ctx *ctx, uint32_t first_member, uint32_t n
 int  esim_ensemble_quantiles(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const uint32_t *ranks, uint32_t n_ranks, uint32_t *out);
 int  esim_ensemble_exceedance(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, const int64_t *thresholds, uint32_t n_thresholds, uint32_t *out);
 
+/* Curve-based ensemble statistics: the members kept by esim_ensemble_keep_members ranked as whole curves, for the
+ * questions a band stitched from per-cell quantiles answers wrongly (no single member stays inside it, and its median peaks
+ * lower and wider than any member does).  The store holds kept = M members, n_rows rows and n_cols columns.
+ * curve:  the curve of member i in column c is its keys x[i][r][c] over the rows r of a window [first_row, first_row + n_rows).
+ *        Keys order as the store orders them: unsigned, signed kinds with the top bit flipped, ESIM_NEVER largest.
+ * depth:  modified band depth with bands of two curves (Lopez-Pintado and Romo 2009), stated so that ties are safe.  For a cell
+ *        (r, c) and member i, below = the members whose key is < x[i], above = the members whose key is > x[i]; the pairs {j, k}
+ *        of the M members (i itself included) with min(x[j], x[k]) <= x[i] <= max(x[j], x[k]) number exactly
+ *        C(M, 2) - C(below, 2) - C(above, 2).  depth[i * n_cols + c] is the sum of that count over the rows of the window, an
+ *        exact integer; depth / (n_rows * C(M, 2)) is the modified band depth; total[i] is the sum of depth[i][c] over c, in 64
+ *        bits.  With M = 1 every depth is 0.  ESIM_ERANGE for a window whose n_rows * C(M, 2) does not fit 32 bits.
+ * central region, for need in 1..M.  Per column (pooled = 0): thr[c] is the need-th largest of depth[.][c]; member i is in if
+ *        depth[i][c] >= thr[c], ties at the threshold all in; n_in[c] >= need counts the members that are in; deepest[c] is the
+ *        smallest member index whose depth is the maximum.  Pooled (pooled = 1): the same with total[.] in place of
+ *        depth[.][c] -- one set of members and one deepest member for all columns, one coherent future for the whole map.
+ * band:  lo[r * n_cols + c] and hi[r * n_cols + c] are the minimum and maximum key over the members that are in,
+ *        median[r * n_cols + c] is the key of member deepest[c]; signed kinds come back as the numbers they are, as
+ *        esim_ensemble_quantiles returns them, and a plane may hold ESIM_NEVER for the arrival and peak-step stores, where it
+ *        means what it means there.
+ *        Both calls are ESIM_ESTATE without a store or with nothing kept (a store invalidated by esim_set_groups or ended by a
+ *        new begin included); ESIM_ERANGE for rows outside the store and for need 0 or above the members kept; ESIM_EINVAL for a
+ *        pooled that is not 0 or 1.  Any output may be NULL, all of them too: the call still validates.  They wait for the
+ *        stream and leave everything as it is; their tables on the device (4 B per member and column) go when they return. */
+int  esim_ensemble_depth(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows,
+                         uint32_t *depth /* [kept * n_cols] or NULL */, uint64_t *total /* [kept] or NULL */);
+int  esim_ensemble_band(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, uint32_t need, int pooled,
+                        uint32_t *lo, uint32_t *hi, uint32_t *median /* [n_rows * n_cols] each, any may be NULL */,
+                        uint32_t *deepest, uint32_t *n_in /* [n_cols] each, any may be NULL */);
+
 /* Hospital burden: admissions, bed occupancy and deaths laid over a finished run.  In the model's SEIR(+V) rules
  * nothing that happens to a case after its onset feeds back into transmission, so severity is drawn after the fact, one Philox
  * block per case under the contract below, as the infector draw is.  No step kernel is touched; a run that never asks pays nothing.

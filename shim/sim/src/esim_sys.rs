@@ -101,6 +101,10 @@ extern "C" {
     pub fn esim_checkpoint_size(ctx: *mut c_void, bytes: *mut usize) -> c_int;
     pub fn esim_checkpoint_save(ctx: *mut c_void, buf: *mut c_void, cap: usize) -> c_int;
     pub fn esim_checkpoint_restore(ctx: *mut c_void, buf: *const c_void, bytes: usize) -> c_int;
+    // curve-based ensemble statistics over the members kept on the device: band depth per member, the central envelope
+    pub fn esim_ensemble_depth(ctx: *mut c_void, first_row: u32, n_rows: u32, depth: *mut u32, total: *mut u64) -> c_int;
+    pub fn esim_ensemble_band(ctx: *mut c_void, first_row: u32, n_rows: u32, need: u32, pooled: c_int, lo: *mut u32, hi: *mut u32, median: *mut u32,
+                              deepest: *mut u32, n_in: *mut u32) -> c_int;
     pub fn esim_enable_phase_timing(ctx: *mut c_void, enable: c_int) -> c_int;
     pub fn esim_phase_timings(ctx: *mut c_void, out: *mut f64) -> c_int;
     // multi-GPU: one context per GPU and process; the exchange between the shards is the library's
