@@ -339,3 +339,29 @@ class _Accumulators:
         if info["signed"]:
             planes = planes.view(np.int32)
         return dict(cols, lo=planes[0], hi=planes[1], median=planes[2], need=int(need))
+
+    # -- ensemble distances: the members kept compared pair by pair (esim_ensemble_distances) -------
+    DIST_METRIC = {"l1": _lib.DIST_L1, "differ": _lib.DIST_DIFFER}
+
+    def ensemble_distances(self, metric="l1", first_row=0, n_rows=None, never_as=None):
+        """{"distances": uint64 [kept, kept], "live_cells": int, "cells": int, "metric": str}: the distance of every pair of
+        members kept, summed on the device over the rows [first_row, first_row + n) of the store and all columns
+        (esim_ensemble_distances).  metric="l1": the sum of |x_i - x_j| per cell; "differ": the cells in which the two differ.
+        Exact integers, symmetric, the diagonal 0.  never_as: what _lib.NEVER counts as in the stores that hold it (arrival,
+        peak_step) -- the horizon, say; None leaves it as it is.  cells: those of the window; live_cells: those of them the
+        accumulators do not settle, which the kernel compared.  n_rows=None: all from first_row on."""
+        code = self.DIST_METRIC.get(metric, metric)
+        if not isinstance(code, int) or isinstance(code, bool):
+            raise ValueError("Simulator.ensemble_distances: metric must be 'l1' or 'differ', got %r" % (metric,))
+        kept = self.ensemble_members_info()["kept"]
+        first_row, n, _ = self._members_planes(0, first_row, n_rows)
+        out, live = np.zeros((kept, kept), np.uint64), C.c_uint64(0)
+        _lib.check(self.lib.esim_ensemble_distances(self._ctx, first_row, n, code, _lib.NEVER if never_as is None else int(never_as), ptr(out), C.byref(live)), self._ctx)
+        names = {v: k for k, v in self.DIST_METRIC.items()}
+        return {"distances": out, "live_cells": int(live.value), "cells": n * int(getattr(self, "_ens_n", self.population.n_areas)), "metric": names.get(code, metric)}
+
+    def ensemble_distances_info(self):
+        """{"tiles", "tiles_32bit", "tiles_partial"} of the last ensemble_distances (esim_ensemble_distances_info)."""
+        t = [C.c_uint64(0) for _ in range(3)]
+        _lib.check(self.lib.esim_ensemble_distances_info(self._ctx, *(C.byref(x) for x in t)), self._ctx)
+        return dict(zip(("tiles", "tiles_32bit", "tiles_partial"), (int(x.value) for x in t)))

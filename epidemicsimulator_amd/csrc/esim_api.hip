@@ -21,6 +21,7 @@
 #include "esim_host_ensemble.h"
 #include "esim_host_members.h"
 #include "esim_host_depth.h"
+#include "esim_host_dist.h"
 #include "esim_host_upload.h"
 #include "esim_host_run.h"
 #include "esim_host_shard.h"

@@ -117,6 +117,7 @@ struct Ensemble {
         bool is_signed = false, has_never = false;
     } store;
     uint32_t folds = 0;
+    uint64_t dist_stats[4] = { 0u, 0u, 0u, 0u };  // esim_ensemble_distances (esim_host_dist.h): the counts of the last call's kernel (esim_dist.h)
 };
 
 // esim_set_groups: a label per citizen, the groups' sizes and the count table of esim_group_census [n * 5] (nullptr: no labels).

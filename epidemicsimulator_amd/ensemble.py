@@ -160,6 +160,7 @@ def peaks_summary(acc):
 
 
 PEAKS_ARRAYS = ("defined", "hit", "p_peak", "peak_mean", "peak_var", "peak_step_mean", "peak_step_var", "duration_mean", "duration_var")
+CLUSTER_ARRAYS = ("distances", "cluster_medoid", "cluster_label", "cluster_size", "cluster_silhouette", "cluster_curves", "cluster_cost", "cluster_metric")   # of ensemble_area_clusters.npz
 BAND_ARRAYS = ("band_lo", "band_hi", "band_median", "band_deepest", "band_n_in", "band_need", "band_coverage", "band_pooled", "depth")     # of ensemble_area_band.npz
 
 
@@ -205,7 +206,8 @@ class EnsembleResult:
         asked for them, go to ensemble_area_quantiles.npz: probs, quantiles, thresholds, exceed, steps for a summary over rows, and
         codes; every other file is what it is without them.  The central band, where the area dict asked for it (band=), goes to
         ensemble_area_band.npz the same way: band_lo, band_hi, band_median, band_deepest, band_n_in, band_need, band_coverage,
-        band_pooled, depth, steps and codes."""
+        band_pooled, depth, steps and codes.  The clusters (clusters=) go to ensemble_area_clusters.npz: distances, cluster_medoid,
+        cluster_label, cluster_size, cluster_silhouette, cluster_curves, cluster_cost, cluster_metric, steps and codes."""
         os.makedirs(directory, exist_ok=True)
         stats = {"members": self.members, "n_done": self.n_done.tolist(), "fields": {}}
         for f in STAT_FIELDS:
@@ -252,6 +254,13 @@ class EnsembleResult:
             if self.area_codes is not None:
                 extra["codes"] = np.asarray(self.area_codes)
             np.savez(os.path.join(directory, "ensemble_area_band.npz"), **extra)
+        if self.area is not None and "cluster_medoid" in self.area:  # the clusters: a file of their own too
+            extra = {k: np.asarray(self.area[k]) for k in CLUSTER_ARRAYS}
+            if "steps" in self.area:
+                extra["steps"] = self.area["steps"]
+            if self.area_codes is not None:
+                extra["codes"] = np.asarray(self.area_codes)
+            np.savez(os.path.join(directory, "ensemble_area_clusters.npz"), **extra)
         if self.settings is not None:
             np.savez(os.path.join(directory, "ensemble_settings.npz"), settings=self.settings, names=np.asarray(_lib.SETTING_NAMES))
         if self.reproduction is not None:
@@ -567,12 +576,16 @@ class BurdenCompareResult:
         np.savez(os.path.join(directory, "ensemble_burden_compare.npz"), **arrays)
 
 
-def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep", "band", "band_pooled")):
-    """The keys of the quantile maps and of the central band popped from `area` and checked before any library call: None where
-    none is given, else dict(probs, method, thresholds, what) -- and, where band= or band_pooled= is given, band (the coverage),
-    band_pooled and band_only (no key of the quantile maps beside them).  ValueError for the reproduction kind (a ratio per cell
-    is not kept), a probability or a coverage outside [0, 1], an unknown method, `keep` on another kind than peaks, or more
-    members than the store takes."""
+_EXTRA_KEYS = ("band", "band_pooled", "clusters", "cluster_metric")       # of the area dict: what reads the kept members beside the quantile maps
+
+
+def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_method", "exceed", "keep") + _EXTRA_KEYS):
+    """The keys of the quantile maps, of the central band and of the clusters popped from `area` and checked before any library
+    call: None where none is given, else dict(probs, method, thresholds, what) -- and, where band= or band_pooled= is given, band
+    (the coverage) and band_pooled; where clusters= or cluster_metric= is given, clusters (k, 2 by default) and cluster_metric;
+    with either, band_only (no key of the quantile maps beside them).  ValueError for the reproduction kind (a ratio per cell
+    is not kept), a probability or a coverage outside [0, 1], an unknown method or metric, clusters below 1 or above the
+    members, `keep` on another kind than peaks, or more members than the store takes."""
     given = {k: area.pop(k) for k in keys if k in area}
     if not given:
         return None
@@ -592,8 +605,76 @@ def _keep_spec(who, kind, area, n_members=None, keys=("quantiles", "quantile_met
         coverage = float(given.get("band", 0.5))
         if not 0.0 <= coverage <= 1.0:
             raise ValueError("%s: band is the coverage of the central region and must lie in [0, 1], got %r" % (who, given.get("band")))
-        spec.update(band=coverage, band_pooled=bool(given.get("band_pooled", False)), band_only=all(k in ("band", "band_pooled") for k in given))
+        spec.update(band=coverage, band_pooled=bool(given.get("band_pooled", False)), band_only=all(k in _EXTRA_KEYS for k in given))
+    if "clusters" in given or "cluster_metric" in given:
+        k, metric = given.get("clusters", 2), given.get("cluster_metric", "l1")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (n_members is not None and k > int(n_members)):
+            raise ValueError("%s: clusters is the number of medoids and must lie in 1..the members, got %r" % (who, k))
+        if metric not in Simulator.DIST_METRIC:
+            raise ValueError("%s: cluster_metric must be 'l1' or 'differ', got %r" % (who, metric))
+        spec.update(clusters=int(k), cluster_metric=metric, band_only=all(k in _EXTRA_KEYS for k in given))
     return spec
+
+
+def medoids(distances, k, max_swaps=1000):
+    """Deterministic k-medoids (PAM) over a symmetric matrix of distances [M, M], as Simulator.ensemble_distances returns it: k
+    real members that stand for the ensemble, and every member with the nearest of them.
+    BUILD: the first medoid is the member with the smallest sum of distances to all; each further one the member that lowers
+    the cost -- the sum over the members of the distance to their nearest medoid -- most.  SWAP: while a swap of a medoid
+    against a member that is none lowers the cost, the one that lowers it most is made, max_swaps at the most.  Ties go to
+    the lowest index everywhere, and the sums are exact integers.  The result is a local optimum under single swaps; for k = 1
+    it is the medoid of the ensemble, the member with the smallest total distance.
+    Returns {"medoid": int64 [k], ascending; "label": int64 [M], the position in `medoid` of the member's nearest medoid (a
+    medoid is its own; ties to the lowest); "size": int64 [k]; "cost": int; "silhouette": float64 [M]}: (b - a) / max(a, b)
+    with a the mean distance to the other members of the member's cluster and b the smallest mean distance to the members of
+    another cluster; 0 for a member alone in its cluster, where a = b = 0, and for k = 1.  ValueError for a matrix that is not
+    square, k < 1 or k > M."""
+    d = np.asarray(distances)
+    if d.ndim != 2 or d.shape[0] != d.shape[1]:
+        raise ValueError("medoids: distances must be a square matrix, got shape %r" % (d.shape,))
+    m, k = d.shape[0], int(k)
+    if not 1 <= k <= m:
+        raise ValueError("medoids: k must lie in 1..%d (the members), got %d" % (m, k))
+    top = int(d.max()) if m else 0
+    d = d.astype(np.int64) if top * m < 1 << 62 else np.array([[int(v) for v in row] for row in d.tolist()], object)   # (sums stay exact either way)
+    chosen = [int(np.argmin(d.sum(axis=0)))]
+    while len(chosen) < k:
+        near = d[:, chosen].min(axis=1)
+        cost = np.minimum(near[:, None], d).sum(axis=0)             # the cost with member h as one more medoid
+        for c in chosen:
+            cost[c] = near.sum() + 1                                # (never better than a member that is none: those cost <= near.sum())
+        chosen.append(int(np.argmin(cost)))
+    cost = d[:, chosen].min(axis=1).sum()
+    for _ in range(int(max_swaps)):
+        best = None
+        for p in range(k):
+            rest = [c for q, c in enumerate(chosen) if q != p]
+            trial = np.minimum(d[:, rest].min(axis=1)[:, None], d).sum(axis=0) if rest else d.sum(axis=0)
+            for c in chosen:
+                trial[c] = cost                                     # (a medoid is no candidate)
+            h = int(np.argmin(trial))
+            if trial[h] < cost and (best is None or trial[h] < best[0]):
+                best = (trial[h], p, h)
+        if best is None:
+            break
+        cost, chosen[best[1]] = best[0], best[2]
+    chosen.sort()
+    to = d[:, chosen]
+    label = np.argmin(to, axis=1).astype(np.int64)
+    label[chosen] = np.arange(k)
+    size = np.bincount(label, minlength=k).astype(np.int64)
+    cost = int(sum(int(to[i, label[i]]) for i in range(m)))
+    sil = np.zeros(m, np.float64)
+    if k > 1:
+        total = np.stack([d[:, label == q].sum(axis=1).astype(np.float64) for q in range(k)], axis=1)     # [M, k]: to the members of each cluster
+        for i in range(m):
+            own = label[i]
+            if size[own] < 2:
+                continue
+            a = total[i, own] / (size[own] - 1)
+            b = min(total[i, q] / size[q] for q in range(k) if q != own)
+            sil[i] = (b - a) / max(a, b) if max(a, b) > 0 else 0.0
+    return {"medoid": np.asarray(chosen, np.int64), "label": label, "size": size, "cost": cost, "silhouette": sil}
 
 
 _KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")
@@ -670,11 +751,14 @@ class Ensemble:
         if self._keep_spec is not None and n_members:
             self.simulator.ensemble_keep_members(n_members, self._keep_spec["what"])
 
-    def _keep_summary(self, summary, kind, n_members):
+    def _keep_summary(self, summary, kind, n_members, area=None):
         """The summary with probs, quantiles, thresholds and exceed added: [n_q, n_rows, n_cols], [n_q, n_cols] for the kinds
         without rows (census, arrival, peaks).  With band= in the area dict it gains band_lo, band_hi, band_median ([n_rows,
         n_cols], [n_cols] for the kinds without rows), band_deepest, band_n_in [n_cols], band_need, band_coverage, band_pooled
-        and depth, the modified band depth [members, n_cols] (Simulator.ensemble_band, ensemble_depth)."""
+        and depth, the modified band depth [members, n_cols] (Simulator.ensemble_band, ensemble_depth).  With clusters= it
+        gains distances [members, members] (Simulator.ensemble_distances; for the arrival kind ESIM_NEVER counts as the horizon
+        of `area`), cluster_medoid, cluster_label, cluster_size, cluster_silhouette and cluster_cost (medoids), cluster_metric,
+        and cluster_curves [k, n_rows, n_cols], the medoids' own planes ([k, n_cols] for the kinds without rows)."""
         spec = self._keep_spec
         if spec is None or summary is None or not n_members:
             return summary
@@ -690,6 +774,13 @@ class Ensemble:
             row = (lambda a: a[0]) if kind in ("census", "arrival", "peaks", "burden_peaks") else (lambda a: a)
             out.update(band_lo=row(b["lo"]), band_hi=row(b["hi"]), band_median=row(b["median"]), band_deepest=b["deepest"], band_n_in=b["n_in"], band_need=b["need"],
                        band_coverage=spec["band"], band_pooled=spec["band_pooled"], depth=sim.ensemble_depth()["mbd"])
+        if "clusters" in spec:
+            horizon = (area or {}).get("horizon") if kind == "arrival" else None
+            dist = sim.ensemble_distances(spec["cluster_metric"], never_as=horizon)["distances"]
+            c = medoids(dist, min(spec["clusters"], dist.shape[0]))
+            curves = np.concatenate([sim.ensemble_members(int(i), 1) for i in c["medoid"]])           # one member a call
+            out.update(distances=dist, cluster_medoid=c["medoid"], cluster_label=c["label"], cluster_size=c["size"], cluster_silhouette=c["silhouette"],
+                       cluster_cost=c["cost"], cluster_metric=spec["cluster_metric"], cluster_curves=flat(curves))
         return out
 
     def _summary(self, kind, area):
@@ -883,6 +974,9 @@ class Ensemble:
         ceil(band x members) of them, band_median, the curve of the deepest member -- a real run, unlike a row of quantiles --,
         band_deepest, band_n_in, band_need and depth [members, n_cols] (Simulator.ensemble_band); band_pooled=True ranks the
         members once for all columns, by default every column ranks its own.
+        And clusters=k with cluster_metric="l1" or "differ": the members are compared pair by pair on the device
+        (Simulator.ensemble_distances) and grouped round k of them (medoids): the summary gains distances, cluster_medoid,
+        cluster_label, cluster_size, cluster_silhouette, cluster_cost, cluster_metric and cluster_curves, the medoids' own rows.
         settings: None, or dict(first_step=..., n_rows=..., stride=...): every member's exposures by setting
         (Simulator.setting_series(where="setting")) gathered on the host as EnsembleResult.settings, [members, n_rows, 4]; not
         with stop_when_done=True either.
@@ -909,7 +1003,7 @@ class Ensemble:
             n_done.append(len(rec))
             rows.append(pad_records(rec, n_steps))
         records = _stack(rows, (n_steps,), RECORD_DTYPE)
-        summary = self._keep_summary(self._summary(kind, area), kind, len(members))
+        summary = self._keep_summary(self._summary(kind, area), kind, len(members), area)
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
 
@@ -949,7 +1043,7 @@ class Ensemble:
             n_done.append(len(history) + len(rec))
             rows.append(pad_records(np.concatenate([history, rec]), n_steps))
         records = _stack(rows, (n_steps,), RECORD_DTYPE)
-        summary = self._keep_summary(self._summary(kind, area), kind, len(members))
+        summary = self._keep_summary(self._summary(kind, area), kind, len(members), area)
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
 

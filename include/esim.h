@@ -1074,6 +1074,28 @@ int  esim_ensemble_band(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, uint
                         uint32_t *lo, uint32_t *hi, uint32_t *median /* [n_rows * n_cols] each, any may be NULL */,
                         uint32_t *deepest, uint32_t *n_in /* [n_cols] each, any may be NULL */);
 
+/* Ensemble distances: the members kept by esim_ensemble_keep_members compared pair by pair, for ensembles with more
+ * than one centre -- the medoid, k-medoids clusters with their weights, silhouettes and the nearest real run to any member all
+ * follow from this M x M table on the host (M = kept <= ESIM_MEMBERS_MAX).
+ * out:   out[i * M + j], for the keys x[i][r][c] of the store over the rows r of a window [first_row, first_row + n_rows) and all
+ *        columns c:  ESIM_DIST_L1, the sum of |x[i] - x[j]|;  ESIM_DIST_DIFFER, the number of cells with x[i] != x[j].  Exact
+ *        integers in 64 bits over the full range of the keys; symmetric, the diagonal 0, both triangles written.  A signed
+ *        store (the paired kinds) gives the distances of the signed values.
+ * never_as:  for the stores in which ESIM_NEVER occurs (arrival, the step of the peak) a key equal to ESIM_NEVER is replaced by
+ *        never_as before it is compared -- the horizon, for instance; ESIM_NEVER leaves it as it is.  Ignored by every other store.
+ * live_cells:  may be NULL; the cells of the window that the accumulators do not settle (every member holds the same key there,
+ *        the planes are not read): what the kernel compared.  0 where nothing is launched (no rows, or one member).
+ *        ESIM_EINVAL for an unknown metric; ESIM_ESTATE without a store or with nothing kept; ESIM_ERANGE for rows outside the
+ *        store.  n_rows == 0 or kept <= 1 gives zeros.  out may be NULL: the call still validates and counts.  It waits for
+ *        the stream and leaves everything as it is; its matrix on the device goes when it returns.
+ * info:  what the kernel of the context's last esim_ensemble_distances did, any pointer NULL: the tiles of 64 packed live cells it
+ *        compared (per pair of member tiles), those of them summed in 32-bit accumulators, and those compared partially full. */
+#define ESIM_DIST_L1     0
+#define ESIM_DIST_DIFFER 1
+int  esim_ensemble_distances(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, int metric, uint32_t never_as,
+                             uint64_t *out /* [kept * kept] or NULL */, uint64_t *live_cells /* may be NULL */);
+int  esim_ensemble_distances_info(esim_ctx *ctx, uint64_t *tiles, uint64_t *tiles_32bit, uint64_t *tiles_partial);
+
 /* Hospital burden: admissions, bed occupancy and deaths laid over a finished run.  In the model's SEIR(+V) rules
  * nothing that happens to a case after its onset feeds back into transmission, so severity is drawn after the fact, one Philox
  * block per case under the contract below, as the infector draw is.  No step kernel is touched; a run that never asks pays nothing.
