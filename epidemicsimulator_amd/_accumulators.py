@@ -360,6 +360,28 @@ class _Accumulators:
         names = {v: k for k, v in self.DIST_METRIC.items()}
         return {"distances": out, "live_cells": int(live.value), "cells": n * int(getattr(self, "_ens_n", self.population.n_areas)), "metric": names.get(code, metric)}
 
+    # -- ensembles on several contexts: the accumulators of one added into another, or through bytes (esim_ensemble_merge) -------
+    def ensemble_merge(self, other):
+        """Adds the accumulators of `other` -- a Simulator with the same begin in force on the same population -- into this
+        one's and appends its kept members behind this one's (esim_ensemble_merge); `other` stays as it was.  Exact: the result
+        is the ensemble folded in sequence.  The call does not wait for this simulator's stream: leave `other` alone until this
+        one has been read or synchronized."""
+        _lib.check(self.lib.esim_ensemble_merge(self._ctx, other._ctx), self._ctx)
+
+    def ensemble_save(self):
+        """The ensemble in force as bytes: its descriptor, its accumulators and its kept members (esim_ensemble_save)."""
+        size = C.c_size_t(0)
+        _lib.check(self.lib.esim_ensemble_save_size(self._ctx, C.byref(size)), self._ctx)
+        buf = np.zeros(size.value, np.uint8)
+        _lib.check(self.lib.esim_ensemble_save(self._ctx, C.cast(ptr(buf), C.c_void_p), size.value), self._ctx)
+        return buf.tobytes()
+
+    def ensemble_load(self, blob):
+        """A merge from the bytes of ensemble_save: added into the begin in force, which must describe the same ensemble; behind
+        a fresh begin (and ensemble_keep_members) it restores (esim_ensemble_load)."""
+        buf = np.frombuffer(bytes(blob), np.uint8)
+        _lib.check(self.lib.esim_ensemble_load(self._ctx, C.cast(ptr(buf), C.c_void_p) if buf.size else None, buf.size), self._ctx)
+
     def ensemble_distances_info(self):
         """{"tiles", "tiles_32bit", "tiles_partial"} of the last ensemble_distances (esim_ensemble_distances_info)."""
         t = [C.c_uint64(0) for _ in range(3)]

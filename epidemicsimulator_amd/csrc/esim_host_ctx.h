@@ -117,6 +117,7 @@ struct Ensemble {
         bool is_signed = false, has_never = false;
     } store;
     uint32_t folds = 0;
+    uint8_t *merge_stage = nullptr; size_t merge_stage_bytes = 0;   // esim_ensemble_merge / _load (esim_host_merge.h): where a piece of the other ensemble lands, kept from call to call
     uint64_t dist_stats[4] = { 0u, 0u, 0u, 0u };  // esim_ensemble_distances (esim_host_dist.h): the counts of the last call's kernel (esim_dist.h)
 };
 
@@ -124,6 +125,7 @@ struct Ensemble {
 struct Groups {
     uint16_t *lab = nullptr; uint32_t n = 0;
     uint32_t *size = nullptr, *cnt = nullptr;
+    std::vector<uint32_t> sizes;                  // the groups' sizes on the host (what esim_ensemble_merge compares)
 };
 
 // esim_burden_set: the severity tables in force, on the host as they were given and on the device as the kernels
@@ -203,6 +205,7 @@ struct Tuning {
     uint32_t draw_mult = 4, units_mult = 4;     // k_chunk_draw / k_chunk_units run this many times the marks grid: more, shorter wavefronts than the chip holds at once
     uint32_t small_max = 128;                   // infected-slice length up to which the persistent single-workgroup kernel runs a step
     uint32_t pair_log2 = 0;                     // ESIM_PAIR_LOG2: the pair table of esim_area_flows / esim_lineage_areas has 1 << this many slots (0: sized by the log)
+    uint32_t merge_piece = 0;                   // ESIM_MERGE_PIECE: the cells a piece of esim_ensemble_merge / _load stages (0: unset, MERGE_PIECE_CELLS; tests only)
     uint32_t grid_cap = 0;                      // ESIM_GRID_CAP: the grids of the output kernels hold at most this many workgroups (0: unset, as in production)
 };
 

@@ -469,6 +469,7 @@ extern "C" int esim_set_groups(esim_ctx *ctx, const uint16_t *group, uint32_t n_
     if (c->grp.lab) HIP_TRY(c, hipStreamSynchronize(c->stream));
     dev_free(c, c->grp.lab); dev_free(c, c->grp.size); dev_free(c, c->grp.cnt);
     c->grp.lab = lab; c->grp.size = sz; c->grp.cnt = cnt; c->grp.n = group ? n_groups : 0u;
+    c->grp.sizes = size;
     if (c->ens.where == ESIM_BY_GROUP) c->ens.valid = false;
     if (c->burden.set && c->burden.n_groups != 1u && c->burden.n_groups != c->grp.n) burden_forget(c);   // (tables per group of labels that are gone)
     return ESIM_OK;

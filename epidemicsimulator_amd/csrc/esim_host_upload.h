@@ -385,6 +385,8 @@ void upload_tuning(esim_ctx_impl *c, const UploadHost &u)
     if (const char *e = std::getenv("ESIM_PAIR_LOG2")) t.pair_log2 = (uint32_t)std::min(31, std::max(6, std::atoi(e)));     // (at least 64 slots)
     t.grid_cap = 0u;
     if (const char *e = std::getenv("ESIM_GRID_CAP")) t.grid_cap = (uint32_t)std::max(1, std::atoi(e));                     // (tests only: the output kernels' grids)
+    t.merge_piece = 0u;
+    if (const char *e = std::getenv("ESIM_MERGE_PIECE")) t.merge_piece = (uint32_t)std::min(1 << 30, std::max(4, (std::atoi(e) + 3) / 4 * 4));   // (tests only: whole groups of four cells)
     c->launches = LaunchLog();
 }
 

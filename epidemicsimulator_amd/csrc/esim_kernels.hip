@@ -48,4 +48,5 @@
 #include "esim_kernels_burden.h"
 #include "esim_kernels_beds.h"
 #include "esim_kernels_members.h"
+#include "esim_kernels_merge.h"
 #include "esim_kernels_snapshot.h"

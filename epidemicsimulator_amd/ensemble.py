@@ -2,9 +2,13 @@
 or under other index cases (where the outbreak starts), one member after another on ONE context (esim_restart,
 esim_restart_seeded), summarised per step on the host and per Output Area -- or per citizen group -- on the device
 (esim_ensemble_*); or, as a forecast, as branches from one snapshot of a shared history (esim_snapshot, esim_rollback).  The
-population is validated, hashed and uploaded once."""
+population is validated, hashed and uploaded once per context: Ensemble(..., devices=(0, 1)) has a context per entry, each with
+a copy of the population, hands every context a contiguous block of the members (split_members) on a thread of its own and
+merges the contexts into the first (esim_ensemble_merge) -- the results are those of one context, bit for bit."""
+import copy
 import json
 import os
+import threading
 
 import numpy as np
 
@@ -677,26 +681,113 @@ def medoids(distances, k, max_swaps=1000):
     return {"medoid": np.asarray(chosen, np.int64), "label": label, "size": size, "cost": cost, "silhouette": sil}
 
 
+def split_members(n, k):
+    """The members 0 .. n - 1 as k contiguous blocks [(begin, end), ...] in order, sized as evenly as possible, the earlier
+    blocks the larger ones; with n < k the last blocks are empty."""
+    n, k = int(n), int(k)
+    if n < 0 or k < 1:
+        raise ValueError("split_members: n must be >= 0 and k >= 1, got %d and %d" % (n, k))
+    q, r = divmod(n, k)
+    ends = [i * q + min(i, r) for i in range(k + 1)]
+    return list(zip(ends[:-1], ends[1:]))
+
+
+def _check_devices(devices):
+    """devices of Ensemble(...) as a tuple of ordinals, before any context is created; None stays None."""
+    if devices is None:
+        return None
+    out = tuple(devices)
+    if not out:
+        raise ValueError("Ensemble: devices must name at least one device (None: one context on the device of params)")
+    for d in out:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d < 0:
+            raise ValueError("Ensemble: devices holds device ordinals >= 0, got %r" % (d,))
+    return tuple(int(d) for d in out)
+
+
 _KINDS = ("census", "arrival", "series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")
 _ROW_KINDS = ("series", "settings", "reproduction", "peaks", "burden_peaks", "burden_series")      # a member that stopped early has no rows behind its last step
 
 
 class Ensemble:
-    """Owns one Simulator; every member is a restart of it under the base parameters changed by the member's overrides."""
+    """Owns one Simulator -- or one per entry of `devices` --; every member is a restart of one of them under the base parameters
+    changed by the member's overrides."""
 
-    def __init__(self, population, params=None, area_codes=None, group=None, burden=None):
+    def __init__(self, population, params=None, area_codes=None, group=None, burden=None, devices=None):
         """group: None, or (labels, n_groups) for Simulator.set_groups -- what run(area=dict(where="group", ...)) counts by.
         burden: None, or the tables of _lib.burden_tables for Simulator.set_burden, set once for every member -- what
         run(area=dict(kind="burden_peaks", ...)) and run(area=dict(kind="burden_series", ...)) summarise and compare_burden()
-        compares (tables of several groups need `group` with as many)."""
-        self.simulator = Simulator(population, params, area_codes=area_codes)
-        if group is not None:
-            self.simulator.set_groups(*group)
-        if burden is not None:
-            self.simulator.set_burden(burden)
+        compares (tables of several groups need `group` with as many).
+        devices: None -- one context on the device of `params` --, or a sequence of device ordinals: one Simulator per entry,
+        each with its own upload of the population, groups and burden tables; repeats are allowed, (0, 0) is two contexts on one
+        device.  The first entry is self.simulator.  Every loop over members then hands each context a contiguous block of
+        them (split_members) on a thread of its own and merges the contexts into the first in block order."""
+        devices = _check_devices(devices)
+        self._others = []
         self.area_codes = area_codes
-        self.base = _lib.with_overrides(self.simulator.params, {})
         self._own_seeds = True            # the seeds in force are the uploaded population's
+        for k, device in enumerate(devices if devices is not None else (None,)):
+            p = params if device is None else _lib.with_overrides(params if params is not None else _lib.default_params(), {"device": device})
+            sim = Simulator(population, p, area_codes=area_codes)
+            if group is not None:
+                sim.set_groups(*group)
+            if burden is not None:
+                sim.set_burden(burden)
+            # (a context's base parameters carry its own device: esim_restart insists on it)
+            if k == 0:
+                self.simulator, self.base = sim, _lib.with_overrides(sim.params, {})
+            else:
+                lane = copy.copy(self)
+                lane.simulator, lane.base, lane._others = sim, _lib.with_overrides(sim.params, {}), []
+                self._others.append(lane)
+
+    def _lanes(self):
+        """The contexts as views of this Ensemble that differ in simulator, base and _own_seeds; the first is self."""
+        return [self] + list(getattr(self, "_others", ()))
+
+    def _each_member(self, members, body, prepare=None, merge=False):
+        """The one loop over members: body(lane, member, prepared) for every member, in member order on one context; on several,
+        block i of split_members on context i, each block on a thread of its own (the library calls release the GIL).
+        prepare(lane) runs once per context in front of its block.  An exception in one thread stops the others at their next
+        member and is raised once they have joined.  merge: the contexts' accumulators and kept members are then merged into
+        the first in block order (Simulator.ensemble_merge), so that kept slot i is member i.  Returns body's results stacked
+        in member order."""
+        lanes = self._lanes()
+        blocks = split_members(len(members), len(lanes))
+        out, errors, stop = [[] for _ in lanes], [], threading.Event()
+
+        def work(i):
+            try:
+                prepared = prepare(lanes[i]) if prepare is not None else None
+                for m in members[blocks[i][0]:blocks[i][1]]:
+                    if stop.is_set():
+                        return
+                    out[i].append(body(lanes[i], m, prepared))
+            except BaseException as e:          # (raised below, once every thread has joined)
+                errors.append((i, e))
+                stop.set()
+
+        active = [i for i in range(len(lanes)) if i == 0 or blocks[i][1] > blocks[i][0]]
+        if len(active) == 1:
+            work(0)
+        else:
+            threads = [threading.Thread(target=work, args=(i,)) for i in active]
+            for t in threads:
+                t.start()
+            for t in threads:
+                t.join()
+        if errors:
+            raise min(errors, key=lambda x: x[0])[1]
+        if merge and len(active) > 1:
+            for i in active[1:]:
+                self.simulator.ensemble_merge(lanes[i].simulator)
+            self.simulator.synchronize()        # (the merges have read the other contexts: those are free again)
+        return [row for rows in out for row in rows]
+
+    def _active_lanes(self, n_members):
+        """The contexts that get a member, with the size of their block: the first always."""
+        lanes = self._lanes()
+        return [(lane, e - b) for i, (lane, (b, e)) in enumerate(zip(lanes, split_members(n_members, len(lanes)))) if i == 0 or e > b]
 
     def _area_kind(self, who, area, n_steps, stop_when_done=False, n_members=None):
         """area of run() / forecast() checked, before anything runs: (kind, the area dict without its kind), or (None, None).
@@ -739,17 +830,19 @@ class Ensemble:
                 area["n_rows"] = n_rows
         return kind, area
 
-    def _begin(self, kind, area):
-        sim = self.simulator
-        if kind is not None:
-            getattr(sim, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
+    def _begin(self, kind, area, n_members=0):
+        for lane, _ in self._active_lanes(n_members) if kind is not None else ():
+            getattr(lane.simulator, {"census": "ensemble_begin", "arrival": "ensemble_begin_arrival", "series": "ensemble_begin_series",
                           "settings": "ensemble_begin_settings", "reproduction": "ensemble_begin_reproduction", "peaks": "ensemble_begin_peaks",
                           "burden_peaks": "ensemble_begin_burden_peaks", "burden_series": "ensemble_begin_burden_series"}[kind])(**area)
 
-    def _keep_begin(self, n_members):
-        """Behind the begin: the store of the quantile maps, where the area dict asked for them."""
-        if self._keep_spec is not None and n_members:
-            self.simulator.ensemble_keep_members(n_members, self._keep_spec["what"])
+    def _keep_begin(self, n_members, what=None):
+        """Behind the begin: the store of the quantile maps, where the area dict asked for them -- on the first context with
+        the capacity of all members, on the others with that of their block."""
+        what = self._keep_spec["what"] if what is None and self._keep_spec is not None else what
+        if what is not None and n_members:
+            for k, (lane, block) in enumerate(self._active_lanes(n_members)):
+                lane.simulator.ensemble_keep_members(n_members if k == 0 else block, what)
 
     def _keep_summary(self, summary, kind, n_members, area=None):
         """The summary with probs, quantiles, thresholds and exceed added: [n_q, n_rows, n_cols], [n_q, n_cols] for the kinds
@@ -881,13 +974,14 @@ class Ensemble:
         """What outbreaks() .. events() share: every member (as for run()) is restarted and run for n_steps steps, and what each
         of `calls` returns for the simulator then is kept.  Returns (members, one list per call)."""
         members = self._members(members)
-        out = [[] for _ in calls]
-        for m in members:
-            self._restart_member(m)
-            self.simulator.run(n_steps)
-            for rows, call in zip(out, calls):
-                rows.append(call(self.simulator))
-        return (members, *out)
+
+        def body(lane, m, _):
+            lane._restart_member(m)
+            lane.simulator.run(n_steps)
+            return [call(lane.simulator) for call in calls]
+
+        got = self._each_member(members, body)
+        return (members, *([row[k] for row in got] for k in range(len(calls))))
 
     def _group_cols(self, where):
         """The columns of the pair tables: the groups given to Ensemble(...) for where="group", else one."""
@@ -987,21 +1081,20 @@ class Ensemble:
         kind, area = self._area_kind("run", area, n_steps, stop_when_done, len(members))
         spec = self._settings_rows("run", settings, n_steps, stop_when_done)
         r_spec = self._reproduction_rows("run", reproduction, n_steps, stop_when_done)
-        sim = self.simulator
-        self._begin(kind, area)
+        self._begin(kind, area, len(members))
         self._keep_begin(len(members))
-        rows, n_done, by_setting, by_cohort = [], [], [], []
-        for m in members:
-            self._restart_member(m)
+
+        def body(lane, m, _):
+            sim = lane.simulator
+            lane._restart_member(m)
             rec = sim.run(n_steps, stop_when_done=stop_when_done)
             if area is not None:
                 sim.ensemble_fold()
-            if spec is not None:
-                by_setting.append(sim.setting_series("setting", **spec))
-            if r_spec is not None:
-                by_cohort.append(self._reproduction_of_member(r_spec))
-            n_done.append(len(rec))
-            rows.append(pad_records(rec, n_steps))
+            return (len(rec), pad_records(rec, n_steps), sim.setting_series("setting", **spec) if spec is not None else None,
+                    lane._reproduction_of_member(r_spec) if r_spec is not None else None)
+
+        got = self._each_member(members, body, merge=area is not None)
+        n_done, rows, by_setting, by_cohort = ([g[k] for g in got] for k in range(4))
         records = _stack(rows, (n_steps,), RECORD_DTYPE)
         summary = self._keep_summary(self._summary(kind, area), kind, len(members), area)
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
@@ -1018,34 +1111,39 @@ class Ensemble:
         kind, area = self._area_kind("forecast", area, n_steps, False, len(members))
         spec = self._settings_rows("forecast", settings, n_steps)
         r_spec = self._reproduction_rows("forecast", reproduction, n_steps)
-        sim = self.simulator
         history_steps, n_steps = int(history_steps), int(n_steps)
         if not 1 <= history_steps <= n_steps:
             raise ValueError("Ensemble.forecast: history_steps must be in 1..n_steps")
         if any("index_cases" in m for m in members):
             raise ValueError("Ensemble.forecast: a branch cannot change the index cases of the shared history")
-        self._begin(kind, area)
+        self._begin(kind, area, len(members))
         self._keep_begin(len(members))
-        sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
-        self._own_seeds = True
-        history = sim.run(history_steps)
-        sim.snapshot()
-        rows, n_done, by_setting, by_cohort = [], [], [], []
-        for m in members:
+
+        def body(lane, m, history):
+            sim = lane.simulator
             sim.rollback(**m)
             rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
             if area is not None:
                 sim.ensemble_fold()
-            if spec is not None:
-                by_setting.append(sim.setting_series("setting", **spec))
-            if r_spec is not None:
-                by_cohort.append(self._reproduction_of_member(r_spec))
-            n_done.append(len(history) + len(rec))
-            rows.append(pad_records(np.concatenate([history, rec]), n_steps))
+            return (len(history) + len(rec), pad_records(np.concatenate([history, rec]), n_steps), sim.setting_series("setting", **spec) if spec is not None else None,
+                    lane._reproduction_of_member(r_spec) if r_spec is not None else None)
+
+        # (the history is run and kept on every context: it is deterministic, so the contexts' histories are identical)
+        got = self._each_member(members, body, prepare=lambda lane: lane._shared_history(history_steps), merge=area is not None)
+        n_done, rows, by_setting, by_cohort = ([g[k] for g in got] for k in range(4))
         records = _stack(rows, (n_steps,), RECORD_DTYPE)
         summary = self._keep_summary(self._summary(kind, area), kind, len(members), area)
         return EnsembleResult(records, n_done, members, summary, self._codes(area), self._settings_stack(by_setting, spec),
                               self._reproduction_stack(by_cohort, r_spec), kind)
+
+    def _shared_history(self, history_steps):
+        """The base run of history_steps steps made on this context and kept on the device (Simulator.snapshot); its records."""
+        sim = self.simulator
+        sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
+        self._own_seeds = True
+        history = sim.run(history_steps)
+        sim.snapshot()
+        return history
 
     _FIXED_BY_HISTORY = ("exposed_time", "infected_time", "start_hour", "end_hour")
 
@@ -1077,10 +1175,12 @@ class Ensemble:
             rows = dict(rows)
             first, n_rows, stride = sim._compare_rows("Ensemble.compare", rows.get("first_step", 0), rows.get("n_rows"), rows.get("stride", 24), n_steps)
             rows.update(first_step=first, n_rows=n_rows, stride=stride)
-            sim.ensemble_begin_paired(where, **rows)
-            if keep is not None and members:
-                sim.ensemble_keep_members(len(members))
-        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, sim.keep_baseline, lambda: sim.compare(where, 0, n_steps), rows is not None)
+            for lane, _ in self._active_lanes(len(members)):
+                lane.simulator.ensemble_begin_paired(where, **rows)
+            if keep is not None:
+                self._keep_begin(len(members), "value")
+        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, lambda s: s.keep_baseline(), lambda s: s.compare(where, 0, n_steps),
+                                                    rows is not None)
         summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
         codes = self.area_codes if place == _lib.AREA_HOME else None
         out = CompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, codes)
@@ -1109,33 +1209,32 @@ class Ensemble:
 
     def _paired_members(self, baseline, policy, members, n_steps, history_steps, keep, table, fold):
         """The member loop compare() and compare_burden() share, behind their begins: the shared history once where asked for;
-        then per member the baseline arm, keep(), the policy arm, table() -- gathered -- and, with `fold`, the fold into the
-        accumulators in force.  Returns (the tables, the padded records of the baseline arms, of the policy arms)."""
-        sim = self.simulator
-        history = np.zeros(0, RECORD_DTYPE)
-        if history_steps is not None:
-            sim.restart(self.base, seeds=None if self._own_seeds else sim.population.seeds)
-            self._own_seeds = True
-            history = sim.run(history_steps)
-            sim.snapshot()
+        then per member the baseline arm, keep(simulator), the policy arm, table(simulator) -- gathered -- and, with `fold`, the
+        fold into the accumulators in force.  Returns (the tables, the padded records of the baseline arms, of the policy arms)."""
+        def prepare(lane):
+            return np.zeros(0, RECORD_DTYPE) if history_steps is None else lane._shared_history(history_steps)
 
-        def arm(over, m):
+        def arm(lane, history, over, m):
+            sim = lane.simulator
             if history_steps is None:
-                self._restart_member(dict(over, **m))
+                lane._restart_member(dict(over, **m))
                 return sim.run(n_steps)
             sim.rollback(**dict(over, **m))
             rec = sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)
             return np.concatenate([history, rec])
 
-        tables, rec_b, rec_p = [], [], []
-        for m in members:
-            rec_b.append(pad_records(arm(baseline, m), n_steps))
-            keep()
-            rec_p.append(pad_records(arm(policy, m), n_steps))
-            tables.append(table())
+        def body(lane, m, history):
+            sim = lane.simulator
+            rec_b = pad_records(arm(lane, history, baseline, m), n_steps)
+            keep(sim)
+            rec_p = pad_records(arm(lane, history, policy, m), n_steps)
+            got = table(sim)
             if fold:
                 sim.ensemble_fold()
-        return tables, rec_b, rec_p
+            return got, rec_b, rec_p
+
+        got = self._each_member(members, body, prepare=prepare, merge=fold)
+        return tuple([g[k] for g in got] for k in range(3))
 
     def compare_burden(self, baseline, policy, members, n_steps, history_steps=None, where="all", what="occupancy", rows=None, quantiles=None):
         """compare() for the hospital burden under the tables of Ensemble(..., burden=...): every member is run under `baseline`,
@@ -1166,11 +1265,12 @@ class Ensemble:
             if n_rows is None:
                 n_rows = (n_steps - first) // stride + 1 if stride > 0 and 1 <= first <= n_steps else 0
             rows.update(first_step=first, n_rows=int(n_rows), stride=stride)
-            sim.ensemble_begin_burden_paired(where, what, **rows)
-            if keep is not None and members:
-                sim.ensemble_keep_members(len(members))
-        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, sim.keep_burden_baseline,
-                                                    lambda: sim.burden_compare(where, 1, n_steps), rows is not None)
+            for lane, _ in self._active_lanes(len(members)):
+                lane.simulator.ensemble_begin_burden_paired(where, what, **rows)
+            if keep is not None:
+                self._keep_begin(len(members), "value")
+        tables, rec_b, rec_p = self._paired_members(baseline, policy, members, n_steps, history_steps, lambda s: s.keep_burden_baseline(),
+                                                    lambda s: s.burden_compare(where, 1, n_steps), rows is not None)
         summary = None if rows is None else paired_summary(sim.ensemble_read_paired(), rows["first_step"], rows["stride"])
         codes = self.area_codes if place == _lib.AREA_HOME else None
         out = BurdenCompareResult.gathered(members, tables, rec_b, rec_p, sim._compare_cols(place), n_steps, summary, where, what, codes)
@@ -1180,4 +1280,5 @@ class Ensemble:
         return out
 
     def close(self):
-        self.simulator.close()
+        for lane in self._lanes():
+            lane.simulator.close()

@@ -12,7 +12,8 @@
  * never unwinds across the boundary; esim_last_error() gives the text.  The caller
  * owns every buffer it passes (the library copies in/out and retains no host
  * pointer).  A context is used from one host thread at a time (the reference
- * `Simulator` is !Send: it owns a ThreadRng, simulator.rs:102).  All compute runs
+ * `Simulator` is !Send: it owns a ThreadRng, simulator.rs:102); any number of
+ * contexts may be used at once, each from its own thread.  All compute runs
  * on the GPU; there is no CPU fallback -- without a usable HIP device
  * esim_create() fails with ESIM_ENODEVICE.
  */
@@ -1095,6 +1096,45 @@ int  esim_ensemble_band(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, uint
 int  esim_ensemble_distances(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows, int metric, uint32_t never_as,
                              uint64_t *out /* [kept * kept] or NULL */, uint64_t *live_cells /* may be NULL */);
 int  esim_ensemble_distances_info(esim_ctx *ctx, uint64_t *tiles, uint64_t *tiles_32bit, uint64_t *tiles_partial);
+
+/* Ensembles on several contexts: the unit of parallelism of an ensemble is the member.  Several contexts -- on several
+ * devices, or several on one -- each upload the population, make the same begin (and the same esim_ensemble_keep_members) and
+ * fold their share of the members; merging them gives, bit for bit, the ensemble folded in sequence on one context, because every
+ * accumulator is an integer count or sum.  Every statistic behind the accumulators and the kept members works on the result
+ * unchanged.  The contexts share nothing.
+ * merge: adds every accumulator of src's kind in force into dst's (the counters and sums the kind owns and the member counter),
+ *        appends src's kept members behind dst's in their order, adds src's folds to dst's, and leaves src exactly as it was.  A
+ *        member's temporaries (the row planes, the series engine's small buffers) are not merged.  Both contexts must describe
+ *        the same ensemble: the kind, where, n_rows, n_cols, every parameter of the begin, the population without its seeds and
+ *        its number of citizens, by group the number of groups and their sizes, for the burden kinds the severity tables in
+ *        force, and the store -- none on both sides, or the same `what` on both.  Checked on the host before anything is
+ *        enqueued; a refused call leaves both contexts untouched:
+ *          ESIM_EINVAL  a null context, dst == src
+ *          ESIM_ESTATE  no upload or no begin in force on either side; a descriptor that differs (esim_last_error of dst names the
+ *                       first field that does); a communicator of several ranks or a shard (the rule of esim_restart)
+ *          ESIM_ERANGE  dst keeps more members with src's than its store takes
+ *        A src without a member folded is a valid call that changes nothing.  The call waits for src's stream on the host, then
+ *        enqueues on dst's stream and does not wait for it: src's accumulators and kept members must stay as they are (no fold,
+ *        begin, upload or destroy on src) until dst has been waited for -- any read-out of dst, or esim_synchronize.  After a
+ *        HIP failure mid-way the call returns ESIM_ENODEVICE and dst's accumulators are undefined until its next begin.
+ *        src's accumulators come to dst's device piece by piece through a staging buffer of bounded size that dst keeps
+ *        (hipMemcpyPeerAsync; between two contexts of one device that is a device-to-device copy).
+ * save_size, save:  the ensemble in force as bytes -- a magic word, a version, the descriptor above, members, folds and kept, the
+ *        accumulators, the kept planes; little-endian.  ESIM_ESTATE as merge; ESIM_ERANGE for a buffer smaller than save_size.
+ *        save waits for the stream.
+ * load:  a merge from bytes: it needs a begin of the same descriptor in force and ADDS.  Behind a fresh begin (and
+ *        esim_ensemble_keep_members where the blob has a store) it restores; an ensemble saved, loaded later and folded further is
+ *        the ensemble folded without the break.  No length is taken from the blob on trust: `bytes` must be exactly what the
+ *        descriptor in force implies with the blob's kept members.  ESIM_EINVAL for a buffer that is no blob of this version,
+ *        is truncated or longer, or was saved from another ensemble (the codes of esim_checkpoint_restore); ESIM_ERANGE when
+ *        the store in force has no room for the blob's members; ESIM_ESTATE as merge.  A refused call leaves the context
+ *        untouched.  It waits for the stream before it returns: the buffer is the caller's again.
+ * Threads: one host thread at a time per context, any number of contexts at once -- contexts hold no state in common, and every
+ * entry point makes its context's device current for the calling thread.  A merge uses both of its contexts. */
+int  esim_ensemble_merge(esim_ctx *dst, esim_ctx *src);
+int  esim_ensemble_save_size(esim_ctx *ctx, size_t *bytes);
+int  esim_ensemble_save(esim_ctx *ctx, void *buf, size_t cap);
+int  esim_ensemble_load(esim_ctx *ctx, const void *buf, size_t bytes);
 
 /* Hospital burden: admissions, bed occupancy and deaths laid over a finished run.  In the model's SEIR(+V) rules
  * nothing that happens to a case after its onset feeds back into transmission, so severity is drawn after the fact, one Philox
