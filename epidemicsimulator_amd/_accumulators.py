@@ -387,3 +387,28 @@ class _Accumulators:
         t = [C.c_uint64(0) for _ in range(3)]
         _lib.check(self.lib.esim_ensemble_distances_info(self._ctx, *(C.byref(x) for x in t)), self._ctx)
         return dict(zip(("tiles", "tiles_32bit", "tiles_partial"), (int(x.value) for x in t)))
+
+    # -- policy grids: the members kept read as replicates of arms run on common random numbers (esim_ensemble_arms) -------
+    def ensemble_arms(self, n_arms, maximize=False, never_as=None, first_row=0, n_rows=None):
+        """{"best", "sole": uint32 [n_arms, n, n_cols], "regret", "sum": uint64 [n_arms, n, n_cols], "totals": uint64 [replicates,
+        n_arms], "live_cells": int, "replicates": int, "maximize": bool}: the members kept read as replicates of n_arms arms, slot = replicate *
+        n_arms + arm -- the arms of a replicate folded one after the other under the same seed and index cases --, compared on the
+        device over the rows [first_row, first_row + n) of the store and all columns (esim_ensemble_arms; the kinds without rows
+        have one row, as in ensemble_quantiles).  Per cell and arm: best, the replicates in which the arm holds the smallest value
+        of its replicate (the largest with maximize=True; ties all count); sole, those in which no other arm does; regret, the sum
+        over the replicates of the distance to the best arm of the same replicate; sum, the arm's sum.  totals: every run's sum
+        over the whole window (modulo 2^64).  never_as: what _lib.NEVER counts as in the stores that hold it (arrival, peak_step)
+        -- the horizon, say; None leaves it as it is.  live_cells: the cells the accumulators do not settle, which the kernel read.
+        The library refuses 0 or more than 16 arms, a number of members kept that is no multiple of n_arms, and the signed store
+        of the paired kinds.  n_rows=None: all from first_row on."""
+        a = int(n_arms)
+        kept = self.ensemble_members_info()["kept"]
+        first_row, n, _ = self._members_planes(0, first_row, n_rows)
+        cols = int(getattr(self, "_ens_n", self.population.n_areas))
+        width = min(max(a, 0), _lib.ARMS_MAX)                       # (of the buffers, whatever the library then says to n_arms)
+        out = zeros(("best", "sole", "regret", "sum"), (width, n, cols), u64=("regret", "sum"))
+        reps = kept // a if 0 < a <= _lib.ARMS_MAX and kept % a == 0 else 0
+        totals, live = np.zeros((reps, width), np.uint64), C.c_uint64(0)
+        _lib.check(self.lib.esim_ensemble_arms(self._ctx, a, int(bool(maximize)), _lib.NEVER if never_as is None else int(never_as), first_row, n,
+                                               *(ptr(out[k]) for k in ("best", "sole", "regret", "sum")), ptr(totals) if reps else None, C.byref(live)), self._ctx)
+        return dict(out, totals=totals, live_cells=int(live.value), replicates=reps, maximize=bool(maximize))

@@ -102,7 +102,7 @@ SYMBOLS = [
     "esim_burden_set", "esim_burden_drop", "esim_burden_get", "esim_burden_outcomes", "esim_burden_series", "esim_burden_summary", "esim_ensemble_begin_burden_peaks",
     "esim_burden_baseline_keep", "esim_burden_baseline_info", "esim_burden_baseline_drop", "esim_burden_baseline_read", "esim_burden_compare", "esim_burden_compare_series",
     "esim_ensemble_begin_burden_series", "esim_ensemble_begin_burden_paired",
-    "esim_ensemble_keep_members", "esim_ensemble_members_info", "esim_ensemble_read_members", "esim_ensemble_quantiles", "esim_ensemble_exceedance", "esim_ensemble_depth", "esim_ensemble_band", "esim_ensemble_distances", "esim_ensemble_distances_info", "esim_ensemble_merge", "esim_ensemble_save_size", "esim_ensemble_save", "esim_ensemble_load", "esim_enable_phase_timing", "esim_phase_timings",
+    "esim_ensemble_keep_members", "esim_ensemble_members_info", "esim_ensemble_read_members", "esim_ensemble_quantiles", "esim_ensemble_exceedance", "esim_ensemble_depth", "esim_ensemble_band", "esim_ensemble_distances", "esim_ensemble_distances_info", "esim_ensemble_arms", "esim_ensemble_merge", "esim_ensemble_save_size", "esim_ensemble_save", "esim_ensemble_load", "esim_enable_phase_timing", "esim_phase_timings",
     "esim_enable_kernel_timing", "esim_kernel_timings", "esim_set_small_step_limit", "esim_set_tiny_chunk_limit", "esim_small_kernel_timing", "esim_debug_counters", "esim_debug_launches",
     "esim_last_error", "esim_destroy",
     "esim_threshold_lut", "esim_synth_preset", "esim_synth_create", "esim_synth_create_shard", "esim_synth_free",
@@ -236,6 +236,8 @@ def load():
         "esim_ensemble_band": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p, _u32p, _u32p]),
         "esim_ensemble_distances": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "esim_ensemble_distances_info": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "esim_ensemble_arms": (C.c_int, [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "esim_ensemble_merge": (C.c_int, [vp, vp]),
         "esim_ensemble_save_size": (C.c_int, [vp, C.POINTER(C.c_size_t)]),
         "esim_ensemble_save": (C.c_int, [vp, vp, C.c_size_t]),
@@ -286,6 +288,7 @@ NO_LINEAGE = 0xFFFFFFFF               # ESIM_NO_LINEAGE: esim_transmission_chain
 MEMBERS_MAX, RANKS_MAX = 256, 16      # ESIM_MEMBERS_MAX, ESIM_RANKS_MAX: esim_ensemble_keep_members' capacity, ranks or thresholds a call
 KEEP_VALUE, KEEP_PEAK_STEP, KEEP_DURATION = range(3)   # ESIM_KEEP_*: `what` of esim_ensemble_keep_members
 DIST_L1, DIST_DIFFER = range(2)       # ESIM_DIST_*: `metric` of esim_ensemble_distances
+ARMS_MAX = 16                         # ESIM_ARMS_MAX: the arms of esim_ensemble_arms
 BURDEN_BINS = 64                      # ESIM_BURDEN_BINS: the most entries of a delay or stay CDF of esim_burden_set
 BURDEN_ADMISSIONS, BURDEN_OCCUPANCY, BURDEN_DEATHS = range(3)   # ESIM_BURDEN_*: `what` of esim_burden_series
 BURDEN_NAMES = ("admissions", "occupancy", "deaths")

@@ -22,6 +22,7 @@
 #include "esim_host_members.h"
 #include "esim_host_depth.h"
 #include "esim_host_dist.h"
+#include "esim_host_arms.h"
 #include "esim_host_merge.h"
 #include "esim_host_upload.h"
 #include "esim_host_run.h"

@@ -2,12 +2,14 @@
 // written into its slot of the store, for the kinds whose fold does not leave that value in a plane (the series and the settings
 // kind do: their slot is a copy of plane 0).  A lane owns its cells and every kernel loops with a grid stride.  Nothing here
 // writes simulation state or an accumulator.  esim_depth.h, the ranking of the kept members as whole curves, reads
-// the same store and comes in here beside it, and so does esim_dist.h, the members compared pair by pair.
+// the same store and comes in here beside it, and so do esim_dist.h, the members compared pair by pair, and
+// esim_arms.h, the members read as replicates of policy arms.
 #pragma once
 #include "esim_curves.h"
 #include "esim_members.h"
 #include "esim_depth.h"
 #include "esim_dist.h"
+#include "esim_arms.h"
 
 // esim_ensemble_begin: what k_ensemble_fold adds to `sum`, the citizens of the area or group whose status is in `mask`.
 __global__ __launch_bounds__(TPB) void k_members_keep_census(const uint32_t *counts, uint32_t n, uint32_t mask, uint32_t *slot)

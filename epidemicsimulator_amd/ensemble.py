@@ -681,6 +681,69 @@ def medoids(distances, k, max_swaps=1000):
     return {"medoid": np.asarray(chosen, np.int64), "label": label, "size": size, "cost": cost, "silhouette": sil}
 
 
+ARMS_CELL_KEYS = ("p_best", "p_sole", "expected_regret", "mean")                                  # of arms_summary: per arm and cell
+ARMS_OVERALL_KEYS = ("overall_p_best", "overall_p_sole", "overall_regret", "overall_mean", "overall_choice")   # ... per arm over the whole window
+ARMS_TABLE_KEYS = ("best", "sole", "regret", "sum", "totals")                                     # of Simulator.ensemble_arms
+
+
+def arms_summary(tables):
+    """From Simulator.ensemble_arms(): the decision figures of a grid of A policies run over S futures on common random numbers.
+    Per arm and cell, float64 in the shape of the tables: p_best = best / S, the share of the futures in which the arm is the
+    best one (ties all count); p_sole = sole / S, in which it alone is; expected_regret = regret / S, what choosing the arm costs
+    against the best arm of the same future; mean = sum / S.  From totals [S, A], every run's sum over the whole window, the
+    same four for the map as a whole, [A] each: overall_p_best, overall_p_sole, overall_regret, overall_mean -- the best arm of a
+    future is then the one with the smallest total (the largest where the tables were made with maximize=True) -- and
+    overall_choice, the arm of least overall regret, the smallest index on a tie (decided on the exact integer sums).  Beside
+    them replicates, n_arms and maximize.  NaN everywhere for S = 0."""
+    totals = np.asarray(tables["totals"], np.uint64)
+    s, a = int(totals.shape[0]), int(np.asarray(tables["best"]).shape[0])
+    maximize = bool(tables.get("maximize", False))
+    out = {"replicates": s, "n_arms": a, "maximize": maximize}
+    for name, key in zip(ARMS_CELL_KEYS, ("best", "sole", "regret", "sum")):
+        out[name] = _rate(tables[key], np.full(np.asarray(tables[key]).shape, s, np.float64))
+    t = [[int(v) for v in row] for row in totals.tolist()]          # exact: Python integers
+    best = [max(row) if maximize else min(row) for row in t]
+    n_best = [sum(1 for v in row if v == b) for row, b in zip(t, best)]
+    over_runs = lambda f: [sum(f(r, arm) for r in range(s)) for arm in range(a)]
+    regret = over_runs(lambda r, arm: abs(t[r][arm] - best[r]))
+    over = {"overall_p_best": over_runs(lambda r, arm: int(t[r][arm] == best[r])), "overall_p_sole": over_runs(lambda r, arm: int(t[r][arm] == best[r] and n_best[r] == 1)),
+            "overall_regret": regret, "overall_mean": over_runs(lambda r, arm: t[r][arm])}
+    for k, v in over.items():
+        out[k] = _rate(np.asarray([float(x) for x in v], np.float64), np.full(a, s, np.float64))
+    out["overall_choice"] = min(range(a), key=lambda arm: (regret[arm], arm)) if a else -1
+    return out
+
+
+class GridResult:
+    """What Ensemble.grid gathers: A policies run over the same S members -- seeds and index cases --, arm by arm."""
+
+    def __init__(self, policies, members, records, n_done, arms, tables, area=None, area_kind=None, area_codes=None):
+        self.policies = [dict(p) for p in policies]                  # the overrides of every arm
+        self.members = list(members)      # the overrides of every replicate
+        self.records = records            # structured [n_arms, members, n_steps]
+        self.n_done = np.asarray(n_done, np.uint32)                  # [n_arms, members]
+        self.arms = arms                  # arms_summary(tables)
+        self.tables = tables              # Simulator.ensemble_arms(): best, sole, regret, sum [n_arms, n_rows, n_cols] ([n_arms, n_cols] for the kinds without rows), totals
+        self.area = area                  # the summary of the kind as run() gives it, over ALL members x arms runs:
+        self.area_mixes_arms = True       # ... it mixes the arms
+        self.area_kind = area_kind
+        self.area_codes = area_codes
+
+    def dump(self, directory):
+        """ensemble_grid.npz: p_best, p_sole, expected_regret, mean per arm and cell; overall_p_best, overall_p_sole,
+        overall_regret, overall_mean per arm and overall_choice; the integer tables best, sole, regret, sum and totals
+        [replicates, n_arms]; replicates, n_arms, maximize, live_cells; steps for a kind over rows, and codes where area codes
+        name the columns."""
+        os.makedirs(directory, exist_ok=True)
+        arrays = {k: np.asarray(self.arms[k]) for k in ARMS_CELL_KEYS + ARMS_OVERALL_KEYS + ("replicates", "n_arms", "maximize")}
+        arrays.update({k: np.asarray(self.tables[k]) for k in ARMS_TABLE_KEYS + ("live_cells",)})
+        if self.area is not None and "steps" in self.area:
+            arrays["steps"] = self.area["steps"]
+        if self.area_codes is not None:
+            arrays["codes"] = np.asarray(self.area_codes)
+        np.savez(os.path.join(directory, "ensemble_grid.npz"), **arrays)
+
+
 def split_members(n, k):
     """The members 0 .. n - 1 as k contiguous blocks [(begin, end), ...] in order, sized as evenly as possible, the earlier
     blocks the larger ones; with n < k the last blocks are empty."""
@@ -1235,6 +1298,69 @@ class Ensemble:
 
         got = self._each_member(members, body, prepare=prepare, merge=fold)
         return tuple([g[k] for g in got] for k in range(3))
+
+    def grid(self, policies, members, n_steps, history_steps=None, area=None, maximize=False, never_as=None):
+        """A grid of policies over the same random futures: every member s (as for run(): a seed, index cases) is run once under
+        each of `policies` -- 1 to 16 override dicts on the base parameters, the arms --, arm after arm, and every run is folded
+        into the accumulators of `area` and kept on the device (Simulator.ensemble_keep_members): kept slot s * A + a is member
+        s under arm a.  The arms of a member share their random numbers, as the two runs of compare() do, so that they differ by
+        the policy alone.  Simulator.ensemble_arms then counts on the device, per cell, in how many futures each arm is the best
+        one -- the smallest value, the largest with maximize=True --, in how many it alone, and its regret against the best arm
+        of the same future; never_as is what _lib.NEVER counts as for the arrival kind and for peaks with keep="peak_step".
+        area: an area dict as for run(), of any kind but "reproduction" (a ratio per cell is not kept); required.  At most 256
+        runs, members x arms.  history_steps: None, or the steps of a shared history run once under the base parameters and
+        kept (Simulator.snapshot); every run is then a branch from it, under the rules of compare(): no "index_cases" in a
+        member, no other times or working hours in a policy.  "index_cases" in a policy is refused either way: they belong to
+        the member.  On several contexts (devices=) each takes a contiguous block of members with all their arms, and the merge
+        keeps the slots in order.  Returns a GridResult: records [n_arms, members, n_steps], arms (arms_summary), tables, and
+        area, the summary of the kind over all runs -- which mixes the arms."""
+        who = "Ensemble.grid"
+        policies = [dict(p) for p in policies]
+        n_steps = int(n_steps)
+        if not 1 <= len(policies) <= _lib.ARMS_MAX:
+            raise ValueError("%s: policies holds 1 to %d override dicts (ESIM_ARMS_MAX), got %d" % (who, _lib.ARMS_MAX, len(policies)))
+        members = self._members(members)
+        if not members:
+            raise ValueError("%s: no members" % who)
+        n_arms, n_runs = len(policies), len(policies) * len(members)
+        if n_runs > _lib.MEMBERS_MAX:
+            raise ValueError("%s: %d members x %d policies are %d runs, the store takes %d (ESIM_MEMBERS_MAX)" % (who, len(members), n_arms, n_runs, _lib.MEMBERS_MAX))
+        for p in policies:
+            history_steps = self._paired_check(who, p, p, members, n_steps, history_steps)[3]
+        if area is None:
+            raise ValueError("%s: area is required (the cells the arms are compared in)" % who)
+        if dict(area).get("kind", "census") == "reproduction":
+            raise ValueError("%s: the reproduction kind keeps no members (a ratio per cell is out of scope)" % who)
+        kind, area = self._area_kind("grid", area, n_steps, False, n_runs)
+        what = self._keep_spec["what"] if self._keep_spec is not None else "value"
+        self._begin(kind, area, len(members))
+        for k, (lane, block) in enumerate(self._active_lanes(len(members))):
+            lane.simulator.ensemble_keep_members((len(members) if k == 0 else block) * n_arms, what)
+
+        def prepare(lane):
+            return np.zeros(0, RECORD_DTYPE) if history_steps is None else lane._shared_history(history_steps)
+
+        def body(lane, m, history):
+            sim, rows = lane.simulator, []
+            for p in policies:
+                if history_steps is None:
+                    lane._restart_member(dict(p, **m))
+                    rec = sim.run(n_steps)
+                else:
+                    sim.rollback(**dict(p, **m))
+                    rec = np.concatenate([history, sim.run(n_steps - history_steps) if n_steps > history_steps else np.zeros(0, RECORD_DTYPE)])
+                sim.ensemble_fold()
+                rows.append((len(rec), pad_records(rec, n_steps)))
+            return rows
+
+        got = self._each_member(members, body, prepare=prepare, merge=True)
+        records = np.stack([_stack([g[a][1] for g in got], (n_steps,), RECORD_DTYPE) for a in range(n_arms)])
+        n_done = np.asarray([[g[a][0] for g in got] for a in range(n_arms)], np.uint32)
+        tables = self.simulator.ensemble_arms(n_arms, maximize, never_as)
+        if kind in ("census", "arrival", "peaks", "burden_peaks"):  # the kinds without rows: [n_arms, n_cols]
+            tables.update({k: tables[k][:, 0] for k in ("best", "sole", "regret", "sum")})
+        summary = self._keep_summary(self._summary(kind, area), kind, n_runs, area)
+        return GridResult(policies, members, records, n_done, arms_summary(tables), tables, summary, kind, self._codes(area))
 
     def compare_burden(self, baseline, policy, members, n_steps, history_steps=None, where="all", what="occupancy", rows=None, quantiles=None):
         """compare() for the hospital burden under the tables of Ensemble(..., burden=...): every member is run under `baseline`,

@@ -1097,6 +1097,39 @@ int  esim_ensemble_distances(esim_ctx *ctx, uint32_t first_row, uint32_t n_rows,
                              uint64_t *out /* [kept * kept] or NULL */, uint64_t *live_cells /* may be NULL */);
 int  esim_ensemble_distances_info(esim_ctx *ctx, uint64_t *tiles, uint64_t *tiles_32bit, uint64_t *tiles_partial);
 
+/* Policy grids: the members kept by esim_ensemble_keep_members read as a grid of n_arms policies run over
+ * S = kept / n_arms random futures on common random numbers -- the draws are a function of (seed, citizen, step, slot), so the
+ * arms of one replicate share theirs.  The store is read replicate-major, arms adjacent: slot = s * n_arms + a, the order in
+ * which the arms of one replicate are folded one after the other and which a merge of contiguous blocks of replicates keeps.
+ * For a cell (r, c) of the window of rows [first_row, first_row + n_rows) and all columns, k[s][a] is the key of slot
+ * s * n_arms + a there and b[s] the smallest of k[s][.], the largest with maximize = 1.
+ * never_as:  for the stores in which ESIM_NEVER occurs (arrival, the step of the peak) a key equal to ESIM_NEVER is replaced by
+ *        never_as first, the rule of esim_ensemble_distances; ESIM_NEVER leaves it as it is.  Ignored by every other store.
+ * best, sole, regret, sum:  indexed [(a * n_rows + r) * n_cols + c], each may be NULL.
+ *        best    the replicates s with k[s][a] == b[s]; ties all count, so the arms of a cell may sum to more than S.
+ *        sole    those of them in which no other arm attains b[s]: sole <= best, the arms' sole sum to at most S; with
+ *                n_arms = 1, sole = best = S.
+ *        regret  the sum over s of |k[s][a] - b[s]|, in 64 bits: what choosing arm a costs against the best arm of the same future.
+ *        sum     the sum over s of k[s][a], in 64 bits.  best / S, sole / S, regret / S and sum / S are P(best), P(best alone),
+ *                the expected regret and the mean of the arm.
+ * totals:  may be NULL; totals[s * n_arms + a] is the sum of k[s][a] over ALL cells of the window, in 64 bits modulo 2^64: the
+ *        whole-map figure per run, from which the pooled P(best) and the pooled regret follow on the host.
+ * live_cells:  may be NULL; the cells of the window that the accumulators do not settle, as esim_ensemble_distances reports
+ *        them.  A settled cell (every member holds the same key) is not read: best = S, sole = 0 (S with one arm), regret = 0,
+ *        sum = S times the key, and the key in every member's total.
+ *        Decided on the host before anything is enqueued: ESIM_EINVAL for n_arms 0 or above ESIM_ARMS_MAX or maximize not 0 or
+ *        1; ESIM_ESTATE without a store, with nothing kept, or with a SIGNED store (the paired kinds are a difference of two
+ *        arms already: a grid of them has no meaning); ESIM_ERANGE for rows outside the store or kept % n_arms != 0.
+ *        n_rows == 0 gives zeros.  With every output NULL the call still validates.  It waits for the stream and leaves the
+ *        accumulators and the store as they are; its tables on the device go when it returns. */
+#define ESIM_ARMS_MAX 16
+int  esim_ensemble_arms(esim_ctx *ctx, uint32_t n_arms, int maximize, uint32_t never_as,
+                        uint32_t first_row, uint32_t n_rows,
+                        uint32_t *best, uint32_t *sole,          /* [n_arms * n_rows * n_cols] each, or NULL */
+                        uint64_t *regret, uint64_t *sum,         /* [n_arms * n_rows * n_cols] each, or NULL */
+                        uint64_t *totals,                        /* [kept] or NULL */
+                        uint64_t *live_cells);                   /* may be NULL */
+
 /* Ensembles on several contexts: the unit of parallelism of an ensemble is the member.  Several contexts -- on several
  * devices, or several on one -- each upload the population, make the same begin (and the same esim_ensemble_keep_members) and
  * fold their share of the members; merging them gives, bit for bit, the ensemble folded in sequence on one context, because every
